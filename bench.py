@@ -14,8 +14,12 @@ backward -> gradient exchange -> fused Adam.
 Workload = BASELINE.json configs[1]: item vocab 100k, d_model 128, 4 layers, 4 heads, seq 20,
 per-GPU batch 1024 (weak scaling: global batch 1024*N; 8192 at N=8), MLM p=0.15, fp32, every
 reference dropout site active (p = 0.3).
-Prints ONE JSON line on rank 0: the metric/value contract + `roofline` (+ `roofline_gather`) +
-`cpu_baseline` + `recall_at_20` (the other half of BASELINE.json's metric).
+Prints ONE JSON line on rank 0.  A plain run sets up, pre-heats, warms up, times the K steps and prints the
+metric/value contract (`value`, `ms_per_step`, `config`, `comm`) and nothing else.  `--full` adds everything that takes
+runs of its own: the spread over more timed windows, `roofline` (+ `roofline_gather`, `roofline_body`), the 8-GPU
+exchange rehearsal, `cpu_baseline` and `recall_at_20` (the other half of BASELINE.json's metric).
+`--dump-outputs DIR` writes what the last timed step computed (loss, labels, a fixed row sample of the logits, the
+parameters after its optimizer step) as DIR/<name>.npy, so that two builds can be compared output for output.
 
 Data-parallel wiring (N > 1): the table bucket's dense part (the tied head's d W) is final right after
 the head's backward: its all-reduce is launched there, on its own stream, under the transformer's
@@ -238,6 +242,54 @@ def extra_windows(train_step, steps, world, device, first_step, n_windows=5):
     srt = sorted(ms)
     return {"n_windows": n_windows, "steps_per_window": steps, "min": round(srt[0], 4), "median": round(srt[len(srt) // 2], 4),
             "max": round(srt[-1], 4), "all": [round(x, 4) for x in ms]}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_LOGIT_ROWS = 64        # label rows of the [N, V] logits kept (all V columns)
+DUMP_TABLE_ROWS = 4096      # rows kept of a parameter table larger than DUMP_TABLE_FULL_BYTES
+DUMP_TABLE_FULL_BYTES = 4 << 20
+
+
+def dump_outputs(path, out, flats, seed=0):
+    """--dump-outputs: what the last timed step computed, as <path>/<name>.npy (float32, or float64 where the values are
+    integers): `loss`, `labels`, a fixed seeded row sample of `predictions` (+ the row indices), and every parameter
+    bucket after the step's optimizer update (`params<i>`, dense buckets whole; a table larger than 4 MB as a fixed seeded
+    row sample + its row indices).  The samples depend only on the shapes and `seed`, so two builds with the same arguments
+    dump the same positions.  -> {name: shape}"""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    arrays = {"loss": out["loss"].detach().float().reshape(1).cpu().numpy()}
+    if "labels" in out:
+        arrays["labels"] = out["labels"].detach().cpu().numpy().astype(np.float64)
+    pred = out.get("predictions")
+    if pred is not None:
+        if not isinstance(pred, torch.Tensor):
+            pred = pred.materialize()           # a non-materialising head: the logits are computed on request
+        rows = np.sort(rng.choice(pred.shape[0], min(DUMP_LOGIT_ROWS, pred.shape[0]), replace=False))
+        arrays["predictions_rows"] = rows.astype(np.float64)
+        arrays["predictions"] = pred.detach()[torch.from_numpy(rows).to(pred.device)].float().cpu().numpy()
+    for i, f in enumerate(flats):
+        entries = [(n, p) for n, p, _ in f.entries] if hasattr(f, "entries") else [("", f.data)]
+        small = [p for _, p in entries if p.numel() * 4 <= DUMP_TABLE_FULL_BYTES or p.ndim != 2]
+        if len(small) == len(entries):
+            arrays[f"params{i}"] = f.data.detach().float().cpu().numpy()
+            continue
+        for j, (_, p) in enumerate(entries):
+            name = f"params{i}_{j}"
+            if p.numel() * 4 <= DUMP_TABLE_FULL_BYTES or p.ndim != 2:
+                arrays[name] = p.detach().float().cpu().numpy()
+                continue
+            rows = np.sort(rng.choice(p.shape[0], min(DUMP_TABLE_ROWS, p.shape[0]), replace=False))
+            arrays[name + "_rows"] = rows.astype(np.float64)
+            arrays[name] = p.detach()[torch.from_numpy(rows).to(p.device)].float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes, more than the {DUMP_LIMIT_BYTES} allowed")
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 # --------------------------------------------------------------------------------------------- CPU leg
@@ -897,18 +949,23 @@ def _stub_main(args, world, rank):
         raise SystemExit(f"process group has {dist.get_world_size()} ranks, --gpus says {args.gpus}")
     step = make_train_step(model, batches, reducer, _Sgd())
     dt, out, n_lab = timed_region(step, args.warmup, args.steps, world, "cpu")
-    windows = extra_windows(step, args.steps, world, "cpu", args.warmup + args.steps, n_windows=2)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, (dense, tables))
+    windows = extra_windows(step, args.steps, world, "cpu", args.warmup + args.steps, n_windows=2) if args.full else None
     if rank == 0:
-        print(json.dumps({"metric": "launch-plumbing stub (no GPU, not a measurement)", "stub": True,
-                          "value": round(16 * world * args.steps / dt, 1), "unit": "sessions/s", "n_gpus": world,
-                          "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 4),
-                          "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-                          "ms_per_step_windows": windows, "comm": {"table_exchange_ms_per_step": exchange_ms},
-                          "data": "synthetic", "config": {"workload": "stub", "global_batch": 16 * world,
-                                                          "parallelism": f"dp{world}", "table_exchange": exchange_mode,
-                                                          "world_size": world,
-                                                          "final_loss": round(float(out["loss"].detach()), 4),
-                                                          "label_rows": n_lab}}), flush=True)
+        res = {"metric": "launch-plumbing stub (no GPU, not a measurement)", "stub": True,
+               "value": round(16 * world * args.steps / dt, 1), "unit": "sessions/s", "n_gpus": world,
+               "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 4),
+               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "full": bool(args.full),
+               "comm": {"table_exchange_ms_per_step": exchange_ms},
+               "data": "synthetic", "config": {"workload": "stub", "global_batch": 16 * world,
+                                               "parallelism": f"dp{world}", "table_exchange": exchange_mode,
+                                               "world_size": world,
+                                               "final_loss": round(float(out["loss"].detach()), 4),
+                                               "label_rows": n_lab}}
+        if windows is not None:
+            res["ms_per_step_windows"] = windows
+        print(json.dumps(res), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -934,6 +991,12 @@ def main():
     ap.add_argument("--config", choices=("c2", "c3"), default="c2",
                     help="c2 = BASELINE.json configs[1] (the configuration `metric` is quoted on; default); "
                          "c3 = configs[2], the multi-feature input block on the same XLNet (the 8-GPU DP configuration)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure everything that takes runs of its own: more timed windows, the "
+                         "roofline / gather / body kernel probes, the live HBM traffic, the 8-GPU rehearsal, Recall@20 and the "
+                         "CPU baselines (the --no-* options above switch single legs of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1036,12 +1099,56 @@ def main():
     del snap
     dt, out, n_lab = timed_region(train_step, args.warmup, args.steps, world, device)
     loss = float(out["loss"].detach())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, opt.flats)     # before anything else runs a step
+    N_m = max(1, n_lab // max(1, args.steps))
+    W = model.input_features.item_embedding_table.weight.detach()
+    mode = ops.get_precision()
+    sparse = getattr(reducer, "sparse", None)
+
+    def comm_report(steps_run):
+        return {"dense_bucket_bytes": int(dense.grad.numel() * 4) if world > 1 else 0,
+                "tables_bucket_bytes": int(tables.grad.numel() * 4) if world > 1 and reducer.tables is not None else 0,
+                "row_sparse_gathered_bytes": int((sparse.bytes_exchanged if sparse is not None else 0) // max(1, steps_run)),
+                "table_exchange_ms_per_step": exchange_ms,
+                "note": "per rank and step; the tables all-reduce starts right after the head's backward and runs under the "
+                        "transformer body's backward; the dense bucket and the (ids, rows) all-gather are exposed"}
+
+    # the headline, the same on a plain and on a --full run
+    res = {
+        "metric": "training sessions/sec (XLNet 4x128, 100k items, seq 20, MLM, tied full softmax" +
+                  (", multi-feature input: item + 3 categoricals + 2 SoftEmbedding, concat" if args.config == "c3" else "") + ") + Recall@20",
+        "value": round(BATCH * world * args.steps / dt, 1), "unit": "sessions/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+        "data": "synthetic", "full": bool(args.full),
+        "config": {"workload": WORKLOADS[args.config],
+                   "global_batch": BATCH * world, "seq_len": SEQ, "parallelism": f"dp{world}",
+                   "dropout": args.dropout, "label_rows_per_step": N_m, "final_loss": round(loss, 4),
+                   "head_mode": model.prediction_task.resolve_head_mode(N_m, W.shape[0]),
+                   "precision_mode": mode, "table_exchange": exchange_mode, "world_size": world,
+                   "collective_backend": (backend if world > 1 else None),
+                   "nccl_max_nchannels": (os.environ.get("NCCL_MAX_NCHANNELS") if world > 1 else None),
+                   "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
+                   "extra_streams": args.extra_streams,
+                   "prefetch": int(os.environ.get("T4R_PREFETCH", "1")),
+                   "preheat_s": round(preheat_s, 2), "preheat_steps": n_pre,
+                   "timed_region_s": round(dt, 4)},
+    }
+    if not args.full:
+        if rank == 0:
+            res["comm"] = comm_report(n_pre + args.warmup + args.steps)
+            print(json.dumps(res), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: everything below takes runs of its own
     windows = extra_windows(train_step, args.steps, world, device, args.warmup + args.steps)
 
     # ---- roofline of the dominant kernel, measured live with HIP events on the launch stream
     # (the same GEMM launches the timed steps issue: logits = X[N_m,128] @ W[100001,128]^T)
-    N_m = max(1, n_lab // max(1, args.steps))
-    W = model.input_features.item_embedding_table.weight.detach()
     xr = torch.randn(N_m, D_MODEL, device=device)
     ld = ops.pad_ld(W.shape[0])
     buf = torch.empty((N_m, ld), device=device)
@@ -1061,7 +1168,6 @@ def main():
     # the step runs in the library's default precision mode ("auto": fp32-class accuracy -- the head and the body's token-tile
     # kernels on the two-way fp16 split with power-of-two scales, three matrix-core products per fp32-equivalent one; the
     # general GEMM's remaining large contractions on the exact 3-way bf16 split, six products); timed in both forms
-    mode = ops.get_precision()
     from transformers4rec_amd.prediction_task import _head_split_ok
 
     general_ms = timed(lambda: ops.gemm(xr, W, False, True, out=buf[:, : W.shape[0]]))
@@ -1320,34 +1426,9 @@ def main():
                        "v_mfma_f32_32x32x16_bf16 products per K=16)")
     else:
         kernel_desc = "gemm_f32_kernel<128,128,16,NT> (next-item logits X@W^T)"
-    sparse = getattr(reducer, "sparse", None)
-    comm = {"dense_bucket_bytes": int(dense.grad.numel() * 4) if world > 1 else 0,
-            "tables_bucket_bytes": int(tables.grad.numel() * 4) if world > 1 and reducer.tables is not None else 0,
-            "row_sparse_gathered_bytes": int((sparse.bytes_exchanged if sparse is not None else 0) //
-                                             max(1, n_pre + args.warmup + args.steps * (1 + windows["n_windows"]))),
-            "table_exchange_ms_per_step": exchange_ms,
-            "note": "per rank and step; the tables all-reduce starts right after the head's backward and runs under the "
-                    "transformer body's backward; the dense bucket and the (ids, rows) all-gather are exposed"}
+    comm = comm_report(n_pre + args.warmup + args.steps * (1 + windows["n_windows"]))
     if rank == 0:
-        res = {
-            "metric": "training sessions/sec (XLNet 4x128, 100k items, seq 20, MLM, tied full softmax" +
-                      (", multi-feature input: item + 3 categoricals + 2 SoftEmbedding, concat" if args.config == "c3" else "") + ") + Recall@20",
-            "value": round(BATCH * world * args.steps / dt, 1), "unit": "sessions/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": WORKLOADS[args.config],
-                       "global_batch": BATCH * world, "seq_len": SEQ, "parallelism": f"dp{world}",
-                       "dropout": args.dropout, "label_rows_per_step": N_m, "final_loss": round(loss, 4),
-                       "head_mode": model.prediction_task.resolve_head_mode(N_m, W.shape[0]),
-                       "precision_mode": mode, "table_exchange": exchange_mode, "world_size": world,
-                       "collective_backend": (backend if world > 1 else None),
-                       "nccl_max_nchannels": (os.environ.get("NCCL_MAX_NCHANNELS") if world > 1 else None),
-                       "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
-                       "extra_streams": args.extra_streams,
-                       "prefetch": int(os.environ.get("T4R_PREFETCH", "1")),
-                       "preheat_s": round(preheat_s, 2), "preheat_steps": n_pre,
-                       "timed_region_s": round(dt, 4)},
+        res.update({
             "ms_per_step_windows": windows,
             "roofline": {"kernel": kernel_desc,
                          # `achieved` / `frac` are ALGORITHMIC work over the live launch time against the roof that algorithmic work
@@ -1416,7 +1497,7 @@ def main():
                                     "avg_launch_ms": round(gather_c3_ms, 5), "bytes_per_launch": gather_c3_bytes,
                                     "note": "163 840 tokens, item table 10 000 001 x 128 (out of cache, 4 id sets rotated), the three "
                                             "small tables are cache resident"}},
-        }
+        })
         if body is not None:
             res["roofline_body"] = body
         if world == 1 and args.config == "c2":

@@ -35,6 +35,7 @@ import ref_standins as rs  # noqa: E402
 from ref_standins import ColumnSchema, Schema, Tags, _IntDomain, _ValueCount  # noqa: E402
 
 OUT = os.path.join(os.path.dirname(HERE), "tests", "golden")
+SHARD_BYTES = 900 * 1024          # compressed bytes per fixture file (the repository keeps every file under 1 MiB)
 
 
 class DrawRecorder:
@@ -189,6 +190,24 @@ def save(name, d, **meta):
     path = os.path.join(OUT, name + ".npz")
     np.savez_compressed(path, **d)
     print(f"{name}: {os.path.getsize(path) / 1024:.0f} KiB, loss={d.get('out/loss')}")
+    for f in os.listdir(OUT):                   # shards of an earlier run
+        if f.startswith(name + ".") and f != name + ".npz":
+            os.remove(os.path.join(OUT, f))
+    if os.path.getsize(path) > SHARD_BYTES:
+        # no file over 1 MiB in the repository: <name>.npz + <name>.1.npz, ... (tests/golden_utils.py merges them)
+        import zipfile
+
+        with zipfile.ZipFile(path) as z:
+            packed = {i.filename[:-4]: i.compress_size for i in z.infolist()}
+        shards, acc = [{}], 0
+        for k, v in d.items():
+            if shards[-1] and acc + packed[k] > SHARD_BYTES:
+                shards.append({})
+                acc = 0
+            shards[-1][k] = v
+            acc += packed[k]
+        for i, s in enumerate(shards):
+            np.savez_compressed(os.path.join(OUT, name + (".npz" if i == 0 else f".{i}.npz")), **s)
 
 
 def main():

@@ -212,7 +212,7 @@ def test_bench_main_two_ranks():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--steps", "6", "--warmup", "2", "--preheat-seconds", "0.5"]
+           "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--steps", "6", "--warmup", "2", "--preheat-seconds", "0.5", "--full"]
     run = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert run.returncode == 0, run.stderr[-3000:]
     line = json.loads(run.stdout.strip().splitlines()[-1])

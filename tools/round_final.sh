@@ -7,8 +7,8 @@ tag=${1:-fin}
 out=gpurun_out
 mkdir -p $out
 python -m pytest tests -m gpu -q 2>&1 | tail -5 > $out/${tag}_gputest.log
-python bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err
-python bench.py --config c3 --no-cpu-baseline > $out/${tag}_bench_c3.json 2>> $out/${tag}_bench.err
+python bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+python bench.py --full --config c3 --no-cpu-baseline > $out/${tag}_bench_c3.json 2>> $out/${tag}_bench.err
 bash tools/prof_stats.sh $tag > /dev/null 2>&1
 bash tools/prof_timeline.sh $tag > /dev/null 2>&1
 cd /tmp 2>/dev/null; export TMPDIR=/tmp; cd - >/dev/null

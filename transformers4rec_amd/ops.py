@@ -85,6 +85,9 @@ class precision:
 def gemm(a, b, trans_a=False, trans_b=False, alpha=1.0, bias=None, epilogue=EPI_NONE, out=None,
          aux=None, splitk=1, accumulate=False, ldc=None, drop=(0.0, 0, 0)):
     """out[M,N] = alpha * op(a) @ op(b) (+epilogue).  a, b 2-D row-major fp32."""
+    for t, name in ((a, "a"), (b, "b"), (out, "out"), (aux, "aux")):
+        if t is not None and not t.is_cuda:     # (strided views are fine here: _chk would demand contiguity)
+            raise _lib.T4RHipError(f"gemm: {name} must be a HIP device tensor (got {t.device}); there is no CPU path")
     M = a.shape[1] if trans_a else a.shape[0]
     K = a.shape[0] if trans_a else a.shape[1]
     N = b.shape[0] if trans_b else b.shape[1]
