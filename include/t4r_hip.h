@@ -595,6 +595,21 @@ int t4r_topk(void* stream, const float* scores, int N, int V, long ld, int k, fl
 int t4r_rank_of_target_f32(void* stream, int n_rows, int V, int D, float alpha, const float* X, long ldx,
                            const float* W, long ldw, const float* target_score, const long* labels,
                            int* rank);
+/* Fused top-k inference head (replaces the last-item scores model/prediction_task.py:664 + torch.topk :466-470 of a served
+ * model where the [n_rows, V] scores should not exist): out_val / out_idx [n_rows, k] = the k best items per row of
+ * alpha * X[n_rows, D] @ W[V, D]^T, values descending, ties to the lower index -- bit for bit what t4r_gemm_f32 in precision
+ * mode 0 followed by t4r_topk returns, for every input.  1 <= k <= min(256, V); any V, any D, any row pitches ldx / ldw >= D.
+ * One pass over W plus a small prologue (csrc/item_topk.hip): a strided sample of item rows gives every row a lower bound of
+ * its k-th largest score, the GEMM's collect epilogue appends the scores at or above it to per-row candidate lists in
+ * `workspace`, a select kernel ranks the lists.  Rows whose list overflowed (constant tables, thousands of duplicates) are
+ * recomputed through the materialised path inside the workspace; their count is read back, so the call synchronises `stream`
+ * once.  workspace: t4r_item_topk_ws_bytes(n_rows, V, D, k) bytes, 16-byte aligned, contents undefined on entry and exit.
+ * host_stats (HOST memory, 8 longs, may be null) receives what the call did: [0] rows that took the overflow path, [1] sampled
+ * item rows M, [2] candidate-list capacity per row, and -- only if host_stats[7] != 0 on entry (tools: one more [n_rows]
+ * device-to-host copy) -- [3] / [4] the sum / maximum over rows of the candidate counts.  The library keeps no record. */
+long t4r_item_topk_ws_bytes(int n_rows, int V, int D, int k);
+int t4r_item_topk_f32(void* stream, int n_rows, int V, int D, float alpha, const float* X, long ldx, const float* W,
+                      long ldw, int k, float* out_val, long* out_idx, void* workspace, long ws_bytes, long* host_stats);
 
 /* ----------------------------------------------------------------------------------------
  * train-time input regularisers (pre / post transformations of the input block)

@@ -130,6 +130,8 @@ _SIGS = {
     "t4r_sampled_logits_bwd_rows": ("i", "ppppppppp" + "iiif"),
     "t4r_topk": ("i", "pp" + "iili" + "pp"),
     "t4r_rank_of_target_f32": ("i", "p" + "iiif" + "pl" + "pl" + "ppp"),
+    "t4r_item_topk_ws_bytes": ("l", "iiii"),
+    "t4r_item_topk_f32": ("i", "p" + "iiif" + "pl" + "pl" + "i" + "pp" + "pl" + "p"),
     "t4r_swap_noise_ws_bytes": ("l", "l"),
     "t4r_swap_noise": ("i", "ppp" + "il" + "pllf" + "pp" + "QQ" + "pl"),
     "t4r_copy_cols": ("i", "pp" + "li" + "p" + "ili"),

@@ -23,6 +23,11 @@ static int launch_cfg(const GemmParams& p, int batch, hipStream_t stream) {
         t4r_set_error("gemm: the rank epilogue needs the 64x64 NT tile without split-K");
         return -1;
     }
+    if (p.tk_thr) {
+        if (BM == 64 && BN == 64 && !TA && TB && p.splitk == 1) return launch_feat<64, 64, BK, false, true, 8>(p, batch, stream);
+        t4r_set_error("gemm: the top-k collect epilogue needs the 64x64 NT tile without split-K");
+        return -1;
+    }
     if (p.drop.p > 0.f && (p.epilogue == EPI_BIAS_GELU || p.epilogue == EPI_BIAS_RESID)) {
         if (BM == 64 && BN == 64) return launch_feat<64, 64, BK, TA, TB, 2>(p, batch, stream);
         t4r_set_error("gemm: epilogue dropout needs the 64x64 tile");
@@ -150,7 +155,7 @@ extern "C" int t4r_gemm_splitk_sink_bypassed(void) { return g_sink.bypassed; }
 // a split-K launch asks for room: returns the partial buffer (and registers the jobs) or null (-> atomics)
 static float* splitk_sink_take(const GemmParams& p, int batch) {
     SplitKSink& k = g_sink;
-    if (!k.on || !p.accumulate || p.epilogue != EPI_NONE || p.sg_lse || p.rk_thr) return nullptr;
+    if (!k.on || !p.accumulate || p.epilogue != EPI_NONE || p.sg_lse || p.rk_thr || p.tk_thr) return nullptr;
     const long n = (long)p.M * p.ldc;                       // one partial = C's [M][ldc] image (dense outputs: ldc == N)
     if (p.ldc != p.N || n % 4 || ((uintptr_t)p.C & 15) || (p.sC % 4)) return nullptr;        // not a shape the sink takes
     if (k.jobs.n + batch > kMaxSplitKJobs) { ++k.bypassed; return nullptr; }
@@ -202,8 +207,11 @@ bool t4r_wgrad_units_ok(const GemmParams& p);
 int t4r_wgrad_units_launch(const GemmParams& p, int batch, int kper, float* part, hipStream_t st);
 #endif
 
+// force_fp32 (the fused top-k head only: t4r_gemm_fp32_nt_launch / t4r_gemm_topk_collect_launch): this launch runs form 0
+// whatever the process-wide mode says, so that its outputs carry the bits of the materialised fp32 scores
 template <bool TA, bool TB>
-static int launch_layout(GemmParams& p, int batch, int splitk_req, hipStream_t stream) {
+static int launch_layout(GemmParams& p, int batch, int splitk_req, hipStream_t stream, bool force_fp32 = false) {
+    auto launch_precision = [&]() { return force_fp32 ? 0 : t4r_get_precision(); };
     const float* amax_a = g_amax_a;
     const float* amax_b = g_amax_b;
     const int amax_n = g_amax_n, amax_nb = g_amax_nb;
@@ -234,7 +242,7 @@ static int launch_layout(GemmParams& p, int batch, int splitk_req, hipStream_t s
 #endif
     // tokens x small weight in an fp32-accurate mode: the token-stationary kernel (operands cut once, tok_gemm.hip)
     if (!TA && (splitk_req == 0 || splitk_req == 1)) {
-        const int mode = t4r_get_precision();
+        const int mode = launch_precision();
         if (mode == 4 || mode == 1) {
             p.splitk = 1;
             const int rc = t4r_tok_gemm_try(p, batch, TA, TB, stream);
@@ -252,7 +260,7 @@ static int launch_layout(GemmParams& p, int batch, int splitk_req, hipStream_t s
     if (tile_sel < 0) { const char* e = t4r_exp_getenv("T4R_GEMM_TILE"); tile_sel = e ? atoi(e) : 0; }
     if (tile_sel == 1) { bm = 64; bn = 128; } else if (tile_sel == 2) { bm = 128; bn = 64; }
     else if (tile_sel == 3) { bm = 64; bn = 64; } else if (tile_sel == 4) { bm = 128; bn = 128; }
-    else if (!TA && TB && p.M >= 1024 && p.N >= 32768 && !p.sg_lse && !p.rk_thr && p.epilogue == EPI_NONE) {
+    else if (!TA && TB && p.M >= 1024 && p.N >= 32768 && !p.sg_lse && !p.rk_thr && !p.tk_thr && p.epilogue == EPI_NONE) {
         // the vocabulary-wide logits product (end-of-round pipeline): per output the workgroup pulls half
         // as much of X and W through L2 with a 128 x 128 tile, 759 vs 797 us stand-alone at C2
         bm = 128; bn = 128;
@@ -262,9 +270,9 @@ static int launch_layout(GemmParams& p, int batch, int splitk_req, hipStream_t s
     // precision of this launch: the half-precision variants need 16-byte loadable operands; the rank epilogue
     // (exact ranks of the evaluation head) always stays on the fp32 matrix cores
     int half_big = 0;
-    int prec = t4r_get_precision();
+    int prec = launch_precision();
     if (prec == 4) prec = auto_split(p, TA, TB) ? 1 : 0;
-    if (prec && (!(p.vecA && p.vecB) || p.rk_thr)) prec = 0;
+    if (prec && (!(p.vecA && p.vecB) || p.rk_thr || p.tk_thr)) prec = 0;
     if (prec && p.sg_lse && TB) prec = 0;
     if (prec) {
         static int half_tile = -1;
@@ -351,12 +359,14 @@ struct SoftmaxGradA { const float* lse; const long* labels; const float* gout; i
 static thread_local const SoftmaxGradA* g_sg = nullptr;   // set only by t4r_gemm_softmax_grad_f32
 struct RankEpi { const float* thr; const long* label; int* count; };
 static thread_local const RankEpi* g_rank = nullptr;      // set only by t4r_rank_of_target_f32
+struct TopkEpi { const float* thr; long thr_ld; int* count; float* val; int* idx; int cap; };
 
-// Internal C++ entry used by the composite (layer / head) launchers.
-int t4r_gemm_launch(hipStream_t stream, int transA, int transB, int M, int N, int K, float alpha,
-                    const float* A, long lda, const float* B, long ldb, float* C, long ldc,
-                    const float* bias, int epilogue, float* aux, long ldaux, int splitk,
-                    int accumulate, int batch, long sA, long sB, long sC, const DropCfg* drop) {
+// topk / force_fp32: the two products of the fused top-k head (end of this file); null / false everywhere else
+static int gemm_launch_impl(hipStream_t stream, int transA, int transB, int M, int N, int K, float alpha,
+                            const float* A, long lda, const float* B, long ldb, float* C, long ldc,
+                            const float* bias, int epilogue, float* aux, long ldaux, int splitk,
+                            int accumulate, int batch, long sA, long sB, long sC, const DropCfg* drop,
+                            const TopkEpi* topk, bool force_fp32) {
     if (M <= 0 || N <= 0) { g_amax_a = g_amax_b = nullptr; return 0; }     // operand maxima announced for THIS launch die with it
     T4R_CHECK_ARG(K > 0 && A && B && C && batch >= 1, "gemm: bad arguments");
     GemmParams p;
@@ -372,16 +382,30 @@ int t4r_gemm_launch(hipStream_t stream, int transA, int transB, int M, int N, in
     p.sg_lse = nullptr; p.sg_labels = nullptr; p.sg_gout = nullptr; p.sg_rows = 1; p.sg_V = 1; p.sg_smooth = 0.f; p.sg_yoff = 0;
     p.rk_thr = nullptr; p.rk_label = nullptr; p.rk_count = nullptr;
     if (g_rank) { p.rk_thr = g_rank->thr; p.rk_label = g_rank->label; p.rk_count = g_rank->count; }
+    p.tk_thr = nullptr; p.tk_thr_ld = 0; p.tk_count = nullptr; p.tk_val = nullptr; p.tk_idx = nullptr; p.tk_cap = 0;
+    if (topk) {
+        p.tk_thr = topk->thr; p.tk_thr_ld = topk->thr_ld; p.tk_count = topk->count;
+        p.tk_val = topk->val; p.tk_idx = topk->idx; p.tk_cap = topk->cap;
+    }
     if (g_sg) {
         p.sg_lse = g_sg->lse; p.sg_labels = g_sg->labels; p.sg_gout = g_sg->gout;
         p.sg_rows = g_sg->rows; p.sg_V = g_sg->V; p.sg_smooth = g_sg->smooth; p.sg_yoff = g_sg->yoff;
     }
     if (transA) {
-        if (transB) return launch_layout<true, true>(p, batch, splitk, stream);
-        return launch_layout<true, false>(p, batch, splitk, stream);
+        if (transB) return launch_layout<true, true>(p, batch, splitk, stream, force_fp32);
+        return launch_layout<true, false>(p, batch, splitk, stream, force_fp32);
     }
-    if (transB) return launch_layout<false, true>(p, batch, splitk, stream);
-    return launch_layout<false, false>(p, batch, splitk, stream);
+    if (transB) return launch_layout<false, true>(p, batch, splitk, stream, force_fp32);
+    return launch_layout<false, false>(p, batch, splitk, stream, force_fp32);
+}
+
+// Internal C++ entry used by the composite (layer / head) launchers.
+int t4r_gemm_launch(hipStream_t stream, int transA, int transB, int M, int N, int K, float alpha,
+                    const float* A, long lda, const float* B, long ldb, float* C, long ldc,
+                    const float* bias, int epilogue, float* aux, long ldaux, int splitk,
+                    int accumulate, int batch, long sA, long sB, long sC, const DropCfg* drop) {
+    return gemm_launch_impl(stream, transA, transB, M, N, K, alpha, A, lda, B, ldb, C, ldc, bias, epilogue, aux, ldaux, splitk,
+                            accumulate, batch, sA, sB, sC, drop, nullptr, false);
 }
 
 extern "C" int t4r_gemm_f32(void* stream, int transA, int transB, int M, int N, int K, float alpha,
@@ -451,4 +475,22 @@ extern "C" int t4r_rank_of_target_f32(void* stream, int n_rows, int V, int D, fl
                                    0, nullptr);
     g_rank = nullptr;
     return rc;
+}
+
+// ---- the two products of the fused top-k inference head (csrc/item_topk.hip), both form 0 whatever the process-wide mode:
+// C[M, N] = alpha * A[M, K] @ B[N, K]^T with the ordinary epilogue ...
+int t4r_gemm_fp32_nt_launch(hipStream_t stream, int M, int N, int K, float alpha, const float* A, long lda,
+                            const float* B, long ldb, float* C, long ldc) {
+    return gemm_launch_impl(stream, 0, 1, M, N, K, alpha, A, lda, B, ldb, C, ldc, nullptr, EPI_NONE, nullptr, 0, 1, 0, 1, 0, 0,
+                            0, nullptr, nullptr, true);
+}
+// ... and the same product with the collect epilogue: no C; (score, item) of every score >= thr[row * thr_ld] goes to the
+// row's candidate list (GemmParams::tk_*).  count[n_rows] must be zero on entry.
+int t4r_gemm_topk_collect_launch(hipStream_t stream, int n_rows, int V, int D, float alpha, const float* X, long ldx,
+                                 const float* W, long ldw, const float* thr, long thr_ld, int* count, float* cand_val,
+                                 int* cand_idx, int cap) {
+    const TopkEpi te{thr, thr_ld, count, cand_val, cand_idx, cap};
+    // C is never written by the collect epilogue; a non-null dummy keeps the argument check happy
+    return gemm_launch_impl(stream, 0, 1, n_rows, V, D, alpha, X, ldx, W, ldw, cand_val, V, nullptr, EPI_NONE, nullptr, 0, 1, 0,
+                            1, 0, 0, 0, nullptr, &te, true);
 }

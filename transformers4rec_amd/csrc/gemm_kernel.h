@@ -78,6 +78,16 @@ struct GemmParams {
     const float* rk_thr;        // null => normal epilogue
     const long* rk_label;
     int* rk_count;
+    // top-k collect epilogue (FEAT bit 3; fused inference head, csrc/item_topk.hip): nothing is stored to C; every element with
+    //   v >= tk_thr[row * tk_thr_ld]   (a lower bound of the row's k-th largest score)
+    // is appended as (v, col) to the row's candidate list tk_val / tk_idx [M][tk_cap] at the slot a per-row counter hands out.
+    // tk_count[row] ends as the number of such elements, also where it exceeds tk_cap (the surplus is dropped: the row overflowed).
+    const float* tk_thr;        // null => normal epilogue
+    long tk_thr_ld;
+    int* tk_count;
+    float* tk_val;
+    int* tk_idx;
+    int tk_cap;
 };
 
 // softmax-gradient transform of four consecutive columns col0..col0+3 of one logits row.
@@ -121,7 +131,8 @@ __device__ __forceinline__ float4 mask4(float4 v, int valid) {   // keep the fir
     return v;
 }
 
-// FEAT bit 0: softmax-gradient A operand ; bit 1: dropout in the epilogue.  Compile-time so that the
+// FEAT bit 0: softmax-gradient A operand ; bit 1: dropout in the epilogue ; bit 2: rank-of-target epilogue ; bit 3: top-k
+// collect epilogue.  Compile-time so that the
 // plain GEMM does not carry the Philox / exp code (measured: +12 % step time when it did).
 // VEC: both operands can be staged with 16-byte loads (decided by the host from pointers / pitches);
 // the scalar-load variant is its own instantiation so that it does not set the register budget.
@@ -206,7 +217,7 @@ constexpr size_t gemm_lds_bytes() {
 
 template <int BM, int BN, int BK, bool TA, bool TB, int FEAT, bool VEC, int PREC = 0>
 __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
-    constexpr bool SG = (FEAT & 1) != 0, EDROP = (FEAT & 2) != 0, RANK = (FEAT & 4) != 0;
+    constexpr bool SG = (FEAT & 1) != 0, EDROP = (FEAT & 2) != 0, RANK = (FEAT & 4) != 0, TOPK = (FEAT & 8) != 0;
     constexpr int WM = BM / 64, WN = BN / 64;          // MFMA tiles per wave per dim
     constexpr bool A_MK = !TA, B_MK = TB;              // operand image is S[m][k] (k contiguous)
     // S[m][k] images: row pitch BK (no padding) with the 16-byte chunk index XOR-swizzled by the row,
@@ -696,6 +707,37 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
                     const unsigned long long m = __ballot(beats);
                     const int cnt = __popc((unsigned)(khalf ? (m >> 32) : (m & 0xffffffffull)));
                     if ((lane & 31) == 0 && row < p.M && cnt) atomicAdd(p.rk_count + row, cnt);
+                }
+            }
+        }
+        return;
+    }
+    if constexpr (TOPK) {
+        // One 32-lane half of the wave holds 32 consecutive columns of one output row.  The halves that found candidates reserve
+        // their slots with ONE returning atomic each (lane 0 of the half) and every candidate stores at base + its prefix in the
+        // half's ballot.  Most ballots are empty (a row keeps a few hundred of its V scores): those cost a compare and a branch.
+#pragma unroll
+        for (int i = 0; i < WM; ++i) {
+#pragma unroll
+            for (int j = 0; j < WN; ++j) {
+                const int col = n0 + wn * (BN / 2) + j * 32 + (lane & 31);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int row = m0 + wm * (BM / 2) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
+                    const int rr = min(row, p.M - 1);
+                    const float v = alpha * acc[i][j][r], t = p.tk_thr[(long)rr * p.tk_thr_ld];
+                    const bool hit = col < p.N && row < p.M && v >= t;
+                    const unsigned long long m = __ballot(hit);
+                    if (m == 0) continue;                       // wave-uniform
+                    const unsigned mh = (unsigned)(khalf ? (m >> 32) : (m & 0xffffffffull));
+                    int base = 0;
+                    if ((lane & 31) == 0 && mh) base = atomicAdd(p.tk_count + row, __popc(mh));
+                    base = __shfl(base, lane & 32, 64);
+                    const int slot = base + __popc(mh & ((1u << (lane & 31)) - 1u));
+                    if (hit && slot < p.tk_cap) {
+                        p.tk_val[(long)row * p.tk_cap + slot] = v;
+                        p.tk_idx[(long)row * p.tk_cap + slot] = col;
+                    }
                 }
             }
         }

@@ -1,0 +1,243 @@
+// Fused top-k inference head: (values [N, k], ids [N, k]) of the k best items of alpha * X[N, D] @ W[V, D]^T per row, without
+// an [N, V] score matrix.  Replaces the last-item scores + torch.topk of a served model
+// (transformers4rec/torch/model/prediction_task.py:452-470, :664) where the scores are too large to exist.
+//
+// The result is the one "scores by the fp32-core GEMM, then t4r_topk" gives, bit for bit: both products below run form 0
+// (fp32 operands on the fp32 matrix cores), an output element's bits do not depend on its tile position or tile size, and the
+// order is t4r_topk's (value descending, ties to the lower index).
+//
+//   1. threshold  a STRIDED sample of M item rows (v = 0, s, 2 s, ...: ids are often sorted by popularity, a prefix would sit
+//                 far above the rest) is gathered and scored with the ordinary GEMM into S [N, M]; t4r_topk takes each row's k
+//                 best sampled scores.  The k-th of them, t0[row], is a lower bound of the row's true k-th largest score: k real
+//                 scores with exactly these bits exist.
+//   2. collect    one pass over the table: the GEMM kernel with the collect epilogue (gemm_kernel.h, FEAT bit 3) appends
+//                 (score, item) of every score >= t0[row] to the row's candidate list, one slot-counter atomic per 32-lane
+//                 half that found something.  About k V / M candidates per row.
+//   3. select     one workgroup per row runs t4r_topk's own three steps on the list (slice maxima -> tighter bound t1 -> the
+//                 few candidates >= t1 in LDS -> rank by (value desc, item asc)).  Arrival order in the list only moves t1
+//                 between two valid bounds; the k winners and their order do not depend on it.
+//   4. overflow   a row that had more candidates than its list holds (constant tables, thousands of duplicates of the best
+//                 item), fewer than k (a NaN score), or more than the LDS list after t1 is flagged.  The flag count is read back
+//                 once per call (inference: one 4-byte device-to-host read) and flagged rows are recomputed through the
+//                 materialised path -- scores of those rows into the (now free) candidate region, then t4r_topk -- so the result
+//                 is exact for every input.
+#include "t4r_common.h"
+#include <algorithm>
+#include <math.h>
+#include <vector>
+
+int t4r_gemm_fp32_nt_launch(hipStream_t stream, int M, int N, int K, float alpha, const float* A, long lda,
+                            const float* B, long ldb, float* C, long ldc);
+int t4r_gemm_topk_collect_launch(hipStream_t stream, int n_rows, int V, int D, float alpha, const float* X, long ldx,
+                                 const float* W, long ldw, const float* thr, long thr_ld, int* count, float* cand_val,
+                                 int* cand_idx, int cap);
+extern "C" int t4r_topk(void* stream, const float* scores, int N, int V, long ld, int k, float* out_val, long* out_idx);
+
+#define ITK_MAX_K 256
+#define ITK_LDS_CAP 2048       // candidates >= t1 held in LDS by the select kernel (t4r_topk's own list size)
+
+namespace {
+
+// Sizes of one call, from (V, k) alone.  The number of scores >= the k-th largest of M sampled ones is about k V / M on
+// average (the k-th of M order statistics), with a Gamma(k)-like spread: for k >= 10 its maximum over rows stayed below
+// 2.6 x the mean (CPU simulation at V = 100 001, Gaussian and popularity-skewed tables), for small k the tail is long
+// (k = 1: exponential).  cap = mean * max(4, (k + 6 sqrt(k) + 16) / k) keeps the overflow probability of a row below ~1e-9
+// for every k.  M balances the two buffers that grow against each other (S: 4 M bytes per row, lists: 8 cap bytes per row).
+struct Plan {
+    int M, stride, ldS, cap;
+    size_t off_wsamp, off_S, off_tv, off_ti, off_cnt, off_cand, total;
+};
+
+size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+Plan make_plan(long n_rows, long V, long D, int k) {
+    Plan p;
+    const double f = std::max(4.0, (k + 6.0 * sqrt((double)k) + 16.0) / k);
+    long M = (long)ceil(sqrt(2.0 * f * (double)k * (double)V));
+    M = std::max(M, 1024L);
+    M = (M + 63) / 64 * 64;
+    if (M >= V) { M = V; p.stride = 1; }
+    else p.stride = (int)(V / M);                 // (M - 1) * stride < V
+    p.M = (int)M;
+    p.ldS = (int)((M + 3) / 4 * 4);
+    const double mean = (double)k * (double)V / (double)M;
+    long cap = (long)ceil(mean * f);
+    cap = std::max(cap, 2048L);
+    cap = (cap + 63) / 64 * 64;
+    p.cap = (int)std::min(cap, (V + 3) / 4 * 4);  // a row never has more than V candidates
+    size_t o = 0;
+    p.off_wsamp = o; o += align256((size_t)M * D * 4);
+    p.off_S = o;     o += align256((size_t)n_rows * p.ldS * 4);
+    p.off_tv = o;    o += align256((size_t)n_rows * k * 4);
+    p.off_ti = o;    o += align256((size_t)n_rows * k * 8);
+    p.off_cnt = o;   o += align256((size_t)(2 * n_rows + 1) * 4);      // count[N] | n_flagged | flagged[N]
+    p.off_cand = o;
+    // the candidate region doubles as the score buffer of the overflow path: at least one padded row of scores
+    const size_t row_scores = (size_t)((V + 63) / 64 * 64) * 4;
+    o += align256(std::max((size_t)n_rows * p.cap * 8, row_scores));
+    p.total = o;
+    return p;
+}
+
+__global__ __launch_bounds__(256) void itk_sample_rows_kernel(const float* __restrict__ W, long ldw, int stride,
+                                                               float* __restrict__ out, int M, int D) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)M * D) return;
+    const long r = i / D, c = i % D;
+    out[i] = W[r * stride * ldw + c];
+}
+
+// step 3 (and the flagging of step 4) for one row per workgroup
+__global__ __launch_bounds__(256) void itk_select_kernel(const float* __restrict__ cand_val, const int* __restrict__ cand_idx,
+                                                          const int* __restrict__ count, int cap, int k,
+                                                          float* __restrict__ out_val, long* __restrict__ out_idx,
+                                                          int* __restrict__ n_flagged, int* __restrict__ flagged) {
+    __shared__ float lv[ITK_LDS_CAP];
+    __shared__ int li[ITK_LDS_CAP];
+    __shared__ float tmax[256];
+    __shared__ float t1s;
+    __shared__ int cnt;
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const int C = count[row];
+    const float* cv = cand_val + (long)row * cap;
+    const int* ci = cand_idx + (long)row * cap;
+    auto flag_row = [&]() {
+        if (tid == 0) flagged[atomicAdd(n_flagged, 1)] = row;
+    };
+    if (C > cap || C < k) { flag_row(); return; }            // workgroup-uniform
+    float m = -INFINITY;
+    for (int c = tid; c < C; c += 256) m = fmaxf(m, cv[c]);
+    tmax[tid] = m;
+    if (tid == 0) cnt = 0;
+    __syncthreads();
+    {
+        // C >= k candidates dealt round-robin: at least k slices are non-empty, so the k-th largest slice maximum is a real score
+        int rank = 0;
+        for (int o = 0; o < 256; ++o) {
+            const float v = tmax[o];
+            rank += (v > m || (v == m && o < tid)) ? 1 : 0;
+        }
+        if (rank == k - 1) t1s = m;
+    }
+    __syncthreads();
+    const float t1 = t1s;
+    for (int c = tid; c < C; c += 256) {
+        const float v = cv[c];
+        if (v >= t1) {
+            const int slot = atomicAdd(&cnt, 1);
+            if (slot < ITK_LDS_CAP) { lv[slot] = v; li[slot] = ci[c]; }
+        }
+    }
+    __syncthreads();
+    const int L = cnt;
+    if (L > ITK_LDS_CAP) { flag_row(); return; }             // workgroup-uniform
+    for (int c = tid; c < L; c += 256) {
+        const float v = lv[c];
+        const int i = li[c];
+        int rank = 0;
+        for (int o = 0; o < L; ++o) {
+            const float v2 = lv[o];
+            rank += (v2 > v || (v2 == v && li[o] < i)) ? 1 : 0;
+        }
+        if (rank < k) {
+            out_val[(long)row * k + rank] = v;
+            out_idx[(long)row * k + rank] = i;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" long t4r_item_topk_ws_bytes(int n_rows, int V, int D, int k) {
+    if (n_rows <= 0 || V <= 0 || D <= 0 || k < 1) return 0;
+    return (long)make_plan(n_rows, V, D, k).total;
+}
+
+// host_stats (host memory, 8 longs, may be null): what this call did -- [0] rows that took the materialised overflow path,
+// [1] sampled item rows M, [2] list capacity per row; and, only if host_stats[7] != 0 on entry (tools: it costs an [n_rows]
+// device-to-host copy), [3] / [4] = sum / maximum over rows of the candidate counts.  The library keeps no record of its own.
+extern "C" int t4r_item_topk_f32(void* stream, int n_rows, int V, int D, float alpha, const float* X, long ldx,
+                                 const float* W, long ldw, int k, float* out_val, long* out_idx, void* workspace,
+                                 long ws_bytes, long* host_stats) {
+    if (n_rows == 0) return 0;
+    T4R_CHECK_ARG(n_rows > 0 && V > 0 && D > 0 && X && W && out_val && out_idx, "item_topk: bad arguments");
+    T4R_CHECK_ARG(k >= 1 && k <= ITK_MAX_K && k <= V, "item_topk: 1 <= k <= min(256, V)");
+    T4R_CHECK_ARG(ldx >= D && ldw >= D, "item_topk: row pitch below D");
+    const Plan pl = make_plan(n_rows, V, D, k);
+    T4R_CHECK_ARG(workspace && ws_bytes >= (long)pl.total && (uintptr_t)workspace % 16 == 0,
+                  "item_topk: workspace too small (t4r_item_topk_ws_bytes) or not 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    float* wsamp = (float*)(ws + pl.off_wsamp);
+    float* S = (float*)(ws + pl.off_S);
+    float* tv = (float*)(ws + pl.off_tv);
+    long* ti = (long*)(ws + pl.off_ti);
+    int* count = (int*)(ws + pl.off_cnt);
+    int* n_flagged = count + n_rows;
+    int* flagged = n_flagged + 1;
+    float* cand_val = (float*)(ws + pl.off_cand);
+    int* cand_idx = (int*)(cand_val + (size_t)n_rows * pl.cap);
+
+    if (hipMemsetAsync(count, 0, sizeof(int) * ((size_t)n_rows + 1), st) != hipSuccess) {
+        t4r_set_error("item_topk: memset failed");
+        return -1;
+    }
+    // 1. threshold
+    const long md = (long)pl.M * D;
+    hipLaunchKernelGGL(itk_sample_rows_kernel, dim3((unsigned)((md + 255) / 256)), dim3(256), 0, st, W, ldw, pl.stride, wsamp,
+                       pl.M, D);
+    T4R_LAUNCH_CHECK();
+    int rc = t4r_gemm_fp32_nt_launch(st, n_rows, pl.M, D, alpha, X, ldx, wsamp, D, S, pl.ldS);
+    if (rc) return rc;
+    rc = t4r_topk(stream, S, n_rows, pl.M, pl.ldS, k, tv, ti);
+    if (rc) return rc;
+    // 2. collect
+    rc = t4r_gemm_topk_collect_launch(st, n_rows, V, D, alpha, X, ldx, W, ldw, tv + (k - 1), k, count, cand_val, cand_idx,
+                                      pl.cap);
+    if (rc) return rc;
+    // 3. select
+    hipLaunchKernelGGL(itk_select_kernel, dim3(n_rows), dim3(256), 0, st, cand_val, cand_idx, count, pl.cap, k, out_val,
+                       out_idx, n_flagged, flagged);
+    T4R_LAUNCH_CHECK();
+    // 4. overflow: the one device-to-host read of the call
+    int nf = 0;
+    if (hipMemcpyAsync(&nf, n_flagged, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) {
+        t4r_set_error("item_topk: reading the overflow count failed");
+        return -1;
+    }
+    if (host_stats) { host_stats[1] = pl.M; host_stats[2] = pl.cap; }
+    if (host_stats && host_stats[7]) {
+        std::vector<int> hc(n_rows);
+        if (hipMemcpy(hc.data(), count, sizeof(int) * (size_t)n_rows, hipMemcpyDeviceToHost) != hipSuccess) {
+            t4r_set_error("item_topk: reading the candidate counts failed");
+            return -1;
+        }
+        long sum = 0, mx = 0;
+        for (int c : hc) { sum += c; mx = std::max(mx, (long)c); }
+        host_stats[3] = sum; host_stats[4] = mx;
+    }
+    if (nf > 0) {
+        std::vector<int> rows(nf);
+        if (hipMemcpy(rows.data(), flagged, sizeof(int) * (size_t)nf, hipMemcpyDeviceToHost) != hipSuccess) {
+            t4r_set_error("item_topk: reading the overflow rows failed");
+            return -1;
+        }
+        std::sort(rows.begin(), rows.end());          // arrival order of the flags is arbitrary; runs of consecutive rows share a launch
+        const long ldv = ((long)V + 63) / 64 * 64;
+        const long fit = std::max(1L, (long)((pl.total - pl.off_cand) / ((size_t)ldv * 4)));
+        float* scores = cand_val;                     // the lists are dead: the select kernel has finished
+        for (size_t a = 0; a < rows.size();) {
+            size_t b = a + 1;
+            while (b < rows.size() && rows[b] == rows[b - 1] + 1 && (long)(b - a) < fit) ++b;
+            const int r0 = rows[a], n = (int)(b - a);
+            rc = t4r_gemm_fp32_nt_launch(st, n, V, D, alpha, X + (long)r0 * ldx, ldx, W, ldw, scores, ldv);
+            if (rc) return rc;
+            rc = t4r_topk(stream, scores, n, V, ldv, k, out_val + (long)r0 * k, out_idx + (long)r0 * k);
+            if (rc) return rc;
+            a = b;
+        }
+    }
+    if (host_stats) host_stats[0] = nf;
+    return 0;
+}

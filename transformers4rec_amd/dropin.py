@@ -503,6 +503,9 @@ class _HipTaskMixin:
         sh.masking = hm if hm is not None else shadow_masking(self.masking)
         if sh.training != self.training:
             sh.train(self.training)
+        tm = self.__dict__.get("topk_mode")          # `task.topk_mode = "fused"` on the converted reference task
+        if tm is not None and tm != sh.topk_mode:
+            sh.set_topk_mode(tm)
         return sh(inputs, targets=targets, training=training, testing=testing, top_k=top_k)
 
 

@@ -1097,6 +1097,69 @@ def topk(scores, k, V=None):
     return vals, idx
 
 
+_ITEM_TOPK_WS_LIMIT = 2 << 30      # rows are chunked only where one call's workspace would pass 2 GiB
+
+
+def item_topk(x, W, k, alpha=1.0):
+    """(values [N, k] fp32, ids [N, k] int64) of the k best items per row of alpha * x[N, D] @ W[V, D]^T, values descending,
+    ties to the lower index: bit for bit topk(gemm(x, W, False, True, alpha), k) under precision("fp32"), without an [N, V]
+    tensor (csrc/item_topk.hip).  x and W may be row-strided views (unit inner stride)."""
+    for t, name in ((x, "x"), (W, "W")):
+        if not t.is_cuda:
+            raise _lib.T4RHipError(f"item_topk: {name} must be a HIP device tensor (got {t.device}); there is no CPU path")
+        if t.dtype != torch.float32:
+            raise TypeError(f"item_topk: {name}: expected torch.float32, got {t.dtype}")
+        if t.dim() != 2 or t.stride(1) != 1:
+            raise ValueError(f"item_topk: {name} must be 2-D row-major with unit inner stride")
+    N, D = x.shape
+    V = W.shape[0]
+    k = int(k)
+    if W.shape[1] != D:
+        raise ValueError(f"item_topk: inner dims differ ({D} vs {W.shape[1]})")
+    if not 1 <= k <= min(256, V):
+        raise ValueError(f"item_topk: 1 <= k <= min(256, V) (k = {k}, V = {V})")
+    vals = torch.empty((N, k), device=x.device, dtype=torch.float32)
+    idx = torch.empty((N, k), device=x.device, dtype=torch.int64)
+    if N == 0:
+        return vals, idx
+    lib = _lib.load()
+    rows = N
+    while rows > 1 and lib.t4r_item_topk_ws_bytes(rows, V, D, k) > _ITEM_TOPK_WS_LIMIT:
+        rows = (rows + 1) // 2
+    ws = torch.empty(lib.t4r_item_topk_ws_bytes(rows, V, D, k), device=x.device, dtype=torch.uint8)
+    ldx = x.stride(0) if N > 1 else D
+    ldw = W.stride(0) if V > 1 else D
+    st = (ctypes.c_long * 8)()
+    tot = dict(fallback_rows=0, cand_sum=0, cand_max=0)
+    for s0 in range(0, N, rows):
+        n = min(rows, N - s0)
+        st[7] = int(_ITEM_TOPK["collect_counts"])
+        call("t4r_item_topk_f32", _stream(), n, V, D, float(alpha), x[s0:].data_ptr(), ldx, W.data_ptr(), ldw, k,
+             vals[s0:].data_ptr(), idx[s0:].data_ptr(), ws.data_ptr(), ws.numel(), ctypes.cast(st, ctypes.c_void_p))
+        tot["fallback_rows"] += int(st[0])
+        tot["cand_sum"] += int(st[3])
+        tot["cand_max"] = max(tot["cand_max"], int(st[4]))
+        _ITEM_TOPK["calls"] += 1
+    _ITEM_TOPK.update(tot, sample_rows=int(st[1]), list_capacity=int(st[2]))       # summed over the row chunks of this call
+    return vals, idx
+
+
+# the record behind item_topk_stats(): kept here, the library has no state of its own
+_ITEM_TOPK = dict(calls=0, fallback_rows=0, sample_rows=0, list_capacity=0, cand_sum=0, cand_max=0, collect_counts=False)
+
+
+def item_topk_stats():
+    """{"calls": fused top-k launches of this process so far; and of the last item_topk call: "fallback_rows": rows that
+    overflowed their candidate list and were recomputed through the materialised path, "sample_rows" / "list_capacity": the
+    sizes the launch chose, "cand_sum" / "cand_max": its candidate counts (only under item_topk_collect_counts(True))}"""
+    return {k: v for k, v in _ITEM_TOPK.items() if k != "collect_counts"}
+
+
+def item_topk_collect_counts(on):
+    """tools: have every item_topk launch copy its per-row candidate counts back (item_topk_stats: cand_sum / cand_max)"""
+    _ITEM_TOPK["collect_counts"] = bool(on)
+
+
 # ------------------------------------------------------------------------------------ optimizer
 def rank_of_target(x, W, labels, alpha=1.0, chunk=1024):
     """0-based rank of labels[i] among alpha * x[i] @ W^T (ties -> lower index first), int32 [N];

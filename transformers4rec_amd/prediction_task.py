@@ -329,7 +329,8 @@ class NextItemPredictionTask(nn.Module):
     def __init__(self, loss: nn.Module = None, metrics=None, task_block=None, task_name: str = "next-item",
                  weight_tying: bool = False, softmax_temperature: float = 1, padding_idx: int = 0,
                  target_dim: int = None, sampled_softmax: Optional[bool] = False,
-                 max_n_samples: Optional[int] = 100, top_ks=(10, 20), head_mode: str = "auto"):
+                 max_n_samples: Optional[int] = 100, top_ks=(10, 20), head_mode: str = "auto",
+                 topk_mode: str = "auto"):
         super().__init__()
         if head_mode not in ("auto", "materialize", "fused", "recompute"):
             raise ValueError("head_mode must be 'auto', 'materialize', 'fused' or 'recompute'")
@@ -338,6 +339,11 @@ class NextItemPredictionTask(nn.Module):
         #   "fused"      : no [N, V] tensor; `predictions` is a LazyPredictions that computes them on first use
         #   "auto"       : materialise while the logits are small (<= T4R_HEAD_AUTO_GB, default 4 GB), else fused
         self.head_mode = head_mode
+        # inference calls with top_k set (beyond the reference's signature):
+        #   "materialize": scores [B, V] in HBM, then top-k over them
+        #   "fused"      : no [B, V] tensor; scores on the fp32 matrix cores and top-k in one pass over the table (ops.item_topk)
+        #   "auto"       : materialise while the scores are small (<= T4R_HEAD_AUTO_GB, the rule of head_mode), else fused
+        self.set_topk_mode(topk_mode)
         loss = loss if loss is not None else nn.CrossEntropyLoss()
         if not isinstance(loss, nn.CrossEntropyLoss):
             raise NotImplementedError("the HIP head fuses torch.nn.CrossEntropyLoss (optionally label-smoothed)")
@@ -407,6 +413,15 @@ class NextItemPredictionTask(nn.Module):
         """'materialize' when the [N, V] fp32 scores fit T4R_HEAD_AUTO_GB (default 4 GiB), else the chunked 'fused' head"""
         limit = float(os.environ.get("T4R_HEAD_AUTO_GB", "4")) * (1 << 30)
         return "materialize" if 4.0 * N * ops.pad_ld(V) <= limit else "fused"
+
+    def set_topk_mode(self, topk_mode):
+        if topk_mode not in ("auto", "materialize", "fused"):
+            raise ValueError("topk_mode must be 'auto', 'materialize' or 'fused'")
+        self.topk_mode = topk_mode
+
+    def resolve_topk_mode(self, B, V):
+        """'materialize' or 'fused' for an inference call that returns top-k of B sessions over V items"""
+        return self.size_head_mode(B, V) if self.topk_mode == "auto" else self.topk_mode
 
     def resolve_head_mode(self, N, V):
         mode = os.environ.get("T4R_HEAD_MODE") or self.head_mode
@@ -484,11 +499,16 @@ class NextItemPredictionTask(nn.Module):
         W = mod.output_weights.detach()
         T = float(mod.softmax_temperature) if mod.softmax_temperature else 1.0
         V = W.shape[0]
+        fused_topk = top_k is not None and self.resolve_topk_mode(B, V) == "fused"
         if not torch.is_grad_enabled():      # registered operators (torch_ops.py): dispatcher-visible inference head
             from . import torch_ops  # noqa: F401
 
+            if fused_topk:
+                return torch.ops.t4r_hip.item_topk(xr, W, 1.0 / T, top_k)
             scores = torch.ops.t4r_hip.item_scores(xr, W, 1.0 / T)
             return scores if top_k is None else torch.ops.t4r_hip.topk(scores, top_k)
+        if fused_topk:
+            return ops.item_topk(xr, W, top_k, alpha=1.0 / T)
         scores = ops.gemm(xr, W, False, True, alpha=1.0 / T, ldc=ops.pad_ld(V))
         if top_k is None:
             return scores

@@ -73,6 +73,19 @@ def _(scores, k):
     return scores.new_empty((scores.shape[0], k)), scores.new_empty((scores.shape[0], k), dtype=torch.int64)
 
 
+@torch.library.custom_op(f"{NS}::item_topk", mutates_args=())
+def item_topk(x: torch.Tensor, weight: torch.Tensor, alpha: float, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """top-k item scores and ids of x [N, D] @ weight[V, D]^T * alpha per row, sorted, without the [N, V] scores: item_scores
+    (fp32 matrix cores) + topk in one pass over the table (csrc/item_topk.hip)"""
+    vals, idx = ops.item_topk(x, weight, k, alpha)
+    return vals, idx
+
+
+@item_topk.register_fake
+def _(x, weight, alpha, k):
+    return x.new_empty((x.shape[0], k)), x.new_empty((x.shape[0], k), dtype=torch.int64)
+
+
 @torch.library.custom_op(f"{NS}::rank_of_target", mutates_args=())
 def rank_of_target(x: torch.Tensor, weight: torch.Tensor, labels: torch.Tensor, alpha: float) -> torch.Tensor:
     """0-based rank of labels[i] among alpha * x[i] @ weight^T, int32 [N]; the [N, V] scores never exist"""
@@ -662,7 +675,7 @@ def _am_backward(ctx, dy):
 apply_mask.register_autograd(_am_backward, setup_context=_am_setup)
 
 
-OPERATORS = ("gemm", "item_scores", "topk", "rank_of_target", "embedding_gather", "embedding_bag", "ragged_to_padded",
+OPERATORS = ("gemm", "item_scores", "topk", "item_topk", "rank_of_target", "embedding_gather", "embedding_bag", "ragged_to_padded",
              "xlnet_layer_infer", "xlnet_layer_fwd", "xlnet_layer_bwd", "mlm_targets", "seq_item_embedding",
              "seq_item_embedding_bwd", "xlnet_layer_grad", "gather_label_rows", "scatter_label_rows", "linear_softmax_ce",
              "linear_softmax_ce_bwd", "dropout", "pos_emb_dropout", "next_item_head", "next_item_head_bwd",
