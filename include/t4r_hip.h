@@ -610,6 +610,29 @@ int t4r_rank_of_target_f32(void* stream, int n_rows, int V, int D, float alpha, 
 long t4r_item_topk_ws_bytes(int n_rows, int V, int D, int k);
 int t4r_item_topk_f32(void* stream, int n_rows, int V, int D, float alpha, const float* X, long ldx, const float* W,
                       long ldw, int k, float* out_val, long* out_idx, void* workspace, long ws_bytes, long* host_stats);
+/* The same head over a half-precision SERVING IMAGE of the item table (csrc/item_topk_h16.hip): what the last-item scores
+ * model/prediction_task.py:664 + torch.topk :452-470 compute when the reference evaluates under fp16=True / bf16=True, i.e.
+ * under autocast (torch/trainer.py:363-367) -- one 16-bit matrix-core product per multiply, fp32 accumulation:
+ *   score[n, v] = alpha * sum_d x16[n, d] * image[v, d],  x16 = X rounded to nearest even in the image's dtype, no operand scaling.
+ * dtype uses the codes of T4R_GEMM_PREC: 2 = bf16, 3 = fp16.  The image is [V, ldp] 16-bit, rows 16-byte aligned, columns
+ * D .. t4r_item_table_image_ld(D) - 1 zero; it is read from HBM once per call, X (fp32, row pitch ldx) is rounded once per call
+ * into the workspace.  The bits of one (row, item) do not depend on the launch, the tile or n_rows, so t4r_item_topk_h16 equals
+ * t4r_item_scores_h16 followed by t4r_topk bit for bit, for every input (overflow rows take that path inside the workspace).
+ * No allocation, the caller's stream; t4r_item_topk_h16 synchronises it once (the 4-byte overflow count).
+ *   t4r_item_table_image_ld(D)      row pitch in elements of a packed image: D rounded up to the k step (a multiple of 16 >= D)
+ *   t4r_item_topk_h16_supported(D)  1 for 1 <= D <= 512; wider tables are refused with a message by the two product entries
+ *   t4r_item_table_pack_h16         W fp32 [V, D] (row pitch ldw) -> image [V, ldp], round to nearest even, pad columns zero; any D
+ *   t4r_item_scores_h16             C[n_rows, V] (fp32, row pitch ldc >= V); workspace: n_rows * t4r_item_table_image_ld(D) * 2 bytes
+ *   t4r_item_topk_h16               as t4r_item_topk_f32 (k, outputs, host_stats); workspace: t4r_item_topk_h16_ws_bytes(...) */
+int t4r_item_table_image_ld(int D);
+int t4r_item_topk_h16_supported(int D);
+int t4r_item_table_pack_h16(void* stream, const float* W, long ldw, int V, int D, int dtype, void* image, long ldp);
+int t4r_item_scores_h16(void* stream, int n_rows, int V, int D, float alpha, const float* X, long ldx, const void* image,
+                        long ldp, int dtype, float* C, long ldc, void* workspace, long ws_bytes);
+long t4r_item_topk_h16_ws_bytes(int n_rows, int V, int D, int k);
+int t4r_item_topk_h16(void* stream, int n_rows, int V, int D, float alpha, const float* X, long ldx, const void* image,
+                      long ldp, int dtype, int k, float* out_val, long* out_idx, void* workspace, long ws_bytes,
+                      long* host_stats);
 
 /* ----------------------------------------------------------------------------------------
  * train-time input regularisers (pre / post transformations of the input block)

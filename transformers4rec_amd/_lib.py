@@ -132,6 +132,12 @@ _SIGS = {
     "t4r_rank_of_target_f32": ("i", "p" + "iiif" + "pl" + "pl" + "ppp"),
     "t4r_item_topk_ws_bytes": ("l", "iiii"),
     "t4r_item_topk_f32": ("i", "p" + "iiif" + "pl" + "pl" + "i" + "pp" + "pl" + "p"),
+    "t4r_item_table_image_ld": ("i", "i"),
+    "t4r_item_topk_h16_supported": ("i", "i"),
+    "t4r_item_table_pack_h16": ("i", "p" + "pl" + "iii" + "pl"),
+    "t4r_item_scores_h16": ("i", "p" + "iiif" + "pl" + "pl" + "i" + "pl" + "pl"),
+    "t4r_item_topk_h16_ws_bytes": ("l", "iiii"),
+    "t4r_item_topk_h16": ("i", "p" + "iiif" + "pl" + "pl" + "i" + "i" + "pp" + "pl" + "p"),
     "t4r_swap_noise_ws_bytes": ("l", "l"),
     "t4r_swap_noise": ("i", "ppp" + "il" + "pllf" + "pp" + "QQ" + "pl"),
     "t4r_copy_cols": ("i", "pp" + "li" + "p" + "ili"),

@@ -33,51 +33,9 @@ int t4r_gemm_topk_collect_launch(hipStream_t stream, int n_rows, int V, int D, f
                                  int* cand_idx, int cap);
 extern "C" int t4r_topk(void* stream, const float* scores, int N, int V, long ld, int k, float* out_val, long* out_idx);
 
-#define ITK_MAX_K 256
-#define ITK_LDS_CAP 2048       // candidates >= t1 held in LDS by the select kernel (t4r_topk's own list size)
+#include "item_topk_plan.h"
 
 namespace {
-
-// Sizes of one call, from (V, k) alone.  The number of scores >= the k-th largest of M sampled ones is about k V / M on
-// average (the k-th of M order statistics), with a Gamma(k)-like spread: for k >= 10 its maximum over rows stayed below
-// 2.6 x the mean (CPU simulation at V = 100 001, Gaussian and popularity-skewed tables), for small k the tail is long
-// (k = 1: exponential).  cap = mean * max(4, (k + 6 sqrt(k) + 16) / k) keeps the overflow probability of a row below ~1e-9
-// for every k.  M balances the two buffers that grow against each other (S: 4 M bytes per row, lists: 8 cap bytes per row).
-struct Plan {
-    int M, stride, ldS, cap;
-    size_t off_wsamp, off_S, off_tv, off_ti, off_cnt, off_cand, total;
-};
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-Plan make_plan(long n_rows, long V, long D, int k) {
-    Plan p;
-    const double f = std::max(4.0, (k + 6.0 * sqrt((double)k) + 16.0) / k);
-    long M = (long)ceil(sqrt(2.0 * f * (double)k * (double)V));
-    M = std::max(M, 1024L);
-    M = (M + 63) / 64 * 64;
-    if (M >= V) { M = V; p.stride = 1; }
-    else p.stride = (int)(V / M);                 // (M - 1) * stride < V
-    p.M = (int)M;
-    p.ldS = (int)((M + 3) / 4 * 4);
-    const double mean = (double)k * (double)V / (double)M;
-    long cap = (long)ceil(mean * f);
-    cap = std::max(cap, 2048L);
-    cap = (cap + 63) / 64 * 64;
-    p.cap = (int)std::min(cap, (V + 3) / 4 * 4);  // a row never has more than V candidates
-    size_t o = 0;
-    p.off_wsamp = o; o += align256((size_t)M * D * 4);
-    p.off_S = o;     o += align256((size_t)n_rows * p.ldS * 4);
-    p.off_tv = o;    o += align256((size_t)n_rows * k * 4);
-    p.off_ti = o;    o += align256((size_t)n_rows * k * 8);
-    p.off_cnt = o;   o += align256((size_t)(2 * n_rows + 1) * 4);      // count[N] | n_flagged | flagged[N]
-    p.off_cand = o;
-    // the candidate region doubles as the score buffer of the overflow path: at least one padded row of scores
-    const size_t row_scores = (size_t)((V + 63) / 64 * 64) * 4;
-    o += align256(std::max((size_t)n_rows * p.cap * 8, row_scores));
-    p.total = o;
-    return p;
-}
 
 __global__ __launch_bounds__(256) void itk_sample_rows_kernel(const float* __restrict__ W, long ldw, int stride,
                                                                float* __restrict__ out, int M, int D) {
@@ -148,9 +106,18 @@ __global__ __launch_bounds__(256) void itk_select_kernel(const float* __restrict
 
 }  // namespace
 
+// step 3 for the callers outside this file (item_topk_h16.hip): same kernel, same flags
+int t4r_itk_select_launch(hipStream_t st, int n_rows, const float* cand_val, const int* cand_idx, const int* count, int cap, int k,
+                          float* out_val, long* out_idx, int* n_flagged, int* flagged) {
+    hipLaunchKernelGGL(itk_select_kernel, dim3(n_rows), dim3(256), 0, st, cand_val, cand_idx, count, cap, k, out_val, out_idx,
+                       n_flagged, flagged);
+    T4R_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" long t4r_item_topk_ws_bytes(int n_rows, int V, int D, int k) {
     if (n_rows <= 0 || V <= 0 || D <= 0 || k < 1) return 0;
-    return (long)make_plan(n_rows, V, D, k).total;
+    return (long)make_plan(n_rows, V, k, (size_t)D * 4, 0).total;
 }
 
 // host_stats (host memory, 8 longs, may be null): what this call did -- [0] rows that took the materialised overflow path,
@@ -163,7 +130,7 @@ extern "C" int t4r_item_topk_f32(void* stream, int n_rows, int V, int D, float a
     T4R_CHECK_ARG(n_rows > 0 && V > 0 && D > 0 && X && W && out_val && out_idx, "item_topk: bad arguments");
     T4R_CHECK_ARG(k >= 1 && k <= ITK_MAX_K && k <= V, "item_topk: 1 <= k <= min(256, V)");
     T4R_CHECK_ARG(ldx >= D && ldw >= D, "item_topk: row pitch below D");
-    const Plan pl = make_plan(n_rows, V, D, k);
+    const Plan pl = make_plan(n_rows, V, k, (size_t)D * 4, 0);
     T4R_CHECK_ARG(workspace && ws_bytes >= (long)pl.total && (uintptr_t)workspace % 16 == 0,
                   "item_topk: workspace too small (t4r_item_topk_ws_bytes) or not 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
@@ -196,9 +163,8 @@ extern "C" int t4r_item_topk_f32(void* stream, int n_rows, int V, int D, float a
                                       pl.cap);
     if (rc) return rc;
     // 3. select
-    hipLaunchKernelGGL(itk_select_kernel, dim3(n_rows), dim3(256), 0, st, cand_val, cand_idx, count, pl.cap, k, out_val,
-                       out_idx, n_flagged, flagged);
-    T4R_LAUNCH_CHECK();
+    rc = t4r_itk_select_launch(st, n_rows, cand_val, cand_idx, count, pl.cap, k, out_val, out_idx, n_flagged, flagged);
+    if (rc) return rc;
     // 4. overflow: the one device-to-host read of the call
     int nf = 0;
     if (hipMemcpyAsync(&nf, n_flagged, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||

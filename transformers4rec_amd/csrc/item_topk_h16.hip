@@ -1,0 +1,387 @@
+// Inference head over a half-precision SERVING IMAGE of the item table (gfx950 only).
+//
+// Replaces, for a served model, the last-item scores + torch.topk of the reference
+// (transformers4rec/torch/model/prediction_task.py:452-470, :664) as they run under fp16=True / bf16=True, i.e. under autocast
+// (transformers4rec/torch/trainer.py:363-367): ONE 16-bit matrix-core product per multiply, fp32 accumulation.
+//
+//   score[n, v] = alpha * acc[n, v],   acc[n, v] = sum_d x16[n, d] * img[v, d]   (fp32 accumulation on the matrix cores)
+//
+// x16 = round-to-nearest-even(x) in the image's dtype, img = the packed table.  No operand scaling: autocast's semantics and its
+// range (fp16 overflows above 65 504).  Products of two fp16 / two bf16 numbers are exact in fp32, so the only rounding after the
+// operands is the accumulation.
+//
+// Kernels
+//   itk16_round_rows_kernel   fp32 [R, D] (any pitch) -> 16-bit [R, ldp], RNE, pad columns D..ldp-1 zero.  ldp = D rounded up to the
+//                             k step (16 elements = 32 bytes), so rows are 16-byte aligned and the k loop has no edge.  It is the
+//                             PACK of the table (once per table) and the prologue that rounds x (once per call, <= 1 MB).
+//   itk16_kernel<DT, EPI>     item-tile-stationary product.  A workgroup (4 waves) loads 64 image rows with 16-byte loads into LDS
+//                             -- row pitch 2 ldp + 16 bytes: an odd number of 16-byte slots, so the 16 rows a ds_read_b128 lane
+//                             group touches fall on 16 different slots of the 256-byte bank row (conflict free); 65 KB at D = 512,
+//                             two workgroups per CU -- and walks the rows of x16 against it: a wave takes 32 rows x 64 items
+//                             (two v_mfma_f32_32x32x16_f16 / _bf16 accumulators), its A fragments come straight from x16 (L2 / L1:
+//                             x16 is the operand that is re-read), its B fragments from the LDS image.  Every image row is loaded by
+//                             exactly one workgroup, once: the image comes from HBM once per launch.
+//                             EPI 0 stores alpha * acc to C (fp32); EPI 1 is the top-k COLLECT epilogue of gemm_kernel.h (FEAT bit 3):
+//                             compare with the row's threshold, one ballot per 32-lane half (a half holds 32 consecutive items of
+//                             one row), one returning slot atomic by the half's first lane, hits stored at base + prefix.
+//                             `stride` > 1 scores the strided sample of step 1 in place (item i of the launch is image row
+//                             i * stride): no gathered copy of the sample.
+//   select / threshold top-k  itk_select_kernel (item_topk.hip) and t4r_topk, unchanged; the plan is item_topk_plan.h's.
+//
+// Bits.  One element is computed by ONE instruction sequence whatever launch, tile or row block it sits in: k runs 0, 16, 32, ...
+// to ldp in every launch, each step one MFMA into the same accumulator, then one multiplication by alpha.  The sampled thresholds,
+// the collected candidates and the materialised scores of the same (row, item) are therefore the same bits, which is what makes
+// "fused == materialised" exact; rows that overflow their list take the materialised path in this same arithmetic.
+//
+// Widths: 1 <= D <= 512 (t4r_item_topk_h16_supported).  Wider tables are refused with a message: the 64-row LDS image of a
+// workgroup would leave one workgroup per CU, and no model of this project is wider.
+//
+// fp16 subnormals: observed on MI355X (tests/test_item_topk_h16_gpu.py::test_fp16_subnormal_operands, 130 940 subnormal table
+// entries at 64 x 4099 x 128): the matrix cores HONOUR subnormal fp16 operands -- largest error 9.6e-6, inside the plain
+// accumulation bound at every element, against 5.0e-4 to a reference with those entries flushed.  The contract tests still allow
+// either behaviour for entries below 2^-14.
+#include "item_topk_plan.h"
+#include <vector>
+
+extern "C" int t4r_topk(void* stream, const float* scores, int N, int V, long ld, int k, float* out_val, long* out_idx);
+
+#define ITK16_MAX_D 512
+#define ITK16_TILE 64          // image rows per workgroup
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef short bf16x8_t __attribute__((ext_vector_type(8)));
+typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
+
+template <int DT>
+__device__ __forceinline__ uint32_t round16(float f) {
+    if (DT == 3) return (uint32_t)__builtin_bit_cast(unsigned short, (_Float16)f);       // v_cvt_f16_f32, RNE
+    const uint32_t u = __builtin_bit_cast(uint32_t, f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0u;                                 // NaN
+    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;                                       // RNE (overflow rounds to inf)
+}
+
+// one 16-byte chunk (8 elements) per thread
+template <int DT>
+__global__ __launch_bounds__(256) void itk16_round_rows_kernel(const float* __restrict__ src, long lds_, long rows, int D,
+                                                                uint16_t* __restrict__ dst, long ldp, int chunks, int vec) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows * chunks) return;
+    const long r = i / chunks;
+    const int c0 = (int)(i % chunks) * 8;
+    const float* s = src + r * lds_ + c0;
+    float v[8];
+    if (vec && c0 + 8 <= D) {
+        const float4 a = *reinterpret_cast<const float4*>(s), b = *reinterpret_cast<const float4*>(s + 4);
+        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = c0 + e < D ? s[e] : 0.f;
+    }
+    uint4 o;
+    o.x = round16<DT>(v[0]) | (round16<DT>(v[1]) << 16);
+    o.y = round16<DT>(v[2]) | (round16<DT>(v[3]) << 16);
+    o.z = round16<DT>(v[4]) | (round16<DT>(v[5]) << 16);
+    o.w = round16<DT>(v[6]) | (round16<DT>(v[7]) << 16);
+    *reinterpret_cast<uint4*>(dst + r * ldp + c0) = o;
+}
+
+struct Itk16Params {
+    int n_rows, n_items, ldp;       // ldp: k extent (multiple of 16) = pitch of x16
+    const uint16_t* x16;            // [n_rows, ldp]
+    const uint16_t* img; long ldi;  // item i of the launch = image row i * stride
+    int stride;
+    float alpha;
+    float* C; long ldc;             // EPI 0
+    const float* thr; long thr_ld;  // EPI 1: as GemmParams::tk_*
+    int* count;
+    float* cand_val;
+    int* cand_idx;
+    int cap;
+};
+
+template <int DT>
+__device__ __forceinline__ f32x16 mfma16(uint4 a, uint4 b, f32x16 c) {
+    if (DT == 3)
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, a), __builtin_bit_cast(half8_t, b), c, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
+}
+
+template <int DT, int EPI>
+__global__ __launch_bounds__(256) void itk16_kernel(Itk16Params p) {
+    extern __shared__ uint4 itk16_lds[];                    // [64][chunks + 1] 16-byte slots
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int chunks = p.ldp >> 3, pitch = chunks + 1;
+    const long item0 = (long)blockIdx.x * ITK16_TILE;
+    // the image tile, eight 16-byte loads in flight per thread: every load reads a legal address (row clamped into the launch's
+    // items) and rows beyond them are zeroed on the way to LDS (their columns are masked in the epilogue as well)
+    {
+        const int dr = 256 / chunks, dc = 256 - dr * chunks;  // chunk index + 256 = (row + dr, chunk + dc), carried below
+        int tr = tid / chunks, tc = tid - tr * chunks;
+        const long last = (long)p.n_items - 1 - item0;        // last tile row inside the launch's items (>= 0)
+        const long rstep = (long)p.stride * p.ldi;
+        const uint16_t* base = p.img + item0 * rstep;
+        while (tr < ITK16_TILE) {                              // workgroup-divergent only in its last batch
+            uint4 v[8];
+            int off[8];                                        // LDS slot; -1: beyond the tile; bit 30: zero it
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const long rr = min((long)min(tr, ITK16_TILE - 1), last);
+                v[u] = *reinterpret_cast<const uint4*>(base + rr * rstep + tc * 8);
+                off[u] = tr >= ITK16_TILE ? -1 : ((tr * pitch + tc) | (tr > last ? 1 << 30 : 0));
+                tc += dc; tr += dr;
+                if (tc >= chunks) { tc -= chunks; ++tr; }
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                // first use of the staged registers: keeps the eight loads above in one batch
+                asm volatile("" : "+v"(v[u].x), "+v"(v[u].y), "+v"(v[u].z), "+v"(v[u].w));
+                const bool z = (off[u] & (1 << 30)) != 0;
+                uint4 w;
+                w.x = z ? 0u : v[u].x; w.y = z ? 0u : v[u].y; w.z = z ? 0u : v[u].z; w.w = z ? 0u : v[u].w;
+                if (off[u] >= 0) itk16_lds[off[u] & ~(1 << 30)] = w;
+            }
+        }
+    }
+    __syncthreads();
+    const int r = lane & 31, h = lane >> 5;
+    const uint4* b0p = itk16_lds + r * pitch + h;           // items item0 + r and item0 + 32 + r; k-step s is slot 2 s + h
+    const uint4* b1p = itk16_lds + (32 + r) * pitch + h;
+    const int nk = p.ldp >> 4, ng = nk >> 2;                // k-steps, and groups of four of them
+    const float alpha = p.alpha;
+    for (int rb = wave * 32; rb < p.n_rows; rb += 128) {    // wave-uniform
+        // rows beyond n_rows read the last row (a legal address) and are masked in the epilogue
+        const uint4* ap = reinterpret_cast<const uint4*>(p.x16 + (long)min(rb + r, p.n_rows - 1) * p.ldp) + h;
+        float thr[16];
+        if (EPI == 1) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e)
+                thr[e] = p.thr[(long)min(rb + (e & 3) + 8 * (e >> 2) + 4 * h, p.n_rows - 1) * p.thr_ld];
+        }
+        f32x16 acc[2];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) { acc[0][e] = 0.f; acc[1][e] = 0.f; }
+        // k runs 0 .. nk-1 in order into the same two accumulators; the grouping only keeps the next four A fragments in flight
+        uint4 a[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) a[u] = ap[2 * min(u, nk - 1)];
+        for (int g = 0; g < ng; ++g) {
+            uint4 an[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) an[u] = ap[2 * min(4 * g + 4 + u, nk - 1)];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const uint4 b0 = b0p[2 * (4 * g + u)], b1 = b1p[2 * (4 * g + u)];
+                acc[0] = mfma16<DT>(a[u], b0, acc[0]);
+                acc[1] = mfma16<DT>(a[u], b1, acc[1]);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) a[u] = an[u];
+        }
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {                       // at most three more steps; a[] holds their fragments already
+            if (4 * ng + u < nk) {                          // wave-uniform
+                const uint4 b0 = b0p[2 * (4 * ng + u)], b1 = b1p[2 * (4 * ng + u)];
+                acc[0] = mfma16<DT>(a[u], b0, acc[0]);
+                acc[1] = mfma16<DT>(a[u], b1, acc[1]);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const long col = item0 + j * 32 + r;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int row = rb + (e & 3) + 8 * (e >> 2) + 4 * h;
+                const float v = alpha * acc[j][e];
+                if (EPI == 0) {
+                    if (col < p.n_items && row < p.n_rows) p.C[(long)row * p.ldc + col] = v;
+                } else {
+                    const float t = thr[e];
+                    const bool hit = col < p.n_items && row < p.n_rows && v >= t;
+                    const unsigned long long m = __ballot(hit);
+                    if (m == 0) continue;                       // wave-uniform
+                    const unsigned mh = (unsigned)(h ? (m >> 32) : (m & 0xffffffffull));
+                    int base = 0;
+                    if (r == 0 && mh) base = atomicAdd(p.count + row, __popc(mh));
+                    base = __shfl(base, lane & 32, 64);
+                    const int slot = base + __popc(mh & ((1u << r) - 1u));
+                    if (hit && slot < p.cap) {
+                        p.cand_val[(long)row * p.cap + slot] = v;
+                        p.cand_idx[(long)row * p.cap + slot] = (int)col;
+                    }
+                }
+            }
+        }
+    }
+}
+
+T4rLdsAttr g_lds_attr[2][2];
+
+template <int DT, int EPI>
+int launch_t(hipStream_t st, const Itk16Params& p) {
+    const size_t smem = (size_t)ITK16_TILE * ((size_t)(p.ldp >> 3) + 1) * 16;
+    const void* fn = (const void*)itk16_kernel<DT, EPI>;
+    t4r_ensure_dynamic_lds(fn, smem, g_lds_attr[DT - 2][EPI]);
+    const unsigned grid = (unsigned)(((long)p.n_items + ITK16_TILE - 1) / ITK16_TILE);
+    hipLaunchKernelGGL((itk16_kernel<DT, EPI>), dim3(grid), dim3(256), smem, st, p);
+    T4R_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch(hipStream_t st, int dtype, int epi, const Itk16Params& p) {
+    if (dtype == 3) return epi ? launch_t<3, 1>(st, p) : launch_t<3, 0>(st, p);
+    return epi ? launch_t<2, 1>(st, p) : launch_t<2, 0>(st, p);
+}
+
+int round_rows(hipStream_t st, int dtype, const float* src, long ld, long rows, int D, uint16_t* dst, long ldp) {
+    const int chunks = (int)(ldp / 8);
+    const int vec = ((uintptr_t)src % 16 == 0 && ld % 4 == 0) ? 1 : 0;
+    const long n = rows * chunks;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (dtype == 3) hipLaunchKernelGGL(itk16_round_rows_kernel<3>, grid, dim3(256), 0, st, src, ld, rows, D, dst, ldp, chunks, vec);
+    else hipLaunchKernelGGL(itk16_round_rows_kernel<2>, grid, dim3(256), 0, st, src, ld, rows, D, dst, ldp, chunks, vec);
+    T4R_LAUNCH_CHECK();
+    return 0;
+}
+
+long image_ld(long D) { return (D + 15) / 16 * 16; }
+
+}  // namespace
+
+extern "C" int t4r_item_table_image_ld(int D) { return D > 0 ? (int)image_ld(D) : 0; }
+
+extern "C" int t4r_item_topk_h16_supported(int D) { return D >= 1 && D <= ITK16_MAX_D ? 1 : 0; }
+
+#define ITK16_CHECK_IMAGE(name)                                                                                                     \
+    T4R_CHECK_ARG(dtype == 2 || dtype == 3, name ": dtype is 2 (bf16) or 3 (fp16), the codes of T4R_GEMM_PREC");                    \
+    T4R_CHECK_ARG(ldp >= image_ld(D) && ldp % 8 == 0 && (uintptr_t)image % 16 == 0,                                                 \
+                  name ": image rows must be 16-byte aligned with pitch >= t4r_item_table_image_ld(D)")
+
+extern "C" int t4r_item_table_pack_h16(void* stream, const float* W, long ldw, int V, int D, int dtype, void* image, long ldp) {
+    if (V == 0) return 0;
+    T4R_CHECK_ARG(V > 0 && D > 0 && W && image && ldw >= D, "item_table_pack_h16: bad arguments");
+    ITK16_CHECK_IMAGE("item_table_pack_h16");
+    // a wider pitch is zero-filled to its end
+    return round_rows((hipStream_t)stream, dtype, W, ldw, V, D, (uint16_t*)image, ldp) ? -1 : 0;
+}
+
+// workspace: n_rows * t4r_item_table_image_ld(D) * 2 bytes (the 16-bit image of x), 16-byte aligned
+extern "C" int t4r_item_scores_h16(void* stream, int n_rows, int V, int D, float alpha, const float* X, long ldx,
+                                   const void* image, long ldp, int dtype, float* C, long ldc, void* workspace, long ws_bytes) {
+    if (n_rows == 0 || V == 0) return 0;
+    T4R_CHECK_ARG(n_rows > 0 && V > 0 && D > 0 && X && image && C, "item_scores_h16: bad arguments");
+    T4R_CHECK_ARG(t4r_item_topk_h16_supported(D), "item_scores_h16: 1 <= D <= 512 (t4r_item_topk_h16_supported)");
+    T4R_CHECK_ARG(ldx >= D && ldc >= V, "item_scores_h16: row pitch below the row length");
+    ITK16_CHECK_IMAGE("item_scores_h16");
+    const long kp = image_ld(D);
+    T4R_CHECK_ARG(workspace && ws_bytes >= (long)n_rows * kp * 2 && (uintptr_t)workspace % 16 == 0,
+                  "item_scores_h16: workspace below n_rows * t4r_item_table_image_ld(D) * 2 bytes or not 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    uint16_t* x16 = (uint16_t*)workspace;
+    int rc = round_rows(st, dtype, X, ldx, n_rows, D, x16, kp);
+    if (rc) return rc;
+    Itk16Params p = {};
+    p.n_rows = n_rows; p.n_items = V; p.ldp = (int)kp; p.x16 = x16; p.img = (const uint16_t*)image; p.ldi = ldp; p.stride = 1;
+    p.alpha = alpha; p.C = C; p.ldc = ldc;
+    return launch(st, dtype, 0, p);
+}
+
+extern "C" long t4r_item_topk_h16_ws_bytes(int n_rows, int V, int D, int k) {
+    if (n_rows <= 0 || V <= 0 || D <= 0 || k < 1) return 0;
+    return (long)make_plan(n_rows, V, k, 0, (size_t)n_rows * image_ld(D) * 2).total;
+}
+
+// host_stats: as t4r_item_topk_f32
+extern "C" int t4r_item_topk_h16(void* stream, int n_rows, int V, int D, float alpha, const float* X, long ldx, const void* image,
+                                 long ldp, int dtype, int k, float* out_val, long* out_idx, void* workspace, long ws_bytes,
+                                 long* host_stats) {
+    if (n_rows == 0) return 0;
+    T4R_CHECK_ARG(n_rows > 0 && V > 0 && D > 0 && X && image && out_val && out_idx, "item_topk_h16: bad arguments");
+    T4R_CHECK_ARG(t4r_item_topk_h16_supported(D), "item_topk_h16: 1 <= D <= 512 (t4r_item_topk_h16_supported)");
+    T4R_CHECK_ARG(k >= 1 && k <= ITK_MAX_K && k <= V, "item_topk_h16: 1 <= k <= min(256, V)");
+    T4R_CHECK_ARG(ldx >= D, "item_topk_h16: row pitch below D");
+    ITK16_CHECK_IMAGE("item_topk_h16");
+    const long kp = image_ld(D);
+    const Plan pl = make_plan(n_rows, V, k, 0, (size_t)n_rows * kp * 2);
+    T4R_CHECK_ARG(workspace && ws_bytes >= (long)pl.total && (uintptr_t)workspace % 16 == 0,
+                  "item_topk_h16: workspace too small (t4r_item_topk_h16_ws_bytes) or not 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    float* S = (float*)(ws + pl.off_S);
+    float* tv = (float*)(ws + pl.off_tv);
+    long* ti = (long*)(ws + pl.off_ti);
+    int* count = (int*)(ws + pl.off_cnt);
+    int* n_flagged = count + n_rows;
+    int* flagged = n_flagged + 1;
+    float* cand_val = (float*)(ws + pl.off_cand);
+    int* cand_idx = (int*)(cand_val + (size_t)n_rows * pl.cap);
+    uint16_t* x16 = (uint16_t*)(ws + pl.off_x);
+
+    if (hipMemsetAsync(count, 0, sizeof(int) * ((size_t)n_rows + 1), st) != hipSuccess) {
+        t4r_set_error("item_topk_h16: memset failed");
+        return -1;
+    }
+    int rc = round_rows(st, dtype, X, ldx, n_rows, D, x16, kp);
+    if (rc) return rc;
+    Itk16Params p = {};
+    p.n_rows = n_rows; p.ldp = (int)kp; p.x16 = x16; p.img = (const uint16_t*)image; p.ldi = ldp; p.alpha = alpha;
+    // 1. threshold: the strided sample scored in place
+    p.n_items = pl.M; p.stride = pl.stride; p.C = S; p.ldc = pl.ldS;
+    rc = launch(st, dtype, 0, p);
+    if (rc) return rc;
+    rc = t4r_topk(stream, S, n_rows, pl.M, pl.ldS, k, tv, ti);
+    if (rc) return rc;
+    // 2. collect
+    p.n_items = V; p.stride = 1; p.C = nullptr; p.ldc = 0;
+    p.thr = tv + (k - 1); p.thr_ld = k; p.count = count; p.cand_val = cand_val; p.cand_idx = cand_idx; p.cap = pl.cap;
+    rc = launch(st, dtype, 1, p);
+    if (rc) return rc;
+    // 3. select
+    rc = t4r_itk_select_launch(st, n_rows, cand_val, cand_idx, count, pl.cap, k, out_val, out_idx, n_flagged, flagged);
+    if (rc) return rc;
+    // 4. overflow: the one device-to-host read of the call
+    int nf = 0;
+    if (hipMemcpyAsync(&nf, n_flagged, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) {
+        t4r_set_error("item_topk_h16: reading the overflow count failed");
+        return -1;
+    }
+    if (host_stats) { host_stats[1] = pl.M; host_stats[2] = pl.cap; }
+    if (host_stats && host_stats[7]) {
+        std::vector<int> hc(n_rows);
+        if (hipMemcpy(hc.data(), count, sizeof(int) * (size_t)n_rows, hipMemcpyDeviceToHost) != hipSuccess) {
+            t4r_set_error("item_topk_h16: reading the candidate counts failed");
+            return -1;
+        }
+        long sum = 0, mx = 0;
+        for (int c : hc) { sum += c; mx = std::max(mx, (long)c); }
+        host_stats[3] = sum; host_stats[4] = mx;
+    }
+    if (nf > 0) {
+        std::vector<int> rows(nf);
+        if (hipMemcpy(rows.data(), flagged, sizeof(int) * (size_t)nf, hipMemcpyDeviceToHost) != hipSuccess) {
+            t4r_set_error("item_topk_h16: reading the overflow rows failed");
+            return -1;
+        }
+        std::sort(rows.begin(), rows.end());
+        const long ldv = ((long)V + 63) / 64 * 64;
+        const long fit = std::max(1L, (long)((pl.off_x - pl.off_cand) / ((size_t)ldv * 4)));
+        float* scores = cand_val;                     // the lists are dead: the select kernel has finished
+        for (size_t a = 0; a < rows.size();) {
+            size_t b = a + 1;
+            while (b < rows.size() && rows[b] == rows[b - 1] + 1 && (long)(b - a) < fit) ++b;
+            const int r0 = rows[a], n = (int)(b - a);
+            Itk16Params q = {};
+            q.n_rows = n; q.n_items = V; q.ldp = (int)kp; q.x16 = x16 + (long)r0 * kp; q.img = (const uint16_t*)image; q.ldi = ldp;
+            q.stride = 1; q.alpha = alpha; q.C = scores; q.ldc = ldv;
+            rc = launch(st, dtype, 0, q);
+            if (rc) return rc;
+            rc = t4r_topk(stream, scores, n, V, ldv, k, out_val + (long)r0 * k, out_idx + (long)r0 * k);
+            if (rc) return rc;
+            a = b;
+        }
+    }
+    if (host_stats) host_stats[0] = nf;
+    return 0;
+}

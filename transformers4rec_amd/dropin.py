@@ -494,6 +494,22 @@ class _HipTaskMixin:
     def hip_shadow(self):
         return _shadow_of(self, shadow_task)
 
+    # serving image (NextItemPredictionTask.prepare_serving): kept by the shadow, which shares the reference's parameters
+    def prepare_serving(self, dtype="fp16"):
+        self.hip_shadow().prepare_serving(dtype)
+        return self
+
+    def drop_serving_image(self):
+        self.hip_shadow().drop_serving_image()
+
+    @property
+    def serving_dtype(self):
+        return self.hip_shadow().serving_dtype
+
+    @property
+    def serving_packs(self):
+        return self.hip_shadow().serving_packs
+
     def forward(self, inputs, targets=None, training=False, testing=False, top_k=None, **kwargs):
         sh = self.hip_shadow()
         hm = self.masking.__dict__.get("_t4r_hip_masking") if self.masking is not None else None

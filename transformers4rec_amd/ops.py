@@ -1100,17 +1100,96 @@ def topk(scores, k, V=None):
 _ITEM_TOPK_WS_LIMIT = 2 << 30      # rows are chunked only where one call's workspace would pass 2 GiB
 
 
+_H16 = {torch.bfloat16: 2, torch.float16: 3}      # serving-image dtypes -> the codes of T4R_GEMM_PREC
+_H16_NAMES = {"bf16": torch.bfloat16, "fp16": torch.float16}
+
+
+def image_ld(D):
+    """row pitch (elements) of a packed serving image of width D: a multiple of 16 >= D (t4r_item_table_image_ld)"""
+    return int(_lib.load().t4r_item_table_image_ld(int(D)))
+
+
+def item_topk_h16_supported(D):
+    """True where the 16-bit head takes an item table of width D (1 <= D <= 512)"""
+    return bool(_lib.load().t4r_item_topk_h16_supported(int(D)))
+
+
+def pack_item_table(W, dtype="fp16"):
+    """The SERVING IMAGE of an item table: W [V, D] fp32 rounded once (to nearest even) to fp16 / bf16, as a [V, D] view of
+    a [V, image_ld(D)] buffer whose pad columns are zero and whose rows are 16-byte aligned -- `image.float()` is its exact
+    value, W.to(dtype) its bits.  item_topk / item_scores take it in place of W (csrc/item_topk_h16.hip).  Raises for a table
+    whose rounding is not finite (fp16 overflows above 65 504: no operand scaling, as under the reference's autocast)."""
+    if dtype not in _H16_NAMES:
+        raise ValueError(f"pack_item_table: dtype must be 'fp16' or 'bf16' (got {dtype!r})")
+    if not W.is_cuda:
+        raise _lib.T4RHipError(f"pack_item_table: W must be a HIP device tensor (got {W.device}); there is no CPU path")
+    if W.dtype != torch.float32:
+        raise TypeError(f"pack_item_table: W: expected torch.float32, got {W.dtype}")
+    if W.dim() != 2 or W.stride(1) != 1:
+        raise ValueError("pack_item_table: W must be 2-D row-major with unit inner stride")
+    V, D = W.shape
+    td = _H16_NAMES[dtype]
+    ldp = image_ld(D)
+    buf = torch.empty((V, ldp), device=W.device, dtype=td)
+    call("t4r_item_table_pack_h16", _stream(), W.data_ptr(), W.stride(0) if V > 1 else D, V, D, _H16[td], buf.data_ptr(), ldp)
+    if not bool(torch.isfinite(buf).all()):         # once per table: the image is reused by every call
+        raise ValueError(f"pack_item_table: the table does not round to finite {dtype} values")
+    return buf[:, :D]
+
+
+def _check_image(what, W, D):
+    if W.shape[1] != D:
+        raise ValueError(f"{what}: inner dims differ ({D} vs {W.shape[1]})")
+    V = W.shape[0]
+    ldp = W.stride(0) if V > 1 else image_ld(D)
+    if ldp < image_ld(D) or ldp % 8 or W.data_ptr() % 16:
+        raise ValueError(f"{what}: a 16-bit table must be a serving image (ops.pack_item_table): rows 16-byte aligned, "
+                         f"pitch >= image_ld(D) = {image_ld(D)} with zero pad columns")
+    if not _lib.load().t4r_item_topk_h16_supported(D):
+        raise ValueError(f"{what}: the 16-bit head takes 1 <= D <= 512 (D = {D})")
+    return ldp
+
+
+def _check_x_w(what, x, W):
+    for t, name in ((x, "x"), (W, "W")):
+        if not t.is_cuda:
+            raise _lib.T4RHipError(f"{what}: {name} must be a HIP device tensor (got {t.device}); there is no CPU path")
+        if t.dtype != torch.float32 and not (name == "W" and t.dtype in _H16):
+            raise TypeError(f"{what}: {name}: expected torch.float32" + (", torch.float16 or torch.bfloat16 (a serving image)"
+                                                                         if name == "W" else "") + f", got {t.dtype}")
+        if t.dim() != 2 or t.stride(1) != 1:
+            raise ValueError(f"{what}: {name} must be 2-D row-major with unit inner stride")
+
+
+def item_scores(x, W, alpha=1.0):
+    """alpha * x[N, D] @ W[V, D]^T as the [N, V] fp32 view of a row-padded buffer.  W fp32: gemm() under the current
+    precision mode (what the task's inference call has always returned).  W a serving image (pack_item_table): one
+    16-bit matrix-core product per multiply over x rounded to the image's dtype, fp32 accumulation -- the arithmetic of
+    item_topk over that image, bit for bit."""
+    _check_x_w("item_scores", x, W)
+    N, D = x.shape
+    V = W.shape[0]
+    if W.dtype == torch.float32:
+        if W.shape[1] != D:
+            raise ValueError(f"item_scores: inner dims differ ({D} vs {W.shape[1]})")
+        return gemm(x.contiguous(), W, False, True, alpha=alpha, ldc=pad_ld(V))[:, :V]
+    ldp = _check_image("item_scores", W, D)
+    ldc = pad_ld(V)
+    out = torch.empty((N, ldc), device=x.device, dtype=torch.float32)
+    if N and V:
+        ws = torch.empty(N * image_ld(D) * 2, device=x.device, dtype=torch.uint8)
+        call("t4r_item_scores_h16", _stream(), N, V, D, float(alpha), x.data_ptr(), x.stride(0) if N > 1 else D, W.data_ptr(),
+             ldp, _H16[W.dtype], out.data_ptr(), ldc, ws.data_ptr(), ws.numel())
+    return out[:, :V]
+
+
 def item_topk(x, W, k, alpha=1.0):
     """(values [N, k] fp32, ids [N, k] int64) of the k best items per row of alpha * x[N, D] @ W[V, D]^T, values descending,
     ties to the lower index: bit for bit topk(gemm(x, W, False, True, alpha), k) under precision("fp32"), without an [N, V]
-    tensor (csrc/item_topk.hip).  x and W may be row-strided views (unit inner stride)."""
-    for t, name in ((x, "x"), (W, "W")):
-        if not t.is_cuda:
-            raise _lib.T4RHipError(f"item_topk: {name} must be a HIP device tensor (got {t.device}); there is no CPU path")
-        if t.dtype != torch.float32:
-            raise TypeError(f"item_topk: {name}: expected torch.float32, got {t.dtype}")
-        if t.dim() != 2 or t.stride(1) != 1:
-            raise ValueError(f"item_topk: {name} must be 2-D row-major with unit inner stride")
+    tensor (csrc/item_topk.hip).  x and W may be row-strided views (unit inner stride).
+    W a serving image (pack_item_table, fp16 / bf16; x stays fp32): the same from one 16-bit matrix-core product per multiply,
+    bit for bit topk(item_scores(x, W, alpha), k) (csrc/item_topk_h16.hip); the precision mode plays no part."""
+    _check_x_w("item_topk", x, W)
     N, D = x.shape
     V = W.shape[0]
     k = int(k)
@@ -1118,38 +1197,49 @@ def item_topk(x, W, k, alpha=1.0):
         raise ValueError(f"item_topk: inner dims differ ({D} vs {W.shape[1]})")
     if not 1 <= k <= min(256, V):
         raise ValueError(f"item_topk: 1 <= k <= min(256, V) (k = {k}, V = {V})")
+    h16 = W.dtype in _H16
+    ldw = _check_image("item_topk", W, D) if h16 else (W.stride(0) if V > 1 else D)
     vals = torch.empty((N, k), device=x.device, dtype=torch.float32)
     idx = torch.empty((N, k), device=x.device, dtype=torch.int64)
     if N == 0:
         return vals, idx
     lib = _lib.load()
+    ws_bytes = lib.t4r_item_topk_h16_ws_bytes if h16 else lib.t4r_item_topk_ws_bytes
     rows = N
-    while rows > 1 and lib.t4r_item_topk_ws_bytes(rows, V, D, k) > _ITEM_TOPK_WS_LIMIT:
+    while rows > 1 and ws_bytes(rows, V, D, k) > _ITEM_TOPK_WS_LIMIT:
         rows = (rows + 1) // 2
-    ws = torch.empty(lib.t4r_item_topk_ws_bytes(rows, V, D, k), device=x.device, dtype=torch.uint8)
+    ws = torch.empty(ws_bytes(rows, V, D, k), device=x.device, dtype=torch.uint8)
     ldx = x.stride(0) if N > 1 else D
-    ldw = W.stride(0) if V > 1 else D
     st = (ctypes.c_long * 8)()
     tot = dict(fallback_rows=0, cand_sum=0, cand_max=0)
     for s0 in range(0, N, rows):
         n = min(rows, N - s0)
         st[7] = int(_ITEM_TOPK["collect_counts"])
-        call("t4r_item_topk_f32", _stream(), n, V, D, float(alpha), x[s0:].data_ptr(), ldx, W.data_ptr(), ldw, k,
-             vals[s0:].data_ptr(), idx[s0:].data_ptr(), ws.data_ptr(), ws.numel(), ctypes.cast(st, ctypes.c_void_p))
+        if h16:
+            call("t4r_item_topk_h16", _stream(), n, V, D, float(alpha), x[s0:].data_ptr(), ldx, W.data_ptr(), ldw,
+                 _H16[W.dtype], k, vals[s0:].data_ptr(), idx[s0:].data_ptr(), ws.data_ptr(), ws.numel(),
+                 ctypes.cast(st, ctypes.c_void_p))
+        else:
+            call("t4r_item_topk_f32", _stream(), n, V, D, float(alpha), x[s0:].data_ptr(), ldx, W.data_ptr(), ldw, k,
+                 vals[s0:].data_ptr(), idx[s0:].data_ptr(), ws.data_ptr(), ws.numel(), ctypes.cast(st, ctypes.c_void_p))
         tot["fallback_rows"] += int(st[0])
         tot["cand_sum"] += int(st[3])
         tot["cand_max"] = max(tot["cand_max"], int(st[4]))
         _ITEM_TOPK["calls"] += 1
-    _ITEM_TOPK.update(tot, sample_rows=int(st[1]), list_capacity=int(st[2]))       # summed over the row chunks of this call
+        _ITEM_TOPK["calls_h16"] += int(h16)
+    _ITEM_TOPK.update(tot, sample_rows=int(st[1]), list_capacity=int(st[2]),       # summed over the row chunks of this call
+                      dtype={torch.float32: "fp32", torch.float16: "fp16", torch.bfloat16: "bf16"}[W.dtype])
     return vals, idx
 
 
 # the record behind item_topk_stats(): kept here, the library has no state of its own
-_ITEM_TOPK = dict(calls=0, fallback_rows=0, sample_rows=0, list_capacity=0, cand_sum=0, cand_max=0, collect_counts=False)
+_ITEM_TOPK = dict(calls=0, calls_h16=0, dtype=None, fallback_rows=0, sample_rows=0, list_capacity=0, cand_sum=0, cand_max=0,
+                  collect_counts=False)
 
 
 def item_topk_stats():
-    """{"calls": fused top-k launches of this process so far; and of the last item_topk call: "fallback_rows": rows that
+    """{"calls": fused top-k launches of this process so far, "calls_h16": those of them over a 16-bit serving image; and of
+    the last item_topk call: "dtype": "fp32" | "fp16" | "bf16" (what its table was), "fallback_rows": rows that
     overflowed their candidate list and were recomputed through the materialised path, "sample_rows" / "list_capacity": the
     sizes the launch chose, "cand_sum" / "cand_max": its candidate counts (only under item_topk_collect_counts(True))}"""
     return {k: v for k, v in _ITEM_TOPK.items() if k != "collect_counts"}

@@ -344,6 +344,11 @@ class NextItemPredictionTask(nn.Module):
         #   "fused"      : no [B, V] tensor; scores on the fp32 matrix cores and top-k in one pass over the table (ops.item_topk)
         #   "auto"       : materialise while the scores are small (<= T4R_HEAD_AUTO_GB, the rule of head_mode), else fused
         self.set_topk_mode(topk_mode)
+        # serving image (prepare_serving): plain attributes, so the image is no parameter, no buffer and not in state_dict
+        self._serving_dtype = None
+        self._serving_image = None
+        self._serving_record = None
+        self.serving_packs = 0
         loss = loss if loss is not None else nn.CrossEntropyLoss()
         if not isinstance(loss, nn.CrossEntropyLoss):
             raise NotImplementedError("the HIP head fuses torch.nn.CrossEntropyLoss (optionally label-smoothed)")
@@ -419,6 +424,54 @@ class NextItemPredictionTask(nn.Module):
             raise ValueError("topk_mode must be 'auto', 'materialize' or 'fused'")
         self.topk_mode = topk_mode
 
+    # ------------------------------------------------------------------ serving image
+    def prepare_serving(self, dtype="fp16"):
+        """Serve inference calls from a half-precision image of the output weights (tied item table or output_layer), packed
+        once: top_k given -> the fused 16-bit head (ops.item_topk over the image), top_k=None -> [B, V] fp32 scores from the
+        image.  One 16-bit matrix-core product per multiply, fp32 accumulation: the arithmetic of the reference's evaluation
+        under fp16=True / bf16=True (autocast).  A standing choice until drop_serving_image(); the image itself is a snapshot that
+        is never served stale: any training=True forward of the task marks it, a change of the weights' (data_ptr, _version,
+        shape, device) marks it, and a marked image is re-packed by the next inference call (serving_packs counts the packs).
+        Not covered: writers through `.data` / raw pointers with no training forward in between -- call prepare_serving again."""
+        if dtype not in ("fp16", "bf16"):
+            raise ValueError("prepare_serving: dtype must be 'fp16' or 'bf16'")
+        if self.pre is None:
+            raise RuntimeError("prepare_serving: the task is not built yet")
+        D = int(self.pre.module.output_weights.shape[1])
+        if not ops.item_topk_h16_supported(D):
+            raise ValueError(f"prepare_serving: the 16-bit head takes item tables of width 1 <= D <= 512 (D = {D})")
+        prev = (self._serving_dtype, self._serving_image, self._serving_record)
+        self._serving_dtype, self._serving_image, self._serving_record = dtype, None, None
+        try:
+            self._serving_weights()
+        except Exception:
+            self._serving_dtype, self._serving_image, self._serving_record = prev
+            raise
+        return self
+
+    def drop_serving_image(self):
+        """back to the fp32 table: inference calls run exactly as before prepare_serving"""
+        self._serving_dtype = None
+        self._serving_image = None
+        self._serving_record = None
+
+    @property
+    def serving_dtype(self):
+        """'fp16' | 'bf16' while inference is served from an image, else None"""
+        return self._serving_dtype
+
+    def _serving_weights(self):
+        """the current image of the output weights (packed now if absent or stale), or None without prepare_serving"""
+        if self._serving_dtype is None:
+            return None
+        W = self.pre.module.output_weights.detach()
+        rec = (W.data_ptr(), W._version, tuple(W.shape), W.device)
+        if self._serving_image is None or self._serving_record != rec:
+            self._serving_image = ops.pack_item_table(W, self._serving_dtype)
+            self._serving_record = rec
+            self.serving_packs += 1
+        return self._serving_image
+
     def resolve_topk_mode(self, B, V):
         """'materialize' or 'fused' for an inference call that returns top-k of B sessions over V items"""
         return self.size_head_mode(B, V) if self.topk_mode == "auto" else self.topk_mode
@@ -470,6 +523,10 @@ class NextItemPredictionTask(nn.Module):
         mod = self.pre.module
         if training or testing:
             self._training_call = bool(training)
+            if training:
+                # the optimizer step that follows may write the weights through raw pointers (FusedAdam): no version counter
+                # sees that, so the image is re-packed by the next inference call whatever the record says
+                self._serving_image = None
             n, pos, lab = self.masking.compact_labels()
             # N shapes the row-compacted operands; it was copied to the host right after the masking kernel
             # (masking.n_labels): by now it has long arrived, so this does not drain the queue
@@ -499,6 +556,18 @@ class NextItemPredictionTask(nn.Module):
         W = mod.output_weights.detach()
         T = float(mod.softmax_temperature) if mod.softmax_temperature else 1.0
         V = W.shape[0]
+        image = self._serving_weights()
+        if image is not None:
+            # served from the half-precision image: fused head for top-k, [B, V] fp32 scores otherwise; topk_mode plays no part
+            if not torch.is_grad_enabled():
+                from . import torch_ops  # noqa: F401
+
+                if top_k is not None:
+                    return torch.ops.t4r_hip.item_topk(xr, image, 1.0 / T, top_k)
+                return torch.ops.t4r_hip.item_scores(xr, image, 1.0 / T)
+            if top_k is not None:
+                return ops.item_topk(xr, image, top_k, alpha=1.0 / T)
+            return ops.item_scores(xr, image, alpha=1.0 / T)
         fused_topk = top_k is not None and self.resolve_topk_mode(B, V) == "fused"
         if not torch.is_grad_enabled():      # registered operators (torch_ops.py): dispatcher-visible inference head
             from . import torch_ops  # noqa: F401

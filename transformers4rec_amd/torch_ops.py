@@ -50,7 +50,10 @@ def _(a, b, trans_a, trans_b, alpha):
 @torch.library.custom_op(f"{NS}::item_scores", mutates_args=())
 def item_scores(x: torch.Tensor, weight: torch.Tensor, alpha: float) -> torch.Tensor:
     """next-item scores x [N, D] @ weight[V, D]^T * alpha (prediction_task.py:648-671), rows padded to 256-byte
-    boundaries internally; returns the [N, V] view"""
+    boundaries internally; returns the [N, V] view.  A 16-bit weight is a serving image (pack_item_table): one 16-bit
+    matrix-core product per multiply (csrc/item_topk_h16.hip)"""
+    if weight.dtype != torch.float32:
+        return ops.item_scores(x, weight, alpha)
     V = weight.shape[0]
     return ops.gemm(x.contiguous(), weight, False, True, alpha=alpha, ldc=ops.pad_ld(V))[:, :V]
 
@@ -76,7 +79,8 @@ def _(scores, k):
 @torch.library.custom_op(f"{NS}::item_topk", mutates_args=())
 def item_topk(x: torch.Tensor, weight: torch.Tensor, alpha: float, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """top-k item scores and ids of x [N, D] @ weight[V, D]^T * alpha per row, sorted, without the [N, V] scores: item_scores
-    (fp32 matrix cores) + topk in one pass over the table (csrc/item_topk.hip)"""
+    (fp32 matrix cores) + topk in one pass over the table (csrc/item_topk.hip); over a 16-bit serving image
+    (pack_item_table) the same on the 16-bit matrix cores (csrc/item_topk_h16.hip)"""
     vals, idx = ops.item_topk(x, weight, k, alpha)
     return vals, idx
 
@@ -84,6 +88,22 @@ def item_topk(x: torch.Tensor, weight: torch.Tensor, alpha: float, k: int) -> Tu
 @item_topk.register_fake
 def _(x, weight, alpha, k):
     return x.new_empty((x.shape[0], k)), x.new_empty((x.shape[0], k), dtype=torch.int64)
+
+
+@torch.library.custom_op(f"{NS}::pack_item_table", mutates_args=())
+def pack_item_table(weight: torch.Tensor, dtype: str) -> torch.Tensor:
+    """serving image of an item table: weight [V, D] fp32 rounded once to "fp16" / "bf16", rows padded to 16-byte
+    boundaries; returns the [V, D] view (what autocast's cast of the output weights is, trainer.py:363-367)"""
+    return ops.pack_item_table(weight, dtype)
+
+
+@pack_item_table.register_fake
+def _(weight, dtype):
+    if dtype not in ("fp16", "bf16"):
+        raise ValueError(f"pack_item_table: dtype must be 'fp16' or 'bf16' (got {dtype!r})")
+    V, D = weight.shape
+    td = torch.float16 if dtype == "fp16" else torch.bfloat16
+    return weight.new_empty((V, (D + 15) // 16 * 16), dtype=td)[:, :D]
 
 
 @torch.library.custom_op(f"{NS}::rank_of_target", mutates_args=())
@@ -675,7 +695,7 @@ def _am_backward(ctx, dy):
 apply_mask.register_autograd(_am_backward, setup_context=_am_setup)
 
 
-OPERATORS = ("gemm", "item_scores", "topk", "item_topk", "rank_of_target", "embedding_gather", "embedding_bag", "ragged_to_padded",
+OPERATORS = ("gemm", "item_scores", "topk", "item_topk", "pack_item_table", "rank_of_target", "embedding_gather", "embedding_bag", "ragged_to_padded",
              "xlnet_layer_infer", "xlnet_layer_fwd", "xlnet_layer_bwd", "mlm_targets", "seq_item_embedding",
              "seq_item_embedding_bwd", "xlnet_layer_grad", "gather_label_rows", "scatter_label_rows", "linear_softmax_ce",
              "linear_softmax_ce_bwd", "dropout", "pos_emb_dropout", "next_item_head", "next_item_head_bwd",
