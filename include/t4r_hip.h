@@ -633,6 +633,24 @@ long t4r_item_topk_h16_ws_bytes(int n_rows, int V, int D, int k);
 int t4r_item_topk_h16(void* stream, int n_rows, int V, int D, float alpha, const float* X, long ldx, const void* image,
                       long ldp, int dtype, int k, float* out_val, long* out_idx, void* workspace, long ws_bytes,
                       long* host_stats);
+/* Evaluation head over the same serving image (csrc/item_eval_h16.hip): what the reference's Trainer.evaluate computes per label
+ * row under fp16=True / bf16=True (autocast, torch/trainer.py:363-367) -- logits model/prediction_task.py:430 -> log_softmax +
+ * CrossEntropyLoss for the loss, torch.topk + the [N, V] one-hot of ranking_metric.py:52-59 for the metrics -- in ONE pass over
+ * the image and without the [n_rows, V] scores.  With s[n, v] the bits t4r_item_scores_h16 returns for the same X, image, alpha, dtype:
+ *   target[n]    = s[n, labels[n]], bit for bit
+ *   rank[n]      = #{v : s[n,v] > target[n] or (s[n,v] == target[n] and v < labels[n])}   (the rule of t4r_rank_of_target_f32)
+ *   lse[n]       = log sum_v exp(s[n,v]), fp32 with a running maximum (any score range)
+ *   score_sum[n] = sum_v s[n,v], fp32: loss[n] = (1 - eps)(lse - target) + eps (lse - score_sum / V) under label smoothing eps
+ * A label outside [0, V) gives target = NaN and rank = V (lse and score_sum stay valid); a NaN in a row of X gives a non-finite
+ * lse in that row only.  Any n_rows, any V, 1 <= D <= 512, dtype 2 / 3.  No allocation, no host read-back, no synchronisation:
+ * everything runs on the caller's stream.  A row's four outputs do not depend on n_rows, on the other rows or on the call (fixed
+ * reduction orders, a split of V over workgroups that is a function of V alone, integer atomics only).
+ * workspace: t4r_item_eval_h16_ws_bytes(n_rows, V, D) bytes (0 for non-positive sizes), 16-byte aligned, contents undefined on
+ * entry and exit: the 16-bit image of X and n_rows x 16 bytes of partial statistics per workgroup (at most ~2048, or V / 4096). */
+long t4r_item_eval_h16_ws_bytes(int n_rows, int V, int D);
+int t4r_item_eval_h16(void* stream, int n_rows, int V, int D, float alpha, const float* X, long ldx, const void* image,
+                      long ldp, int dtype, const long* labels, float* lse, float* target, float* score_sum, int* rank,
+                      void* workspace, long ws_bytes);
 
 /* ----------------------------------------------------------------------------------------
  * train-time input regularisers (pre / post transformations of the input block)

@@ -138,6 +138,8 @@ _SIGS = {
     "t4r_item_scores_h16": ("i", "p" + "iiif" + "pl" + "pl" + "i" + "pl" + "pl"),
     "t4r_item_topk_h16_ws_bytes": ("l", "iiii"),
     "t4r_item_topk_h16": ("i", "p" + "iiif" + "pl" + "pl" + "i" + "i" + "pp" + "pl" + "p"),
+    "t4r_item_eval_h16_ws_bytes": ("l", "iii"),
+    "t4r_item_eval_h16": ("i", "p" + "iiif" + "pl" + "pl" + "i" + "p" + "pppp" + "pl"),
     "t4r_swap_noise_ws_bytes": ("l", "l"),
     "t4r_swap_noise": ("i", "ppp" + "il" + "pllf" + "pp" + "QQ" + "pl"),
     "t4r_copy_cols": ("i", "pp" + "li" + "p" + "ili"),

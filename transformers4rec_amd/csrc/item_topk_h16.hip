@@ -26,6 +26,7 @@
 //                             one row), one returning slot atomic by the half's first lane, hits stored at base + prefix.
 //                             `stride` > 1 scores the strided sample of step 1 in place (item i of the launch is image row
 //                             i * stride): no gathered copy of the sample.
+//                             The tile load and the k loop live in item_h16_tile.h, shared with item_eval_h16.hip.
 //   select / threshold top-k  itk_select_kernel (item_topk.hip) and t4r_topk, unchanged; the plan is item_topk_plan.h's.
 //
 // Bits.  One element is computed by ONE instruction sequence whatever launch, tile or row block it sits in: k runs 0, 16, 32, ...
@@ -40,27 +41,13 @@
 // entries at 64 x 4099 x 128): the matrix cores HONOUR subnormal fp16 operands -- largest error 9.6e-6, inside the plain
 // accumulation bound at every element, against 5.0e-4 to a reference with those entries flushed.  The contract tests still allow
 // either behaviour for entries below 2^-14.
+#include "item_h16_tile.h"
 #include "item_topk_plan.h"
 #include <vector>
 
 extern "C" int t4r_topk(void* stream, const float* scores, int N, int V, long ld, int k, float* out_val, long* out_idx);
 
-#define ITK16_MAX_D 512
-#define ITK16_TILE 64          // image rows per workgroup
-
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-
-template <int DT>
-__device__ __forceinline__ uint32_t round16(float f) {
-    if (DT == 3) return (uint32_t)__builtin_bit_cast(unsigned short, (_Float16)f);       // v_cvt_f16_f32, RNE
-    const uint32_t u = __builtin_bit_cast(uint32_t, f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0u;                                 // NaN
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;                                       // RNE (overflow rounds to inf)
-}
 
 // one 16-byte chunk (8 elements) per thread
 template <int DT>
@@ -101,54 +88,18 @@ struct Itk16Params {
     int cap;
 };
 
-template <int DT>
-__device__ __forceinline__ f32x16 mfma16(uint4 a, uint4 b, f32x16 c) {
-    if (DT == 3)
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, a), __builtin_bit_cast(half8_t, b), c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
-
 template <int DT, int EPI>
 __global__ __launch_bounds__(256) void itk16_kernel(Itk16Params p) {
     extern __shared__ uint4 itk16_lds[];                    // [64][chunks + 1] 16-byte slots
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int chunks = p.ldp >> 3, pitch = chunks + 1;
     const long item0 = (long)blockIdx.x * ITK16_TILE;
-    // the image tile, eight 16-byte loads in flight per thread: every load reads a legal address (row clamped into the launch's
-    // items) and rows beyond them are zeroed on the way to LDS (their columns are masked in the epilogue as well)
-    {
-        const int dr = 256 / chunks, dc = 256 - dr * chunks;  // chunk index + 256 = (row + dr, chunk + dc), carried below
-        int tr = tid / chunks, tc = tid - tr * chunks;
-        const long last = (long)p.n_items - 1 - item0;        // last tile row inside the launch's items (>= 0)
-        const long rstep = (long)p.stride * p.ldi;
-        const uint16_t* base = p.img + item0 * rstep;
-        while (tr < ITK16_TILE) {                              // workgroup-divergent only in its last batch
-            uint4 v[8];
-            int off[8];                                        // LDS slot; -1: beyond the tile; bit 30: zero it
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const long rr = min((long)min(tr, ITK16_TILE - 1), last);
-                v[u] = *reinterpret_cast<const uint4*>(base + rr * rstep + tc * 8);
-                off[u] = tr >= ITK16_TILE ? -1 : ((tr * pitch + tc) | (tr > last ? 1 << 30 : 0));
-                tc += dc; tr += dr;
-                if (tc >= chunks) { tc -= chunks; ++tr; }
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                // first use of the staged registers: keeps the eight loads above in one batch
-                asm volatile("" : "+v"(v[u].x), "+v"(v[u].y), "+v"(v[u].z), "+v"(v[u].w));
-                const bool z = (off[u] & (1 << 30)) != 0;
-                uint4 w;
-                w.x = z ? 0u : v[u].x; w.y = z ? 0u : v[u].y; w.z = z ? 0u : v[u].z; w.w = z ? 0u : v[u].w;
-                if (off[u] >= 0) itk16_lds[off[u] & ~(1 << 30)] = w;
-            }
-        }
-    }
+    itk16_load_tile(itk16_lds, p.img, p.ldi, p.stride, item0, p.n_items, chunks, tid);
     __syncthreads();
     const int r = lane & 31, h = lane >> 5;
     const uint4* b0p = itk16_lds + r * pitch + h;           // items item0 + r and item0 + 32 + r; k-step s is slot 2 s + h
     const uint4* b1p = itk16_lds + (32 + r) * pitch + h;
-    const int nk = p.ldp >> 4, ng = nk >> 2;                // k-steps, and groups of four of them
+    const int nk = p.ldp >> 4;                              // k-steps
     const float alpha = p.alpha;
     for (int rb = wave * 32; rb < p.n_rows; rb += 128) {    // wave-uniform
         // rows beyond n_rows read the last row (a legal address) and are masked in the epilogue
@@ -160,33 +111,7 @@ __global__ __launch_bounds__(256) void itk16_kernel(Itk16Params p) {
                 thr[e] = p.thr[(long)min(rb + (e & 3) + 8 * (e >> 2) + 4 * h, p.n_rows - 1) * p.thr_ld];
         }
         f32x16 acc[2];
-#pragma unroll
-        for (int e = 0; e < 16; ++e) { acc[0][e] = 0.f; acc[1][e] = 0.f; }
-        // k runs 0 .. nk-1 in order into the same two accumulators; the grouping only keeps the next four A fragments in flight
-        uint4 a[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) a[u] = ap[2 * min(u, nk - 1)];
-        for (int g = 0; g < ng; ++g) {
-            uint4 an[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) an[u] = ap[2 * min(4 * g + 4 + u, nk - 1)];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const uint4 b0 = b0p[2 * (4 * g + u)], b1 = b1p[2 * (4 * g + u)];
-                acc[0] = mfma16<DT>(a[u], b0, acc[0]);
-                acc[1] = mfma16<DT>(a[u], b1, acc[1]);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) a[u] = an[u];
-        }
-#pragma unroll
-        for (int u = 0; u < 3; ++u) {                       // at most three more steps; a[] holds their fragments already
-            if (4 * ng + u < nk) {                          // wave-uniform
-                const uint4 b0 = b0p[2 * (4 * ng + u)], b1 = b1p[2 * (4 * ng + u)];
-                acc[0] = mfma16<DT>(a[u], b0, acc[0]);
-                acc[1] = mfma16<DT>(a[u], b1, acc[1]);
-            }
-        }
+        itk16_product<DT>(ap, b0p, b1p, nk, acc);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const long col = item0 + j * 32 + r;
@@ -248,6 +173,12 @@ int round_rows(hipStream_t st, int dtype, const float* src, long ld, long rows, 
 long image_ld(long D) { return (D + 15) / 16 * 16; }
 
 }  // namespace
+
+// for item_eval_h16.hip (item_h16_tile.h): the same pitch and the same rounding of x as every entry of this file
+long t4r_itk16_image_ld(long D) { return image_ld(D); }
+int t4r_itk16_round_rows(hipStream_t st, int dtype, const float* src, long ld, long rows, int D, uint16_t* dst, long ldp) {
+    return round_rows(st, dtype, src, ld, rows, D, dst, ldp);
+}
 
 extern "C" int t4r_item_table_image_ld(int D) { return D > 0 ? (int)image_ld(D) : 0; }
 

@@ -510,6 +510,17 @@ class _HipTaskMixin:
     def serving_packs(self):
         return self.hip_shadow().serving_packs
 
+    def evaluate_batch(self, inputs):
+        """loss + target ranks + metrics of the batch the HIP TabularSequenceFeatures has just masked, in one pass over the
+        serving image if there is one (NextItemPredictionTask.evaluate_batch of the shadow)"""
+        sh = self.hip_shadow()
+        hm = self.masking.__dict__.get("_t4r_hip_masking") if self.masking is not None else None
+        if hm is None or hm.masked_targets is not self.masking.masked_targets:
+            raise RuntimeError("dropin: the HIP NextItemPredictionTask reads the label compaction of the HIP "
+                               "TabularSequenceFeatures; install / convert both modules")
+        sh.masking = hm
+        return sh.evaluate_batch(inputs)
+
     def forward(self, inputs, targets=None, training=False, testing=False, top_k=None, **kwargs):
         sh = self.hip_shadow()
         hm = self.masking.__dict__.get("_t4r_hip_masking") if self.masking is not None else None

@@ -1232,6 +1232,39 @@ def item_topk(x, W, k, alpha=1.0):
     return vals, idx
 
 
+def item_eval(x, image, labels, alpha=1.0):
+    """(lse, target, score_sum fp32 [N], rank int32 [N]) of the rows of item_scores(x, image, alpha) in ONE pass over the serving
+    image, without the [N, V] scores (csrc/item_eval_h16.hip): lse = logsumexp of the row, target = its score of labels[n] (the
+    bits item_scores returns), score_sum = the row's sum, rank = how many items beat the target (ties to the lower index, the
+    rule of rank_of_target).  Cross entropy with label smoothing eps: (1 - eps)(lse - target) + eps (lse - score_sum / V).
+    A label outside [0, V) gives target NaN and rank V.  image must be a serving image (pack_item_table); labels int64 [N].
+    No synchronisation; a row's outputs do not depend on the other rows of the call."""
+    if image.dtype == torch.float32:       # before the device checks: the one mistake a caller of item_scores / item_topk makes
+        raise TypeError("item_eval: W must be a serving image (ops.pack_item_table(W, 'fp16' | 'bf16')), got torch.float32; "
+                        "for an fp32 table use rank_of_target and linear_softmax_ce_fwd")
+    _check_x_w("item_eval", x, image)
+    if not labels.is_cuda:
+        raise _lib.T4RHipError(f"item_eval: labels must be a HIP device tensor (got {labels.device}); there is no CPU path")
+    if labels.dtype != torch.int64:
+        raise TypeError(f"item_eval: labels: expected torch.int64, got {labels.dtype}")
+    N, D = x.shape
+    V = image.shape[0]
+    if labels.dim() != 1 or labels.shape[0] != N:
+        raise ValueError(f"item_eval: labels must be [N] = [{N}] (got {tuple(labels.shape)})")
+    if V < 1:
+        raise ValueError("item_eval: the image has no rows")
+    ldp = _check_image("item_eval", image, D)
+    labels = labels.contiguous()
+    lse, target, score_sum = (torch.empty(N, device=x.device, dtype=torch.float32) for _ in range(3))
+    rank = torch.empty(N, device=x.device, dtype=torch.int32)
+    if N:
+        ws = torch.empty(_lib.load().t4r_item_eval_h16_ws_bytes(N, V, D), device=x.device, dtype=torch.uint8)
+        call("t4r_item_eval_h16", _stream(), N, V, D, float(alpha), x.data_ptr(), x.stride(0) if N > 1 else D, image.data_ptr(),
+             ldp, _H16[image.dtype], labels.data_ptr(), lse.data_ptr(), target.data_ptr(), score_sum.data_ptr(), rank.data_ptr(),
+             ws.data_ptr(), ws.numel())
+    return lse, target, score_sum, rank
+
+
 # the record behind item_topk_stats(): kept here, the library has no state of its own
 _ITEM_TOPK = dict(calls=0, calls_h16=0, dtype=None, fallback_rows=0, sample_rows=0, list_capacity=0, cand_sum=0, cand_max=0,
                   collect_counts=False)

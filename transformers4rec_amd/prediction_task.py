@@ -641,6 +641,48 @@ class NextItemPredictionTask(nn.Module):
         ranks = ops.rank_of_target(xr, mod.output_weights.detach(), labels, 1.0 / T)
         return {"labels": labels, "ranks": ranks, "metrics": self.metrics_from_ranks(ranks)}
 
+    def evaluate_batch(self, inputs):
+        """Loss AND ranking metrics of an evaluation batch without the [N, V] scores: the label rows of `inputs` [B, L, D]
+        (row selection, task block and temperature as evaluate_ranks) -> {"loss", "loss_rows", "labels", "ranks", "metrics"};
+        metrics are also accumulated for compute_metrics().  loss_rows = (1 - eps)(lse - target) + eps (lse - sum / V) with the
+        task's label smoothing eps, loss its mean.
+        With a serving image (prepare_serving): ONE pass over the image (ops.item_eval) in the arithmetic the model is served
+        in -- one 16-bit matrix-core product per multiply, what the reference's Trainer.evaluate computes under fp16=True /
+        bf16=True.  Without one: the fp32 kernels, ops.rank_of_target for the ranks and the non-materialising cross-entropy
+        forward (ops.linear_softmax_ce_fwd) for the loss -- two passes over the fp32 table."""
+        if self.pre is None:
+            raise RuntimeError("evaluate_batch: the task is not built yet")
+        x = (inputs[0] if isinstance(inputs, (tuple, list)) else inputs).float()
+        mod = self.pre.module
+        n, pos, lab = self.masking.compact_labels()
+        N = self.masking.n_labels()
+        if N == 0:
+            raise ValueError("no label positions in this batch")
+        labels = lab[:N]
+        B, L, D = x.shape
+        xr = ops.gather_rows(x.detach().contiguous().view(B * L, D), pos, N)
+        if self.task_block is not None:
+            lin = self.task_block[0][0]
+            xr = ops.gemm(xr, lin.weight.detach(), False, True, bias=lin.bias.detach(), epilogue=ops.EPI_BIAS)
+        T = float(mod.softmax_temperature) if mod.softmax_temperature else 1.0
+        smooth = float(getattr(self.loss, "label_smoothing", 0.0) or 0.0)
+        image = self._serving_weights()
+        if image is not None:
+            if not torch.is_grad_enabled():
+                from . import torch_ops  # noqa: F401
+
+                lse, target, score_sum, ranks = torch.ops.t4r_hip.item_eval(xr, image, labels, 1.0 / T)
+            else:
+                lse, target, score_sum, ranks = ops.item_eval(xr, image, labels, alpha=1.0 / T)
+            loss_rows = (1.0 - smooth) * (lse - target) + smooth * (lse - score_sum / image.shape[0])
+            loss = loss_rows.mean()
+        else:
+            W = mod.output_weights.detach()
+            ranks = ops.rank_of_target(xr, W, labels, 1.0 / T)
+            loss, loss_rows, _lse = ops.linear_softmax_ce_fwd(xr, W, labels, 1.0 / T, smooth)
+        return {"loss": loss, "loss_rows": loss_rows, "labels": labels, "ranks": ranks,
+                "metrics": self.metrics_from_ranks(ranks)}
+
     def compute_metrics(self, mode=None, group=None):
         """{"<task>/<metric>_<k>": mean over ALL rows seen since reset_metrics()}.  Under torch.distributed
         (world_size > 1) the (sum, count) state is all-reduced first -- the reference `cat`-synchronises the

@@ -90,6 +90,22 @@ def _(x, weight, alpha, k):
     return x.new_empty((x.shape[0], k)), x.new_empty((x.shape[0], k), dtype=torch.int64)
 
 
+@torch.library.custom_op(f"{NS}::item_eval", mutates_args=())
+def item_eval(x: torch.Tensor, weight: torch.Tensor, labels: torch.Tensor,
+              alpha: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(lse, target score, score sum, target rank) per row of x [N, D] @ weight[V, D]^T * alpha over a 16-bit serving image
+    (pack_item_table), in one pass and without the [N, V] scores: the loss and ranking metrics of an evaluation under autocast
+    (trainer.py:363-367, prediction_task.py:430, ranking_metric.py:52-59; csrc/item_eval_h16.hip)"""
+    lse, target, score_sum, rank = ops.item_eval(x, weight, labels, alpha)
+    return lse, target, score_sum, rank
+
+
+@item_eval.register_fake
+def _(x, weight, labels, alpha):
+    n = x.shape[0]
+    return x.new_empty((n,)), x.new_empty((n,)), x.new_empty((n,)), x.new_empty((n,), dtype=torch.int32)
+
+
 @torch.library.custom_op(f"{NS}::pack_item_table", mutates_args=())
 def pack_item_table(weight: torch.Tensor, dtype: str) -> torch.Tensor:
     """serving image of an item table: weight [V, D] fp32 rounded once to "fp16" / "bf16", rows padded to 16-byte
@@ -695,7 +711,7 @@ def _am_backward(ctx, dy):
 apply_mask.register_autograd(_am_backward, setup_context=_am_setup)
 
 
-OPERATORS = ("gemm", "item_scores", "topk", "item_topk", "pack_item_table", "rank_of_target", "embedding_gather", "embedding_bag", "ragged_to_padded",
+OPERATORS = ("gemm", "item_scores", "topk", "item_topk", "item_eval", "pack_item_table", "rank_of_target", "embedding_gather", "embedding_bag", "ragged_to_padded",
              "xlnet_layer_infer", "xlnet_layer_fwd", "xlnet_layer_bwd", "mlm_targets", "seq_item_embedding",
              "seq_item_embedding_bwd", "xlnet_layer_grad", "gather_label_rows", "scatter_label_rows", "linear_softmax_ce",
              "linear_softmax_ce_bwd", "dropout", "pos_emb_dropout", "next_item_head", "next_item_head_bwd",
