@@ -46,6 +46,15 @@ def test_workspace_size_is_pure_positive_and_monotone():
         assert ws(N, V, D) < 4 * N * ops.pad_ld(V) / 8, (N, V, D, ws(N, V, D))
 
 
+def test_workspace_sizes_are_the_recorded_ones():
+    """(N, V, D) -> bytes, as the build before the image contract moved into item_h16_tile.h returned them (the shapes of the
+    two top-k heads' tables, without their k)"""
+    ws = _lib.load().t4r_item_eval_h16_ws_bytes
+    for shape, b in [((1, 7, 8), 272), ((12, 5000, 32), 15936), ((37, 4099, 100), 46928), ((1024, 100001, 128), 25870336),
+                     ((1024, 1000001, 256), 34078720), ((256, 10000001, 512), 10264576)]:
+        assert ws(*shape) == b, (shape, ws(*shape), b)
+
+
 def test_argument_errors_come_back_as_messages_before_any_launch():
     lib = _lib.load()
     P, WS = 64, 1 << 30           # never dereferenced: every call below is refused by the argument checks

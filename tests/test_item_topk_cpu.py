@@ -33,6 +33,15 @@ def test_workspace_is_far_below_the_score_matrix():
     assert lib.t4r_item_topk_ws_bytes(0, 7, 8, 7) == 0
 
 
+def test_workspace_sizes_are_the_recorded_ones():
+    """(N, V, D, k) -> bytes, as the build before the two heads got one driver returned them: the plan did not move"""
+    ws = _lib.load().t4r_item_topk_ws_bytes
+    for shape, b in [((1, 7, 8, 7), 1536), ((12, 5000, 32, 10), 378624), ((37, 4099, 100, 1), 1168640),
+                     ((1024, 100001, 128, 20), 35610880), ((1024, 1000001, 256, 100), 261939456),
+                     ((256, 10000001, 512, 10), 132242432)]:
+        assert ws(*shape) == b, (shape, ws(*shape), b)
+
+
 def test_argument_errors_come_back_as_messages():
     lib = _lib.load()
     rc = lib.t4r_item_topk_f32(None, 4, 100, 8, 1.0, None, 8, None, 8, 10, None, None, None, 0, None)

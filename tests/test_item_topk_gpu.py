@@ -130,6 +130,36 @@ def test_overflow_rows_take_the_materialised_path(case, k):
     assert torch.equal(i, i2) and torch.equal(v, v2)
 
 
+@pytest.mark.parametrize("table", ["fp32", "fp16", "bf16"])
+def test_overflow_rows_with_gaps_between_them(table):
+    """Six all-zero rows of x (every score tied at 0: more candidates than any list holds) among ordinary ones, as the runs
+    {0, 1, 2}, {5}, {9, 10}: the overflow path recomputes runs of consecutive rows together and must split at the gaps.
+    M = 1024 < V and cap = 2048 < V here, so exactly those six rows overflow (the others expect ~49 candidates).  Both heads
+    go through the one driver (csrc/item_topk_plan.h: itk_run)."""
+    from transformers4rec_amd import ops
+
+    N, V, D, k = 12, 5000, 32, 10
+    x, W = _inputs(N, V, D, 13)
+    x[[0, 1, 2, 5, 9, 10]] = 0.0
+    xd, Wd = x.to(DEV), W.to(DEV)
+    if table == "fp32":
+        rv, ri = _stable_reference(ops, xd, Wd, k)
+    else:
+        import test_item_topk_h16_gpu as h16
+
+        Wd = ops.pack_item_table(Wd, table)
+        rv, ri = h16._stable_reference(ops, xd, Wd, k)
+    v, i = ops.item_topk(xd, Wd, k)
+    st = ops.item_topk_stats()
+    print(f"[item_topk overflow gaps] {table}: fallback rows {st['fallback_rows']} of {N} (sample {st['sample_rows']}, "
+          f"cap {st['list_capacity']})")
+    assert st["sample_rows"] < V and st["list_capacity"] < V
+    assert st["fallback_rows"] == 6
+    assert torch.equal(i.cpu(), ri) and torch.equal(v.cpu(), rv)
+    v2, i2 = ops.item_topk(xd, Wd, k)
+    assert torch.equal(i, i2) and torch.equal(v, v2)
+
+
 # ------------------------------------------------------------------------------------------------ reference fixtures
 INFER_FIXTURES = [
     ("xlnet_mlm_item_infer", "xlnet_mlm_item_train", dict(emb_default=32)),

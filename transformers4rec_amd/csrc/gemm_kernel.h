@@ -33,6 +33,7 @@
 // enough workgroups to fill 256 CUs.
 #pragma once
 #include "t4r_common.h"
+#include "item_topk_collect.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -713,9 +714,6 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
         return;
     }
     if constexpr (TOPK) {
-        // One 32-lane half of the wave holds 32 consecutive columns of one output row.  The halves that found candidates reserve
-        // their slots with ONE returning atomic each (lane 0 of the half) and every candidate stores at base + its prefix in the
-        // half's ballot.  Most ballots are empty (a row keeps a few hundred of its V scores): those cost a compare and a branch.
 #pragma unroll
         for (int i = 0; i < WM; ++i) {
 #pragma unroll
@@ -726,18 +724,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
                     const int row = m0 + wm * (BM / 2) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
                     const int rr = min(row, p.M - 1);
                     const float v = alpha * acc[i][j][r], t = p.tk_thr[(long)rr * p.tk_thr_ld];
-                    const bool hit = col < p.N && row < p.M && v >= t;
-                    const unsigned long long m = __ballot(hit);
-                    if (m == 0) continue;                       // wave-uniform
-                    const unsigned mh = (unsigned)(khalf ? (m >> 32) : (m & 0xffffffffull));
-                    int base = 0;
-                    if ((lane & 31) == 0 && mh) base = atomicAdd(p.tk_count + row, __popc(mh));
-                    base = __shfl(base, lane & 32, 64);
-                    const int slot = base + __popc(mh & ((1u << (lane & 31)) - 1u));
-                    if (hit && slot < p.tk_cap) {
-                        p.tk_val[(long)row * p.tk_cap + slot] = v;
-                        p.tk_idx[(long)row * p.tk_cap + slot] = col;
-                    }
+                    itk_collect(col < p.N && row < p.M && v >= t, v, col, row, lane, p.tk_count, p.tk_val, p.tk_idx, p.tk_cap);
                 }
             }
         }

@@ -69,7 +69,7 @@ __global__ __launch_bounds__(64) void itev16_target_kernel(Itev16Params p) {
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[e] = 0.f;
     for (int s = 0; s < nk; ++s) acc = mfma16<DT>(ap[2 * s], bp[2 * s], acc);
-    // element e of lane (r, h) is row (e & 3) + 8 (e >> 2) + 4 h, column r: the diagonal entry of column r sits in half (r >> 2) & 1
+    // element e of lane (r, h) is row itk16_acc_row(e, h), column r: the diagonal entry of column r sits in half (r >> 2) & 1
     const int ed = (r & 3) + 4 * (r >> 3);
     float d = 0.f;
 #pragma unroll
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(256) void itev16_kernel(Itev16Params p) {
     const float ninf = -__builtin_inff();
     const long t0 = (long)blockIdx.x * p.G, t1 = min(t0 + p.G, p.tiles);
     float4* part = p.part + (long)blockIdx.x * p.n_rows;
-    const int krow = (r & 3) + 8 * ((r & 15) >> 2) + 4 * h;  // the row (within the block) whose statistics this lane keeps
+    const int krow = itk16_acc_row(r & 15, h);              // the row (within the block) whose statistics this lane keeps
     for (long t = t0; t < t1; ++t) {
         const long item0 = t * ITK16_TILE;
         if (t > t0) __syncthreads();                        // every wave is done with the previous tile
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(256) void itev16_kernel(Itev16Params p) {
             float km = ninf, ks = 0.f, kq = 0.f;
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int row = rb + (e & 3) + 8 * (e >> 2) + 4 * h, rc = min(row, p.n_rows - 1);
+                const int row = rb + itk16_acc_row(e, h), rc = min(row, p.n_rows - 1);
                 const float tg = p.target[rc];
                 const int lab = (int)p.labels[rc];          // a label outside [0, V) has a NaN target: no hit whatever this is
                 const float v0 = alpha * acc[0][e], v1 = alpha * acc[1][e];
@@ -196,7 +196,7 @@ template <int DT>
 int launch_t(hipStream_t st, const Itev16Params& p) {
     hipLaunchKernelGGL((itev16_target_kernel<DT>), dim3((unsigned)((p.n_rows + 31) / 32)), dim3(64), 0, st, p);
     T4R_LAUNCH_CHECK();
-    const size_t smem = (size_t)ITK16_TILE * ((size_t)(p.ldp >> 3) + 1) * 16;
+    const size_t smem = itk16_lds_bytes(p.ldp);
     t4r_ensure_dynamic_lds((const void*)itev16_kernel<DT>, smem, g_lds_attr[DT - 2]);
     hipLaunchKernelGGL((itev16_kernel<DT>), dim3((unsigned)p.groups), dim3(256), smem, st, p);
     T4R_LAUNCH_CHECK();
@@ -223,7 +223,7 @@ extern "C" long t4r_item_eval_h16_ws_bytes(int n_rows, int V, int D) {
     // sized for the most groups any V' <= V can have (the count itself steps down where G steps up): never decreases in V
     const long tiles = ((long)V + ITK16_TILE - 1) / ITK16_TILE;
     const long most = tiles <= ITEV16_GROUPS ? tiles : std::max((long)ITEV16_GROUPS, (tiles + ITEV16_MAX_G - 1) / ITEV16_MAX_G);
-    return (long)(x16_bytes(n_rows, t4r_itk16_image_ld(D)) + (size_t)most * n_rows * sizeof(float4));
+    return (long)(x16_bytes(n_rows, itk16_image_ld(D)) + (size_t)most * n_rows * sizeof(float4));
 }
 
 extern "C" int t4r_item_eval_h16(void* stream, int n_rows, int V, int D, float alpha, const float* X, long ldx, const void* image,
@@ -232,12 +232,10 @@ extern "C" int t4r_item_eval_h16(void* stream, int n_rows, int V, int D, float a
     if (n_rows == 0) return 0;
     T4R_CHECK_ARG(n_rows > 0 && V > 0 && D > 0 && X && image, "item_eval_h16: bad arguments");
     T4R_CHECK_ARG(labels && lse && target && score_sum && rank, "item_eval_h16: labels and the four outputs must not be null");
-    T4R_CHECK_ARG(D <= ITK16_MAX_D, "item_eval_h16: 1 <= D <= 512 (t4r_item_topk_h16_supported)");
+    T4R_CHECK_ARG(itk16_supported(D), "item_eval_h16: 1 <= D <= 512 (t4r_item_topk_h16_supported)");
     T4R_CHECK_ARG(ldx >= D, "item_eval_h16: row pitch below D");
-    T4R_CHECK_ARG(dtype == 2 || dtype == 3, "item_eval_h16: dtype is 2 (bf16) or 3 (fp16), the codes of T4R_GEMM_PREC");
-    const long kp = t4r_itk16_image_ld(D);
-    T4R_CHECK_ARG(ldp >= kp && ldp % 8 == 0 && (uintptr_t)image % 16 == 0,
-                  "item_eval_h16: image rows must be 16-byte aligned with pitch >= t4r_item_table_image_ld(D)");
+    ITK16_CHECK_IMAGE("item_eval_h16");
+    const long kp = itk16_image_ld(D);
     T4R_CHECK_ARG(workspace && ws_bytes >= t4r_item_eval_h16_ws_bytes(n_rows, V, D) && (uintptr_t)workspace % 16 == 0,
                   "item_eval_h16: workspace too small (t4r_item_eval_h16_ws_bytes) or not 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
@@ -249,5 +247,5 @@ extern "C" int t4r_item_eval_h16(void* stream, int n_rows, int V, int D, float a
     p.labels = labels; p.target = target; p.rank = rank; p.lse = lse; p.score_sum = score_sum;
     p.part = (float4*)((char*)workspace + x16_bytes(n_rows, kp));
     split_of(V, p.G, p.tiles, p.groups);
-    return dtype == 3 ? launch_t<3>(st, p) : launch_t<2>(st, p);
+    return itk16_dispatch(dtype, [&](auto dt) { return launch_t<decltype(dt)::value>(st, p); });
 }

@@ -2,11 +2,36 @@
 // fused top-k head) and item_eval_h16.hip (loss statistics and target ranks in one pass).  What is here IS the arithmetic
 // contract of the image: one element is k = 0, 16, 32, ... to ldp, each step one 16-bit MFMA into the same accumulator, whatever
 // kernel, launch, tile or row block computes it -- so both files return the same bits for the same (row, item).
+// The host side of the contract is here as well, once for every entry that takes an image: its pitch, the supported widths, the
+// argument check, the tile's LDS size and the dispatch on the image's dtype.
 #pragma once
 #include "t4r_common.h"
+#include <type_traits>
 
 #define ITK16_MAX_D 512
 #define ITK16_TILE 64          // image rows per workgroup tile
+
+// row pitch (elements) of an image of width D: D rounded up to the k step (16 elements = 32 bytes)
+static inline long itk16_image_ld(long D) { return (D + 15) / 16 * 16; }
+static inline bool itk16_supported(int D) { return D >= 1 && D <= ITK16_MAX_D; }
+// dynamic LDS of a workgroup's tile: [ITK16_TILE][ldp / 8 + 1] 16-byte slots (ldp: k extent, a multiple of 16)
+static inline size_t itk16_lds_bytes(int ldp) { return (size_t)ITK16_TILE * ((size_t)(ldp >> 3) + 1) * 16; }
+
+// f(std::integral_constant<int, DT>) with DT the image's dtype code: 2 = bf16, 3 = fp16 (the caller has checked it)
+template <class F>
+static inline int itk16_dispatch(int dtype, F&& f) {
+    return dtype == 3 ? f(std::integral_constant<int, 3>()) : f(std::integral_constant<int, 2>());
+}
+
+// the image arguments (dtype, image, ldp, D) of the entry `name`
+#define ITK16_CHECK_IMAGE(name)                                                                                                     \
+    T4R_CHECK_ARG(dtype == 2 || dtype == 3, name ": dtype is 2 (bf16) or 3 (fp16), the codes of T4R_GEMM_PREC");                    \
+    T4R_CHECK_ARG(ldp >= itk16_image_ld(D) && ldp % 8 == 0 && (uintptr_t)image % 16 == 0,                                           \
+                  name ": image rows must be 16-byte aligned with pitch >= t4r_item_table_image_ld(D)")
+
+// X fp32 [rows, D] (row pitch ld) -> dst [rows, ldp] in the image's dtype, RNE, pad columns zero (item_topk_h16.hip): the pack of
+// the table and the rounding of x of every entry
+int t4r_itk16_round_rows(hipStream_t st, int dtype, const float* src, long ld, long rows, int D, uint16_t* dst, long ldp);
 
 namespace {
 
@@ -64,8 +89,11 @@ __device__ __forceinline__ void itk16_load_tile(uint4* lds, const uint16_t* img,
     }
 }
 
+// C/D layout of the 32x32 MFMA: accumulator element e of a lane in half h (= lane >> 5) belongs to this row of the block
+__device__ __forceinline__ int itk16_acc_row(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
+
 // 32 rows of x16 (A fragments from ap, one 16-byte slot per k-step at stride 2) against the 64 items of the LDS tile (B fragments
-// from b0p / b1p: items r and 32 + r of the tile): acc[j][e] = sum over k of row (e & 3) + 8 (e >> 2) + 4 h, item 32 j + r.
+// from b0p / b1p: items r and 32 + r of the tile): acc[j][e] = sum over k of row itk16_acc_row(e, h), item 32 j + r.
 // k runs 0 .. nk-1 in order into the same two accumulators; the grouping only keeps the next four A fragments in flight.
 template <int DT>
 __device__ __forceinline__ void itk16_product(const uint4* ap, const uint4* b0p, const uint4* b1p, int nk, f32x16 (&acc)[2]) {
@@ -99,8 +127,3 @@ __device__ __forceinline__ void itk16_product(const uint4* ap, const uint4* b0p,
 }
 
 }  // namespace
-
-// host side of item_topk_h16.hip, for item_eval_h16.hip
-long t4r_itk16_image_ld(long D);
-// X fp32 [rows, D] (row pitch ld) -> dst [rows, ldp] in the image's dtype (2 = bf16, 3 = fp16), RNE, pad columns zero
-int t4r_itk16_round_rows(hipStream_t st, int dtype, const float* src, long ld, long rows, int D, uint16_t* dst, long ldp);

@@ -21,17 +21,16 @@
 //                 once per call (inference: one 4-byte device-to-host read) and flagged rows are recomputed through the
 //                 materialised path -- scores of those rows into the (now free) candidate region, then t4r_topk -- so the result
 //                 is exact for every input.
+//
+// The four steps and the overflow bookkeeping are itk_run (item_topk_plan.h), shared with item_topk_h16.hip; this file holds the
+// fp32 head's three products (Itk32Head), the gather of the sample and the select kernel.
 #include "t4r_common.h"
-#include <algorithm>
-#include <math.h>
-#include <vector>
 
 int t4r_gemm_fp32_nt_launch(hipStream_t stream, int M, int N, int K, float alpha, const float* A, long lda,
                             const float* B, long ldb, float* C, long ldc);
 int t4r_gemm_topk_collect_launch(hipStream_t stream, int n_rows, int V, int D, float alpha, const float* X, long ldx,
                                  const float* W, long ldw, const float* thr, long thr_ld, int* count, float* cand_val,
                                  int* cand_idx, int cap);
-extern "C" int t4r_topk(void* stream, const float* scores, int N, int V, long ld, int k, float* out_val, long* out_idx);
 
 #include "item_topk_plan.h"
 
@@ -104,9 +103,32 @@ __global__ __launch_bounds__(256) void itk_select_kernel(const float* __restrict
     }
 }
 
+// the fp32 table on the fp32 matrix cores (form 0): the head object of itk_run
+struct Itk32Head {
+    int n_rows, V, D;
+    float alpha;
+    const float* X; long ldx;
+    const float* W; long ldw;
+    float* wsamp;                   // [pl.M, D]: the gathered sample rows
+
+    int sample(hipStream_t st, const Plan& pl, float* S) const {
+        const long md = (long)pl.M * D;
+        hipLaunchKernelGGL(itk_sample_rows_kernel, dim3((unsigned)((md + 255) / 256)), dim3(256), 0, st, W, ldw, pl.stride, wsamp,
+                           pl.M, D);
+        T4R_LAUNCH_CHECK();
+        return t4r_gemm_fp32_nt_launch(st, n_rows, pl.M, D, alpha, X, ldx, wsamp, D, S, pl.ldS);
+    }
+    int collect(hipStream_t st, const float* thr, long thr_ld, int* count, float* cand_val, int* cand_idx, int cap) const {
+        return t4r_gemm_topk_collect_launch(st, n_rows, V, D, alpha, X, ldx, W, ldw, thr, thr_ld, count, cand_val, cand_idx, cap);
+    }
+    int scores(hipStream_t st, int r0, int n, float* C, long ldv) const {
+        return t4r_gemm_fp32_nt_launch(st, n, V, D, alpha, X + (long)r0 * ldx, ldx, W, ldw, C, ldv);
+    }
+};
+
 }  // namespace
 
-// step 3 for the callers outside this file (item_topk_h16.hip): same kernel, same flags
+// step 3 for itk_run (item_topk_plan.h): one select kernel, one set of flags for both heads
 int t4r_itk_select_launch(hipStream_t st, int n_rows, const float* cand_val, const int* cand_idx, const int* count, int cap, int k,
                           float* out_val, long* out_idx, int* n_flagged, int* flagged) {
     hipLaunchKernelGGL(itk_select_kernel, dim3(n_rows), dim3(256), 0, st, cand_val, cand_idx, count, cap, k, out_val, out_idx,
@@ -133,77 +155,6 @@ extern "C" int t4r_item_topk_f32(void* stream, int n_rows, int V, int D, float a
     const Plan pl = make_plan(n_rows, V, k, (size_t)D * 4, 0);
     T4R_CHECK_ARG(workspace && ws_bytes >= (long)pl.total && (uintptr_t)workspace % 16 == 0,
                   "item_topk: workspace too small (t4r_item_topk_ws_bytes) or not 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    float* wsamp = (float*)(ws + pl.off_wsamp);
-    float* S = (float*)(ws + pl.off_S);
-    float* tv = (float*)(ws + pl.off_tv);
-    long* ti = (long*)(ws + pl.off_ti);
-    int* count = (int*)(ws + pl.off_cnt);
-    int* n_flagged = count + n_rows;
-    int* flagged = n_flagged + 1;
-    float* cand_val = (float*)(ws + pl.off_cand);
-    int* cand_idx = (int*)(cand_val + (size_t)n_rows * pl.cap);
-
-    if (hipMemsetAsync(count, 0, sizeof(int) * ((size_t)n_rows + 1), st) != hipSuccess) {
-        t4r_set_error("item_topk: memset failed");
-        return -1;
-    }
-    // 1. threshold
-    const long md = (long)pl.M * D;
-    hipLaunchKernelGGL(itk_sample_rows_kernel, dim3((unsigned)((md + 255) / 256)), dim3(256), 0, st, W, ldw, pl.stride, wsamp,
-                       pl.M, D);
-    T4R_LAUNCH_CHECK();
-    int rc = t4r_gemm_fp32_nt_launch(st, n_rows, pl.M, D, alpha, X, ldx, wsamp, D, S, pl.ldS);
-    if (rc) return rc;
-    rc = t4r_topk(stream, S, n_rows, pl.M, pl.ldS, k, tv, ti);
-    if (rc) return rc;
-    // 2. collect
-    rc = t4r_gemm_topk_collect_launch(st, n_rows, V, D, alpha, X, ldx, W, ldw, tv + (k - 1), k, count, cand_val, cand_idx,
-                                      pl.cap);
-    if (rc) return rc;
-    // 3. select
-    rc = t4r_itk_select_launch(st, n_rows, cand_val, cand_idx, count, pl.cap, k, out_val, out_idx, n_flagged, flagged);
-    if (rc) return rc;
-    // 4. overflow: the one device-to-host read of the call
-    int nf = 0;
-    if (hipMemcpyAsync(&nf, n_flagged, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) {
-        t4r_set_error("item_topk: reading the overflow count failed");
-        return -1;
-    }
-    if (host_stats) { host_stats[1] = pl.M; host_stats[2] = pl.cap; }
-    if (host_stats && host_stats[7]) {
-        std::vector<int> hc(n_rows);
-        if (hipMemcpy(hc.data(), count, sizeof(int) * (size_t)n_rows, hipMemcpyDeviceToHost) != hipSuccess) {
-            t4r_set_error("item_topk: reading the candidate counts failed");
-            return -1;
-        }
-        long sum = 0, mx = 0;
-        for (int c : hc) { sum += c; mx = std::max(mx, (long)c); }
-        host_stats[3] = sum; host_stats[4] = mx;
-    }
-    if (nf > 0) {
-        std::vector<int> rows(nf);
-        if (hipMemcpy(rows.data(), flagged, sizeof(int) * (size_t)nf, hipMemcpyDeviceToHost) != hipSuccess) {
-            t4r_set_error("item_topk: reading the overflow rows failed");
-            return -1;
-        }
-        std::sort(rows.begin(), rows.end());          // arrival order of the flags is arbitrary; runs of consecutive rows share a launch
-        const long ldv = ((long)V + 63) / 64 * 64;
-        const long fit = std::max(1L, (long)((pl.total - pl.off_cand) / ((size_t)ldv * 4)));
-        float* scores = cand_val;                     // the lists are dead: the select kernel has finished
-        for (size_t a = 0; a < rows.size();) {
-            size_t b = a + 1;
-            while (b < rows.size() && rows[b] == rows[b - 1] + 1 && (long)(b - a) < fit) ++b;
-            const int r0 = rows[a], n = (int)(b - a);
-            rc = t4r_gemm_fp32_nt_launch(st, n, V, D, alpha, X + (long)r0 * ldx, ldx, W, ldw, scores, ldv);
-            if (rc) return rc;
-            rc = t4r_topk(stream, scores, n, V, ldv, k, out_val + (long)r0 * k, out_idx + (long)r0 * k);
-            if (rc) return rc;
-            a = b;
-        }
-    }
-    if (host_stats) host_stats[0] = nf;
-    return 0;
+    Itk32Head head = {n_rows, V, D, alpha, X, ldx, W, ldw, (float*)((char*)workspace + pl.off_wsamp)};
+    return itk_run("item_topk", (hipStream_t)stream, pl, workspace, n_rows, V, k, out_val, out_idx, host_stats, head);
 }

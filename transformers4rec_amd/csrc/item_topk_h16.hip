@@ -21,13 +21,16 @@
 //                             (two v_mfma_f32_32x32x16_f16 / _bf16 accumulators), its A fragments come straight from x16 (L2 / L1:
 //                             x16 is the operand that is re-read), its B fragments from the LDS image.  Every image row is loaded by
 //                             exactly one workgroup, once: the image comes from HBM once per launch.
-//                             EPI 0 stores alpha * acc to C (fp32); EPI 1 is the top-k COLLECT epilogue of gemm_kernel.h (FEAT bit 3):
-//                             compare with the row's threshold, one ballot per 32-lane half (a half holds 32 consecutive items of
-//                             one row), one returning slot atomic by the half's first lane, hits stored at base + prefix.
+//                             EPI 0 stores alpha * acc to C (fp32); EPI 1 is the top-k COLLECT epilogue of gemm_kernel.h (FEAT bit 3),
+//                             the same function (itk_collect, item_topk_collect.h): compare with the row's threshold, one ballot
+//                             per 32-lane half (a half holds 32 consecutive items of one row), one returning slot atomic by the
+//                             half's first lane, hits stored at base + prefix.
 //                             `stride` > 1 scores the strided sample of step 1 in place (item i of the launch is image row
 //                             i * stride): no gathered copy of the sample.
-//                             The tile load and the k loop live in item_h16_tile.h, shared with item_eval_h16.hip.
-//   select / threshold top-k  itk_select_kernel (item_topk.hip) and t4r_topk, unchanged; the plan is item_topk_plan.h's.
+//                             The tile load and the k loop live in item_h16_tile.h, shared with item_eval_h16.hip, as do the
+//                             image's argument contract and the dtype dispatch.
+//   select / threshold top-k  itk_select_kernel (item_topk.hip) and t4r_topk, unchanged; the plan and the four-step driver
+//                             (itk_run) are item_topk_plan.h's, shared with item_topk.hip: this file's part is Itk16Head.
 //
 // Bits.  One element is computed by ONE instruction sequence whatever launch, tile or row block it sits in: k runs 0, 16, 32, ...
 // to ldp in every launch, each step one MFMA into the same accumulator, then one multiplication by alpha.  The sampled thresholds,
@@ -42,10 +45,8 @@
 // accumulation bound at every element, against 5.0e-4 to a reference with those entries flushed.  The contract tests still allow
 // either behaviour for entries below 2^-14.
 #include "item_h16_tile.h"
+#include "item_topk_collect.h"
 #include "item_topk_plan.h"
-#include <vector>
-
-extern "C" int t4r_topk(void* stream, const float* scores, int N, int V, long ld, int k, float* out_val, long* out_idx);
 
 namespace {
 
@@ -108,7 +109,7 @@ __global__ __launch_bounds__(256) void itk16_kernel(Itk16Params p) {
         if (EPI == 1) {
 #pragma unroll
             for (int e = 0; e < 16; ++e)
-                thr[e] = p.thr[(long)min(rb + (e & 3) + 8 * (e >> 2) + 4 * h, p.n_rows - 1) * p.thr_ld];
+                thr[e] = p.thr[(long)min(rb + itk16_acc_row(e, h), p.n_rows - 1) * p.thr_ld];
         }
         f32x16 acc[2];
         itk16_product<DT>(ap, b0p, b1p, nk, acc);
@@ -117,24 +118,13 @@ __global__ __launch_bounds__(256) void itk16_kernel(Itk16Params p) {
             const long col = item0 + j * 32 + r;
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int row = rb + (e & 3) + 8 * (e >> 2) + 4 * h;
+                const int row = rb + itk16_acc_row(e, h);
                 const float v = alpha * acc[j][e];
                 if (EPI == 0) {
                     if (col < p.n_items && row < p.n_rows) p.C[(long)row * p.ldc + col] = v;
                 } else {
-                    const float t = thr[e];
-                    const bool hit = col < p.n_items && row < p.n_rows && v >= t;
-                    const unsigned long long m = __ballot(hit);
-                    if (m == 0) continue;                       // wave-uniform
-                    const unsigned mh = (unsigned)(h ? (m >> 32) : (m & 0xffffffffull));
-                    int base = 0;
-                    if (r == 0 && mh) base = atomicAdd(p.count + row, __popc(mh));
-                    base = __shfl(base, lane & 32, 64);
-                    const int slot = base + __popc(mh & ((1u << r) - 1u));
-                    if (hit && slot < p.cap) {
-                        p.cand_val[(long)row * p.cap + slot] = v;
-                        p.cand_idx[(long)row * p.cap + slot] = (int)col;
-                    }
+                    itk_collect(col < p.n_items && row < p.n_rows && v >= thr[e], v, (int)col, row, lane, p.count, p.cand_val,
+                                p.cand_idx, p.cap);
                 }
             }
         }
@@ -145,7 +135,7 @@ T4rLdsAttr g_lds_attr[2][2];
 
 template <int DT, int EPI>
 int launch_t(hipStream_t st, const Itk16Params& p) {
-    const size_t smem = (size_t)ITK16_TILE * ((size_t)(p.ldp >> 3) + 1) * 16;
+    const size_t smem = itk16_lds_bytes(p.ldp);
     const void* fn = (const void*)itk16_kernel<DT, EPI>;
     t4r_ensure_dynamic_lds(fn, smem, g_lds_attr[DT - 2][EPI]);
     const unsigned grid = (unsigned)(((long)p.n_items + ITK16_TILE - 1) / ITK16_TILE);
@@ -155,46 +145,59 @@ int launch_t(hipStream_t st, const Itk16Params& p) {
 }
 
 int launch(hipStream_t st, int dtype, int epi, const Itk16Params& p) {
-    if (dtype == 3) return epi ? launch_t<3, 1>(st, p) : launch_t<3, 0>(st, p);
-    return epi ? launch_t<2, 1>(st, p) : launch_t<2, 0>(st, p);
+    return itk16_dispatch(dtype, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        return epi ? launch_t<DT, 1>(st, p) : launch_t<DT, 0>(st, p);
+    });
 }
 
-int round_rows(hipStream_t st, int dtype, const float* src, long ld, long rows, int D, uint16_t* dst, long ldp) {
+// the image on the 16-bit matrix cores: the head object of itk_run.  p holds what every launch of the call shares.
+struct Itk16Head {
+    int dtype;
+    Itk16Params p;                  // n_rows, ldp, x16, img, ldi, alpha
+
+    int sample(hipStream_t st, const Plan& pl, float* S) const {       // in place: item i of the launch is image row i * stride
+        Itk16Params q = p;
+        q.n_items = pl.M; q.stride = pl.stride; q.C = S; q.ldc = pl.ldS;
+        return launch(st, dtype, 0, q);
+    }
+    int collect(hipStream_t st, const float* thr, long thr_ld, int* count, float* cand_val, int* cand_idx, int cap) const {
+        Itk16Params q = p;
+        q.thr = thr; q.thr_ld = thr_ld; q.count = count; q.cand_val = cand_val; q.cand_idx = cand_idx; q.cap = cap;
+        return launch(st, dtype, 1, q);
+    }
+    int scores(hipStream_t st, int r0, int n, float* C, long ldv) const {
+        Itk16Params q = p;
+        q.n_rows = n; q.x16 = p.x16 + (long)r0 * p.ldp; q.C = C; q.ldc = ldv;
+        return launch(st, dtype, 0, q);
+    }
+};
+
+}  // namespace
+
+int t4r_itk16_round_rows(hipStream_t st, int dtype, const float* src, long ld, long rows, int D, uint16_t* dst, long ldp) {
     const int chunks = (int)(ldp / 8);
     const int vec = ((uintptr_t)src % 16 == 0 && ld % 4 == 0) ? 1 : 0;
     const long n = rows * chunks;
     const dim3 grid((unsigned)((n + 255) / 256));
-    if (dtype == 3) hipLaunchKernelGGL(itk16_round_rows_kernel<3>, grid, dim3(256), 0, st, src, ld, rows, D, dst, ldp, chunks, vec);
-    else hipLaunchKernelGGL(itk16_round_rows_kernel<2>, grid, dim3(256), 0, st, src, ld, rows, D, dst, ldp, chunks, vec);
-    T4R_LAUNCH_CHECK();
-    return 0;
+    return itk16_dispatch(dtype, [&](auto dt) {
+        hipLaunchKernelGGL(itk16_round_rows_kernel<decltype(dt)::value>, grid, dim3(256), 0, st, src, ld, rows, D, dst, ldp, chunks,
+                           vec);
+        T4R_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
-long image_ld(long D) { return (D + 15) / 16 * 16; }
+extern "C" int t4r_item_table_image_ld(int D) { return D > 0 ? (int)itk16_image_ld(D) : 0; }
 
-}  // namespace
-
-// for item_eval_h16.hip (item_h16_tile.h): the same pitch and the same rounding of x as every entry of this file
-long t4r_itk16_image_ld(long D) { return image_ld(D); }
-int t4r_itk16_round_rows(hipStream_t st, int dtype, const float* src, long ld, long rows, int D, uint16_t* dst, long ldp) {
-    return round_rows(st, dtype, src, ld, rows, D, dst, ldp);
-}
-
-extern "C" int t4r_item_table_image_ld(int D) { return D > 0 ? (int)image_ld(D) : 0; }
-
-extern "C" int t4r_item_topk_h16_supported(int D) { return D >= 1 && D <= ITK16_MAX_D ? 1 : 0; }
-
-#define ITK16_CHECK_IMAGE(name)                                                                                                     \
-    T4R_CHECK_ARG(dtype == 2 || dtype == 3, name ": dtype is 2 (bf16) or 3 (fp16), the codes of T4R_GEMM_PREC");                    \
-    T4R_CHECK_ARG(ldp >= image_ld(D) && ldp % 8 == 0 && (uintptr_t)image % 16 == 0,                                                 \
-                  name ": image rows must be 16-byte aligned with pitch >= t4r_item_table_image_ld(D)")
+extern "C" int t4r_item_topk_h16_supported(int D) { return itk16_supported(D) ? 1 : 0; }
 
 extern "C" int t4r_item_table_pack_h16(void* stream, const float* W, long ldw, int V, int D, int dtype, void* image, long ldp) {
     if (V == 0) return 0;
     T4R_CHECK_ARG(V > 0 && D > 0 && W && image && ldw >= D, "item_table_pack_h16: bad arguments");
     ITK16_CHECK_IMAGE("item_table_pack_h16");
     // a wider pitch is zero-filled to its end
-    return round_rows((hipStream_t)stream, dtype, W, ldw, V, D, (uint16_t*)image, ldp) ? -1 : 0;
+    return t4r_itk16_round_rows((hipStream_t)stream, dtype, W, ldw, V, D, (uint16_t*)image, ldp) ? -1 : 0;
 }
 
 // workspace: n_rows * t4r_item_table_image_ld(D) * 2 bytes (the 16-bit image of x), 16-byte aligned
@@ -202,15 +205,15 @@ extern "C" int t4r_item_scores_h16(void* stream, int n_rows, int V, int D, float
                                    const void* image, long ldp, int dtype, float* C, long ldc, void* workspace, long ws_bytes) {
     if (n_rows == 0 || V == 0) return 0;
     T4R_CHECK_ARG(n_rows > 0 && V > 0 && D > 0 && X && image && C, "item_scores_h16: bad arguments");
-    T4R_CHECK_ARG(t4r_item_topk_h16_supported(D), "item_scores_h16: 1 <= D <= 512 (t4r_item_topk_h16_supported)");
+    T4R_CHECK_ARG(itk16_supported(D), "item_scores_h16: 1 <= D <= 512 (t4r_item_topk_h16_supported)");
     T4R_CHECK_ARG(ldx >= D && ldc >= V, "item_scores_h16: row pitch below the row length");
     ITK16_CHECK_IMAGE("item_scores_h16");
-    const long kp = image_ld(D);
+    const long kp = itk16_image_ld(D);
     T4R_CHECK_ARG(workspace && ws_bytes >= (long)n_rows * kp * 2 && (uintptr_t)workspace % 16 == 0,
                   "item_scores_h16: workspace below n_rows * t4r_item_table_image_ld(D) * 2 bytes or not 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     uint16_t* x16 = (uint16_t*)workspace;
-    int rc = round_rows(st, dtype, X, ldx, n_rows, D, x16, kp);
+    int rc = t4r_itk16_round_rows(st, dtype, X, ldx, n_rows, D, x16, kp);
     if (rc) return rc;
     Itk16Params p = {};
     p.n_rows = n_rows; p.n_items = V; p.ldp = (int)kp; p.x16 = x16; p.img = (const uint16_t*)image; p.ldi = ldp; p.stride = 1;
@@ -220,7 +223,7 @@ extern "C" int t4r_item_scores_h16(void* stream, int n_rows, int V, int D, float
 
 extern "C" long t4r_item_topk_h16_ws_bytes(int n_rows, int V, int D, int k) {
     if (n_rows <= 0 || V <= 0 || D <= 0 || k < 1) return 0;
-    return (long)make_plan(n_rows, V, k, 0, (size_t)n_rows * image_ld(D) * 2).total;
+    return (long)make_plan(n_rows, V, k, 0, (size_t)n_rows * itk16_image_ld(D) * 2).total;
 }
 
 // host_stats: as t4r_item_topk_f32
@@ -229,90 +232,21 @@ extern "C" int t4r_item_topk_h16(void* stream, int n_rows, int V, int D, float a
                                  long* host_stats) {
     if (n_rows == 0) return 0;
     T4R_CHECK_ARG(n_rows > 0 && V > 0 && D > 0 && X && image && out_val && out_idx, "item_topk_h16: bad arguments");
-    T4R_CHECK_ARG(t4r_item_topk_h16_supported(D), "item_topk_h16: 1 <= D <= 512 (t4r_item_topk_h16_supported)");
+    T4R_CHECK_ARG(itk16_supported(D), "item_topk_h16: 1 <= D <= 512 (t4r_item_topk_h16_supported)");
     T4R_CHECK_ARG(k >= 1 && k <= ITK_MAX_K && k <= V, "item_topk_h16: 1 <= k <= min(256, V)");
     T4R_CHECK_ARG(ldx >= D, "item_topk_h16: row pitch below D");
     ITK16_CHECK_IMAGE("item_topk_h16");
-    const long kp = image_ld(D);
+    const long kp = itk16_image_ld(D);
     const Plan pl = make_plan(n_rows, V, k, 0, (size_t)n_rows * kp * 2);
     T4R_CHECK_ARG(workspace && ws_bytes >= (long)pl.total && (uintptr_t)workspace % 16 == 0,
                   "item_topk_h16: workspace too small (t4r_item_topk_h16_ws_bytes) or not 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    float* S = (float*)(ws + pl.off_S);
-    float* tv = (float*)(ws + pl.off_tv);
-    long* ti = (long*)(ws + pl.off_ti);
-    int* count = (int*)(ws + pl.off_cnt);
-    int* n_flagged = count + n_rows;
-    int* flagged = n_flagged + 1;
-    float* cand_val = (float*)(ws + pl.off_cand);
-    int* cand_idx = (int*)(cand_val + (size_t)n_rows * pl.cap);
-    uint16_t* x16 = (uint16_t*)(ws + pl.off_x);
-
-    if (hipMemsetAsync(count, 0, sizeof(int) * ((size_t)n_rows + 1), st) != hipSuccess) {
-        t4r_set_error("item_topk_h16: memset failed");
-        return -1;
-    }
-    int rc = round_rows(st, dtype, X, ldx, n_rows, D, x16, kp);
+    uint16_t* x16 = (uint16_t*)((char*)workspace + pl.off_x);
+    int rc = t4r_itk16_round_rows(st, dtype, X, ldx, n_rows, D, x16, kp);
     if (rc) return rc;
-    Itk16Params p = {};
-    p.n_rows = n_rows; p.ldp = (int)kp; p.x16 = x16; p.img = (const uint16_t*)image; p.ldi = ldp; p.alpha = alpha;
-    // 1. threshold: the strided sample scored in place
-    p.n_items = pl.M; p.stride = pl.stride; p.C = S; p.ldc = pl.ldS;
-    rc = launch(st, dtype, 0, p);
-    if (rc) return rc;
-    rc = t4r_topk(stream, S, n_rows, pl.M, pl.ldS, k, tv, ti);
-    if (rc) return rc;
-    // 2. collect
-    p.n_items = V; p.stride = 1; p.C = nullptr; p.ldc = 0;
-    p.thr = tv + (k - 1); p.thr_ld = k; p.count = count; p.cand_val = cand_val; p.cand_idx = cand_idx; p.cap = pl.cap;
-    rc = launch(st, dtype, 1, p);
-    if (rc) return rc;
-    // 3. select
-    rc = t4r_itk_select_launch(st, n_rows, cand_val, cand_idx, count, pl.cap, k, out_val, out_idx, n_flagged, flagged);
-    if (rc) return rc;
-    // 4. overflow: the one device-to-host read of the call
-    int nf = 0;
-    if (hipMemcpyAsync(&nf, n_flagged, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) {
-        t4r_set_error("item_topk_h16: reading the overflow count failed");
-        return -1;
-    }
-    if (host_stats) { host_stats[1] = pl.M; host_stats[2] = pl.cap; }
-    if (host_stats && host_stats[7]) {
-        std::vector<int> hc(n_rows);
-        if (hipMemcpy(hc.data(), count, sizeof(int) * (size_t)n_rows, hipMemcpyDeviceToHost) != hipSuccess) {
-            t4r_set_error("item_topk_h16: reading the candidate counts failed");
-            return -1;
-        }
-        long sum = 0, mx = 0;
-        for (int c : hc) { sum += c; mx = std::max(mx, (long)c); }
-        host_stats[3] = sum; host_stats[4] = mx;
-    }
-    if (nf > 0) {
-        std::vector<int> rows(nf);
-        if (hipMemcpy(rows.data(), flagged, sizeof(int) * (size_t)nf, hipMemcpyDeviceToHost) != hipSuccess) {
-            t4r_set_error("item_topk_h16: reading the overflow rows failed");
-            return -1;
-        }
-        std::sort(rows.begin(), rows.end());
-        const long ldv = ((long)V + 63) / 64 * 64;
-        const long fit = std::max(1L, (long)((pl.off_x - pl.off_cand) / ((size_t)ldv * 4)));
-        float* scores = cand_val;                     // the lists are dead: the select kernel has finished
-        for (size_t a = 0; a < rows.size();) {
-            size_t b = a + 1;
-            while (b < rows.size() && rows[b] == rows[b - 1] + 1 && (long)(b - a) < fit) ++b;
-            const int r0 = rows[a], n = (int)(b - a);
-            Itk16Params q = {};
-            q.n_rows = n; q.n_items = V; q.ldp = (int)kp; q.x16 = x16 + (long)r0 * kp; q.img = (const uint16_t*)image; q.ldi = ldp;
-            q.stride = 1; q.alpha = alpha; q.C = scores; q.ldc = ldv;
-            rc = launch(st, dtype, 0, q);
-            if (rc) return rc;
-            rc = t4r_topk(stream, scores, n, V, ldv, k, out_val + (long)r0 * k, out_idx + (long)r0 * k);
-            if (rc) return rc;
-            a = b;
-        }
-    }
-    if (host_stats) host_stats[0] = nf;
-    return 0;
+    Itk16Head head = {dtype, {}};
+    Itk16Params& p = head.p;
+    p.n_rows = n_rows; p.n_items = V; p.ldp = (int)kp; p.x16 = x16; p.img = (const uint16_t*)image; p.ldi = ldp; p.stride = 1;
+    p.alpha = alpha;
+    return itk_run("item_topk_h16", st, pl, workspace, n_rows, V, k, out_val, out_idx, host_stats, head);
 }

@@ -1,9 +1,12 @@
-// Workspace plan and the select step shared by the two fused top-k inference heads (item_topk.hip: fp32 table on the fp32
-// matrix cores; item_topk_h16.hip: fp16 / bf16 serving image).
+// Workspace plan and host driver shared by the two fused top-k inference heads (item_topk.hip: fp32 table on the fp32 matrix
+// cores; item_topk_h16.hip: fp16 / bf16 serving image).  The four steps of a call (item_topk.hip's header) and the host_stats
+// bookkeeping are itk_run, once; a head only says how a block of scores is computed and how the collect pass runs.
 #pragma once
 #include "t4r_common.h"
 #include <algorithm>
 #include <math.h>
+#include <string>
+#include <vector>
 
 #define ITK_MAX_K 256
 #define ITK_LDS_CAP 2048       // candidates >= t1 held in LDS by the select kernel (t4r_topk's own list size)
@@ -55,3 +58,81 @@ static inline Plan make_plan(long n_rows, long V, int k, size_t samp_row_bytes, 
 // step 3 (item_topk.hip): one workgroup per row ranks the row's candidate list, flags the rows that overflowed
 int t4r_itk_select_launch(hipStream_t st, int n_rows, const float* cand_val, const int* cand_idx, const int* count, int cap, int k,
                           float* out_val, long* out_idx, int* n_flagged, int* flagged);
+
+extern "C" int t4r_topk(void* stream, const float* scores, int N, int V, long ld, int k, float* out_val, long* out_idx);
+
+// Steps 1-4 of one call over the workspace `ws` laid out by `pl`.  The head has three operations, each returning 0 or an error
+// code with the message set:
+//   head.sample(st, pl, S)                           alpha * scores of the strided sample (items 0, s, 2 s, ...: pl.M of them at
+//                                                    s = pl.stride) of every row into S [n_rows, pl.ldS]
+//   head.collect(st, thr, thr_ld, count, cand_val, cand_idx, cap)
+//                                                    one pass over the table: (score, item) of every score >= thr[row * thr_ld]
+//                                                    appended to the row's list (count zeroed here)
+//   head.scores(st, r0, n, C, ldv)                   all V scores of rows [r0, r0 + n) into C (row pitch ldv)
+// All three must give one (row, item) the same bits.  `name` is the calling entry's: the prefix of the messages of failures in
+// here.  host_stats: see t4r_item_topk_f32.
+template <class Head>
+static int itk_run(const char* name, hipStream_t st, const Plan& pl, void* workspace, int n_rows, int V, int k, float* out_val,
+                   long* out_idx, long* host_stats, Head& head) {
+    auto fail = [&](const char* what) {
+        t4r_set_error((std::string(name) + ": " + what).c_str());
+        return -1;
+    };
+    char* ws = (char*)workspace;
+    float* S = (float*)(ws + pl.off_S);
+    float* tv = (float*)(ws + pl.off_tv);
+    long* ti = (long*)(ws + pl.off_ti);
+    int* count = (int*)(ws + pl.off_cnt);
+    int* n_flagged = count + n_rows;
+    int* flagged = n_flagged + 1;
+    float* cand_val = (float*)(ws + pl.off_cand);
+    int* cand_idx = (int*)(cand_val + (size_t)n_rows * pl.cap);
+
+    if (hipMemsetAsync(count, 0, sizeof(int) * ((size_t)n_rows + 1), st) != hipSuccess) return fail("memset failed");
+    // 1. threshold
+    int rc = head.sample(st, pl, S);
+    if (rc) return rc;
+    rc = t4r_topk(st, S, n_rows, pl.M, pl.ldS, k, tv, ti);
+    if (rc) return rc;
+    // 2. collect
+    rc = head.collect(st, tv + (k - 1), k, count, cand_val, cand_idx, pl.cap);
+    if (rc) return rc;
+    // 3. select
+    rc = t4r_itk_select_launch(st, n_rows, cand_val, cand_idx, count, pl.cap, k, out_val, out_idx, n_flagged, flagged);
+    if (rc) return rc;
+    // 4. overflow: the one device-to-host read of the call
+    int nf = 0;
+    if (hipMemcpyAsync(&nf, n_flagged, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return fail("reading the overflow count failed");
+    if (host_stats) { host_stats[1] = pl.M; host_stats[2] = pl.cap; }
+    if (host_stats && host_stats[7]) {
+        std::vector<int> hc(n_rows);
+        if (hipMemcpy(hc.data(), count, sizeof(int) * (size_t)n_rows, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail("reading the candidate counts failed");
+        long sum = 0, mx = 0;
+        for (int c : hc) { sum += c; mx = std::max(mx, (long)c); }
+        host_stats[3] = sum; host_stats[4] = mx;
+    }
+    if (nf > 0) {
+        std::vector<int> rows(nf);
+        if (hipMemcpy(rows.data(), flagged, sizeof(int) * (size_t)nf, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail("reading the overflow rows failed");
+        std::sort(rows.begin(), rows.end());          // arrival order of the flags is arbitrary; runs of consecutive rows share a launch
+        const long ldv = ((long)V + 63) / 64 * 64;
+        const long fit = std::max(1L, (long)((pl.off_x - pl.off_cand) / ((size_t)ldv * 4)));
+        float* scores = cand_val;                     // the lists are dead: the select kernel has finished
+        for (size_t a = 0; a < rows.size();) {
+            size_t b = a + 1;
+            while (b < rows.size() && rows[b] == rows[b - 1] + 1 && (long)(b - a) < fit) ++b;
+            const int r0 = rows[a], n = (int)(b - a);
+            rc = head.scores(st, r0, n, scores, ldv);
+            if (rc) return rc;
+            rc = t4r_topk(st, scores, n, V, ldv, k, out_val + (long)r0 * k, out_idx + (long)r0 * k);
+            if (rc) return rc;
+            a = b;
+        }
+    }
+    if (host_stats) host_stats[0] = nf;
+    return 0;
+}

@@ -50,6 +50,11 @@ def pad_ld(V):
     return (V + _LD_ALIGN - 1) // _LD_ALIGN * _LD_ALIGN
 
 
+def _row_pitch(t, single):
+    """row pitch (elements) of the 2-D tensor t for the C ABI; a one-row tensor's stride(0) is arbitrary: `single` stands in"""
+    return t.stride(0) if t.shape[0] > 1 else single
+
+
 # ------------------------------------------------------------------------------------ GEMM
 PRECISIONS = {"fp32": 0, "fp32_bf16x3": 1, "bf16": 2, "fp16": 3, "auto": 4}
 
@@ -1090,7 +1095,7 @@ def scatter_rows_sorted(d_table, ids, rows, padding_idx=-1):
 def topk(scores, k, V=None):
     N = scores.shape[0]
     V = scores.shape[1] if V is None else V
-    ld = scores.stride(0) if N > 1 else scores.shape[1]
+    ld = _row_pitch(scores, scores.shape[1])
     vals = torch.empty((N, k), device=scores.device, dtype=torch.float32)
     idx = torch.empty((N, k), device=scores.device, dtype=torch.int64)
     call("t4r_topk", _stream(), scores.data_ptr(), N, V, ld, k, vals.data_ptr(), idx.data_ptr())
@@ -1131,7 +1136,7 @@ def pack_item_table(W, dtype="fp16"):
     td = _H16_NAMES[dtype]
     ldp = image_ld(D)
     buf = torch.empty((V, ldp), device=W.device, dtype=td)
-    call("t4r_item_table_pack_h16", _stream(), W.data_ptr(), W.stride(0) if V > 1 else D, V, D, _H16[td], buf.data_ptr(), ldp)
+    call("t4r_item_table_pack_h16", _stream(), W.data_ptr(), _row_pitch(W, D), V, D, _H16[td], buf.data_ptr(), ldp)
     if not bool(torch.isfinite(buf).all()):         # once per table: the image is reused by every call
         raise ValueError(f"pack_item_table: the table does not round to finite {dtype} values")
     return buf[:, :D]
@@ -1140,8 +1145,7 @@ def pack_item_table(W, dtype="fp16"):
 def _check_image(what, W, D):
     if W.shape[1] != D:
         raise ValueError(f"{what}: inner dims differ ({D} vs {W.shape[1]})")
-    V = W.shape[0]
-    ldp = W.stride(0) if V > 1 else image_ld(D)
+    ldp = _row_pitch(W, image_ld(D))
     if ldp < image_ld(D) or ldp % 8 or W.data_ptr() % 16:
         raise ValueError(f"{what}: a 16-bit table must be a serving image (ops.pack_item_table): rows 16-byte aligned, "
                          f"pitch >= image_ld(D) = {image_ld(D)} with zero pad columns")
@@ -1178,7 +1182,7 @@ def item_scores(x, W, alpha=1.0):
     out = torch.empty((N, ldc), device=x.device, dtype=torch.float32)
     if N and V:
         ws = torch.empty(N * image_ld(D) * 2, device=x.device, dtype=torch.uint8)
-        call("t4r_item_scores_h16", _stream(), N, V, D, float(alpha), x.data_ptr(), x.stride(0) if N > 1 else D, W.data_ptr(),
+        call("t4r_item_scores_h16", _stream(), N, V, D, float(alpha), x.data_ptr(), _row_pitch(x, D), W.data_ptr(),
              ldp, _H16[W.dtype], out.data_ptr(), ldc, ws.data_ptr(), ws.numel())
     return out[:, :V]
 
@@ -1198,7 +1202,7 @@ def item_topk(x, W, k, alpha=1.0):
     if not 1 <= k <= min(256, V):
         raise ValueError(f"item_topk: 1 <= k <= min(256, V) (k = {k}, V = {V})")
     h16 = W.dtype in _H16
-    ldw = _check_image("item_topk", W, D) if h16 else (W.stride(0) if V > 1 else D)
+    ldw = _check_image("item_topk", W, D) if h16 else _row_pitch(W, D)
     vals = torch.empty((N, k), device=x.device, dtype=torch.float32)
     idx = torch.empty((N, k), device=x.device, dtype=torch.int64)
     if N == 0:
@@ -1209,7 +1213,7 @@ def item_topk(x, W, k, alpha=1.0):
     while rows > 1 and ws_bytes(rows, V, D, k) > _ITEM_TOPK_WS_LIMIT:
         rows = (rows + 1) // 2
     ws = torch.empty(ws_bytes(rows, V, D, k), device=x.device, dtype=torch.uint8)
-    ldx = x.stride(0) if N > 1 else D
+    ldx = _row_pitch(x, D)
     st = (ctypes.c_long * 8)()
     tot = dict(fallback_rows=0, cand_sum=0, cand_max=0)
     for s0 in range(0, N, rows):
@@ -1259,7 +1263,7 @@ def item_eval(x, image, labels, alpha=1.0):
     rank = torch.empty(N, device=x.device, dtype=torch.int32)
     if N:
         ws = torch.empty(_lib.load().t4r_item_eval_h16_ws_bytes(N, V, D), device=x.device, dtype=torch.uint8)
-        call("t4r_item_eval_h16", _stream(), N, V, D, float(alpha), x.data_ptr(), x.stride(0) if N > 1 else D, image.data_ptr(),
+        call("t4r_item_eval_h16", _stream(), N, V, D, float(alpha), x.data_ptr(), _row_pitch(x, D), image.data_ptr(),
              ldp, _H16[image.dtype], labels.data_ptr(), lse.data_ptr(), target.data_ptr(), score_sum.data_ptr(), rank.data_ptr(),
              ws.data_ptr(), ws.numel())
     return lse, target, score_sum, rank

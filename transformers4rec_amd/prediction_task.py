@@ -7,6 +7,7 @@ state_dict names.  Arithmetic: csrc/masking.hip (row compaction), 
 (X @ W^T and its two backward contractions), head.hip (softmax-CE, sampled logits, top-k).
 """
 import math
+import types
 from typing import Optional
 
 import os
@@ -111,6 +112,12 @@ _SAMPLED_ROWS = _exp_env("T4R_SAMPLED_ROWS", "1") == "1"
 
 _HEAD_SPLIT = _exp_env("T4R_HEAD_SPLIT", "1") != "0"
 _HEAD_RECOMPUTE = _exp_env("T4R_HEAD_RECOMPUTE", "1") != "0"
+
+# the functions behind the registered inference / evaluation operators, under the operators' argument order (torch_ops.py)
+_EAGER_HEAD_OPS = types.SimpleNamespace(
+    item_scores=ops.item_scores, item_eval=ops.item_eval,
+    item_topk=lambda x, W, alpha, k: ops.item_topk(x, W, k, alpha),
+    topk=lambda scores, k: ops.topk(scores, k, scores.shape[1]))
 
 
 def _head_split_ok(xp, W, N, V):
@@ -556,32 +563,26 @@ class NextItemPredictionTask(nn.Module):
         W = mod.output_weights.detach()
         T = float(mod.softmax_temperature) if mod.softmax_temperature else 1.0
         V = W.shape[0]
+        head = self._head_ops()
         image = self._serving_weights()
         if image is not None:
             # served from the half-precision image: fused head for top-k, [B, V] fp32 scores otherwise; topk_mode plays no part
-            if not torch.is_grad_enabled():
-                from . import torch_ops  # noqa: F401
+            return head.item_scores(xr, image, 1.0 / T) if top_k is None else head.item_topk(xr, image, 1.0 / T, top_k)
+        if top_k is not None and self.resolve_topk_mode(B, V) == "fused":
+            return head.item_topk(xr, W, 1.0 / T, top_k)
+        scores = head.item_scores(xr, W, 1.0 / T)
+        return scores if top_k is None else head.topk(scores, top_k)
 
-                if top_k is not None:
-                    return torch.ops.t4r_hip.item_topk(xr, image, 1.0 / T, top_k)
-                return torch.ops.t4r_hip.item_scores(xr, image, 1.0 / T)
-            if top_k is not None:
-                return ops.item_topk(xr, image, top_k, alpha=1.0 / T)
-            return ops.item_scores(xr, image, alpha=1.0 / T)
-        fused_topk = top_k is not None and self.resolve_topk_mode(B, V) == "fused"
-        if not torch.is_grad_enabled():      # registered operators (torch_ops.py): dispatcher-visible inference head
+    @staticmethod
+    def _head_ops():
+        """item_scores(x, W, alpha), item_topk(x, W, alpha, k), topk(scores, k), item_eval(x, image, labels, alpha) of an
+        inference or evaluation call: the registered operators (torch_ops.py: dispatcher-visible) where no graph is recorded,
+        the functions of ops.py behind them otherwise"""
+        if not torch.is_grad_enabled():
             from . import torch_ops  # noqa: F401
 
-            if fused_topk:
-                return torch.ops.t4r_hip.item_topk(xr, W, 1.0 / T, top_k)
-            scores = torch.ops.t4r_hip.item_scores(xr, W, 1.0 / T)
-            return scores if top_k is None else torch.ops.t4r_hip.topk(scores, top_k)
-        if fused_topk:
-            return ops.item_topk(xr, W, top_k, alpha=1.0 / T)
-        scores = ops.gemm(xr, W, False, True, alpha=1.0 / T, ldc=ops.pad_ld(V))
-        if top_k is None:
-            return scores
-        return ops.topk(scores, top_k, V)
+            return torch.ops.t4r_hip
+        return _EAGER_HEAD_OPS
 
     # ------------------------------------------------------------------ ranking metrics (N1)
     def _rank_metrics(self, ranks):
@@ -619,12 +620,9 @@ class NextItemPredictionTask(nn.Module):
         """The task's ranking metrics from 0-based target ranks (one relevant item per row)."""
         return self._rank_metrics(ranks.to(torch.int64))
 
-    def evaluate_ranks(self, inputs):
-        """Fused evaluation head (SURVEY N1): the label rows of `inputs` [B, L, D] (the masking's
-        evaluation targets, e.g. the last item of every session) -> rank of the target item among
-        all V scores, computed tile by tile inside the logits GEMM; the [N, V] score matrix, the
-        top-k pass and the reference's [N, V] one-hot (ranking_metric.py:52-59) never exist.
-        Returns {"labels", "ranks", "metrics"}; metrics are also accumulated for compute_metrics()."""
+    def _evaluation_rows(self, inputs):
+        """(xr, labels, 1 / T) of an evaluation batch: the label rows of `inputs` [B, L, D] (the masking's evaluation targets)
+        through the task block, their labels, and the inverse softmax temperature"""
         x = (inputs[0] if isinstance(inputs, (tuple, list)) else inputs).float()
         mod = self.pre.module
         n, pos, lab = self.masking.compact_labels()
@@ -638,7 +636,16 @@ class NextItemPredictionTask(nn.Module):
             lin = self.task_block[0][0]
             xr = ops.gemm(xr, lin.weight.detach(), False, True, bias=lin.bias.detach(), epilogue=ops.EPI_BIAS)
         T = float(mod.softmax_temperature) if mod.softmax_temperature else 1.0
-        ranks = ops.rank_of_target(xr, mod.output_weights.detach(), labels, 1.0 / T)
+        return xr, labels, 1.0 / T
+
+    def evaluate_ranks(self, inputs):
+        """Fused evaluation head (SURVEY N1): the label rows of `inputs` [B, L, D] (the masking's
+        evaluation targets, e.g. the last item of every session) -> rank of the target item among
+        all V scores, computed tile by tile inside the logits GEMM; the [N, V] score matrix, the
+        top-k pass and the reference's [N, V] one-hot (ranking_metric.py:52-59) never exist.
+        Returns {"labels", "ranks", "metrics"}; metrics are also accumulated for compute_metrics()."""
+        xr, labels, inv_t = self._evaluation_rows(inputs)
+        ranks = ops.rank_of_target(xr, self.pre.module.output_weights.detach(), labels, inv_t)
         return {"labels": labels, "ranks": ranks, "metrics": self.metrics_from_ranks(ranks)}
 
     def evaluate_batch(self, inputs):
@@ -652,34 +659,17 @@ class NextItemPredictionTask(nn.Module):
         forward (ops.linear_softmax_ce_fwd) for the loss -- two passes over the fp32 table."""
         if self.pre is None:
             raise RuntimeError("evaluate_batch: the task is not built yet")
-        x = (inputs[0] if isinstance(inputs, (tuple, list)) else inputs).float()
-        mod = self.pre.module
-        n, pos, lab = self.masking.compact_labels()
-        N = self.masking.n_labels()
-        if N == 0:
-            raise ValueError("no label positions in this batch")
-        labels = lab[:N]
-        B, L, D = x.shape
-        xr = ops.gather_rows(x.detach().contiguous().view(B * L, D), pos, N)
-        if self.task_block is not None:
-            lin = self.task_block[0][0]
-            xr = ops.gemm(xr, lin.weight.detach(), False, True, bias=lin.bias.detach(), epilogue=ops.EPI_BIAS)
-        T = float(mod.softmax_temperature) if mod.softmax_temperature else 1.0
+        xr, labels, inv_t = self._evaluation_rows(inputs)
         smooth = float(getattr(self.loss, "label_smoothing", 0.0) or 0.0)
         image = self._serving_weights()
         if image is not None:
-            if not torch.is_grad_enabled():
-                from . import torch_ops  # noqa: F401
-
-                lse, target, score_sum, ranks = torch.ops.t4r_hip.item_eval(xr, image, labels, 1.0 / T)
-            else:
-                lse, target, score_sum, ranks = ops.item_eval(xr, image, labels, alpha=1.0 / T)
+            lse, target, score_sum, ranks = self._head_ops().item_eval(xr, image, labels, inv_t)
             loss_rows = (1.0 - smooth) * (lse - target) + smooth * (lse - score_sum / image.shape[0])
             loss = loss_rows.mean()
         else:
-            W = mod.output_weights.detach()
-            ranks = ops.rank_of_target(xr, W, labels, 1.0 / T)
-            loss, loss_rows, _lse = ops.linear_softmax_ce_fwd(xr, W, labels, 1.0 / T, smooth)
+            W = self.pre.module.output_weights.detach()
+            ranks = ops.rank_of_target(xr, W, labels, inv_t)
+            loss, loss_rows, _lse = ops.linear_softmax_ce_fwd(xr, W, labels, inv_t, smooth)
         return {"loss": loss, "loss_rows": loss_rows, "labels": labels, "ranks": ranks,
                 "metrics": self.metrics_from_ranks(ranks)}
 
