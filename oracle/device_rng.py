@@ -19,6 +19,10 @@ from the device, tests/test_device_rng_oracle.py against the published Philox kn
   * MLM training draws: bernoulli word x of block (offset + b*L + l, 0); j1 / j2 selectors words x / y of block
     (offset + b, 1), index = min(n - 1, int(float32(word >> 8) * 2^-24 * n)).
 
+`xlnet_dropout_masks` / `gpt2_dropout_masks` / `bert_dropout_masks` lay the site masks of one training forward out for the three
+bodies; their site lists come from the HF sources, not from the HIP path's host code (tests/test_round6_gpu.py and
+tests/test_gpt2_bert_train_gpu.py hold the HIP path to them).
+
 `oracle/device_rng.c` is the same arithmetic in C (OpenMP) for full-size tensors; `use_c()` says whether the compiled
 form is present; results are identical by test.
 """
@@ -182,3 +186,35 @@ def xlnet_dropout_masks(B, L, D, n_head, n_layer, p, seed, offset, d_inner=None)
                              ff_act=site((B, L, F), i, SITE_FF_ACT), ff_out=site((B, L, D), i, SITE_FF_OUT))
                         for i in range(n_layer)],
                 final=site((B, L, D), MODEL_LEVEL, SITE_FINAL))
+
+
+def _site_masks(seed, offset, p_of):
+    import torch
+
+    def site(shape, layer, s):
+        n = int(np.prod(shape))
+        return torch.from_numpy(dropout_keep(seed, dropout_ctr_hi(offset, layer, s), n, p_of(s))).view(*shape)
+
+    return site
+
+
+def gpt2_dropout_masks(B, L, D, n_head, n_layer, p, seed, offset):
+    """every dropout mask of ONE training forward of the GPT-2 body as the device draws them (`offset` = the model's forward
+    counter, 1 for the first training forward).  The sites are HF GPT2Model's (modeling_gpt2.py: `self.drop` on
+    inputs_embeds + position_embeds; per block the attention probabilities, `resid_dropout` on the attention c_proj output,
+    the MLP's `dropout` on its c_proj output): dict input [B,L,D], layers = list of dict prob [B,n,L,L] / attn_out [B,L,D] /
+    ff_out [B,L,D]; uint8 torch tensors (1 = kept).  Element index = the row-major index in the shapes above."""
+    site = _site_masks(seed, offset, lambda s: p)
+    return dict(input=site((B, L, D), MODEL_LEVEL, SITE_INPUT),
+                layers=[dict(prob=site((B, n_head, L, L), i, SITE_PROB), attn_out=site((B, L, D), i, SITE_ATTN_OUT),
+                             ff_out=site((B, L, D), i, SITE_FF_OUT)) for i in range(n_layer)])
+
+
+def bert_dropout_masks(B, L, D, n_head, n_layer, p_hidden, p_attn, seed, offset):
+    """the same for the BERT body (HF modeling_bert.py: BertEmbeddings.dropout after the embedding LayerNorm,
+    BertSelfOutput.dropout and BertOutput.dropout on the dense outputs at hidden_dropout_prob; the attention probabilities at
+    attention_probs_dropout_prob): the dictionary of gpt2_dropout_masks."""
+    site = _site_masks(seed, offset, lambda s: p_attn if s == SITE_PROB else p_hidden)
+    return dict(input=site((B, L, D), MODEL_LEVEL, SITE_INPUT),
+                layers=[dict(prob=site((B, n_head, L, L), i, SITE_PROB), attn_out=site((B, L, D), i, SITE_ATTN_OUT),
+                             ff_out=site((B, L, D), i, SITE_FF_OUT)) for i in range(n_layer)])

@@ -97,3 +97,41 @@ def test_mask_dictionary_shapes():
     assert m["input"].shape == (3, 5, 8) and m["pos"].shape == (3, 10, 8) and m["final"].shape == (3, 5, 8)
     assert len(m["layers"]) == 2 and m["layers"][1]["prob"].shape == (3, 2, 5, 5) and m["layers"][0]["ff_act"].shape == (3, 5, 32)
     assert not torch.equal(m["layers"][0]["attn_out"], m["layers"][1]["attn_out"])
+
+
+@pytest.mark.parametrize("arch", ["gpt2", "bert"])
+def test_gpt2_bert_mask_builders(arch):
+    """shapes, dtypes, every site == dropout_keep at (offset, MODEL_LEVEL, SITE_INPUT) / (offset, layer, SITE_PROB |
+    SITE_ATTN_OUT | SITE_FF_OUT) over the row-major index, BERT's attention rate on the prob site only, and no two sites
+    of one forward on one counter."""
+    B, L, D, n, NL, seed, offset = 3, 5, 8, 2, 3, 0x1234_5678_9ABC, 7
+    ph, pa = (0.3, 0.3) if arch == "gpt2" else (0.1, 0.3)
+    if arch == "gpt2":
+        m = R.gpt2_dropout_masks(B, L, D, n, NL, ph, seed=seed, offset=offset)
+    else:
+        m = R.bert_dropout_masks(B, L, D, n, NL, ph, pa, seed=seed, offset=offset)
+    assert sorted(m) == ["input", "layers"] and len(m["layers"]) == NL
+    want = [("input", m["input"], (B, L, D), R.MODEL_LEVEL, R.SITE_INPUT, ph)]
+    for i, lm in enumerate(m["layers"]):
+        assert sorted(lm) == ["attn_out", "ff_out", "prob"]
+        want += [(f"prob{i}", lm["prob"], (B, n, L, L), i, R.SITE_PROB, pa),
+                 (f"attn_out{i}", lm["attn_out"], (B, L, D), i, R.SITE_ATTN_OUT, ph),
+                 (f"ff_out{i}", lm["ff_out"], (B, L, D), i, R.SITE_FF_OUT, ph)]
+    ctrs = []
+    for name, got, shape, layer, site, p in want:
+        ctr = (offset << 16) | (layer << 8) | site
+        ctrs.append(ctr)
+        assert got.dtype == torch.uint8 and tuple(got.shape) == shape, name
+        keep = R.dropout_keep(seed, ctr, int(np.prod(shape)), p, force_numpy=True)
+        assert np.array_equal(got.numpy().reshape(-1), keep), name
+        assert 0 < int(got.sum()) < got.numel(), name
+    assert len(set(ctrs)) == len(ctrs) == 1 + 3 * NL
+    assert (R.SITE_INPUT, R.SITE_PROB, R.SITE_ATTN_OUT, R.SITE_FF_OUT) == (0, 2, 3, 5) and R.MODEL_LEVEL == 255
+    if arch == "bert":          # the two rates are not exchanged: the keep fractions differ (0.9 vs 0.7)
+        big = R.bert_dropout_masks(8, 32, 64, 4, 1, 0.1, 0.3, seed=seed, offset=1)
+        assert abs(float(big["layers"][0]["prob"].float().mean()) - 0.7) < 0.02
+        assert abs(float(big["layers"][0]["attn_out"].float().mean()) - 0.9) < 0.02
+        assert abs(float(big["input"].float().mean()) - 0.9) < 0.02
+    nxt = (R.gpt2_dropout_masks(B, L, D, n, NL, ph, seed=seed, offset=offset + 1) if arch == "gpt2" else
+           R.bert_dropout_masks(B, L, D, n, NL, ph, pa, seed=seed, offset=offset + 1))
+    assert not torch.equal(nxt["input"], m["input"]) and not torch.equal(nxt["layers"][0]["prob"], m["layers"][0]["prob"])

@@ -187,3 +187,129 @@ def test_xlnet_training_mode_restatement_matches_hf(B, L, D, n, layers):
     torch.testing.assert_close(lp[-1]["w1"].grad, m.layer[-1].ff.layer_1.weight.grad, rtol=1e-4, atol=2e-5)
     # and the masks mattered
     assert float((got - O.xlnet_model(xo, lp, n, 0.03)).abs().max()) > 1e-2
+
+
+def _record_dropout_calls(monkeypatch):
+    """every call of torch.nn.functional.dropout (nn.Dropout modules and the attention-probability dropout inside HF's
+    eager_attention_forward alike) -> list of (kept mask, p); kept <=> output != 0, or the input was 0 (where the mask
+    does not matter)."""
+    calls = []
+    orig = torch.nn.functional.dropout
+
+    def rec(x, p=0.5, training=True, inplace=False):
+        out = orig(x, p=p, training=training, inplace=False)
+        if training and p > 0:
+            calls.append((((out != 0) | (x == 0)).detach(), float(p)))
+        return out
+
+    monkeypatch.setattr(torch.nn.functional, "dropout", rec)
+    return calls
+
+
+def _masks_from_calls(calls, B, L, D, n, layers, p_hidden, p_attn):
+    """the recorded order is HF's execution order: input, then per layer prob, attention output, MLP output"""
+    assert len(calls) == 1 + 3 * layers
+    (inp, p0), rest = calls[0], calls[1:]
+    assert inp.shape == (B, L, D) and p0 == p_hidden
+    masks = dict(input=inp, layers=[])
+    for i in range(layers):
+        (prob, pp), (ao, pao), (fo, pfo) = rest[3 * i: 3 * i + 3]
+        assert prob.shape == (B, n, L, L) and ao.shape == (B, L, D) and fo.shape == (B, L, D), i
+        assert (pp, pao, pfo) == (p_attn, p_hidden, p_hidden), i
+        masks["layers"].append(dict(prob=prob, attn_out=ao, ff_out=fo))
+    return masks
+
+
+def _leaf_params(P):
+    def leaf(v):
+        if isinstance(v, list):
+            return [leaf(x) for x in v]
+        if isinstance(v, dict):
+            return {k: leaf(x) for k, x in v.items()}
+        return v.detach().clone().requires_grad_()
+
+    return leaf(P)
+
+
+@pytest.mark.parametrize("B,L,D,n,layers", [(3, 20, 64, 4, 2), (2, 50, 32, 2, 1)])
+def test_gpt2_training_mode_restatement_matches_hf(B, L, D, n, layers, monkeypatch):
+    """oracle gpt2_model_dropout against the installed HF GPT2Model in .train() at dropout 0.3, configured as
+    GPT2Config.build passes it (eps 1e-5): the masks HF drew are recorded call by call (the attention-probability
+    dropout is a functional call inside eager_attention_forward, which hooks do not see and `sdpa` hides: eager
+    attention, torch.nn.functional.dropout wrapped for the forward) and handed to the oracle; output and gradients must
+    agree.  This pins the site list (input on x + wpe; prob, attention c_proj output, MLP c_proj output per block; none on
+    the GELU activation, none after ln_f), their order against the residual adds, and the 1/(1-p) scaling."""
+    p_drop = 0.3
+    cfg = transformers.GPT2Config(n_embd=D, n_inner=4 * D, n_layer=layers, n_head=n, activation_function="gelu",
+                                  initializer_range=0.01, layer_norm_eps=0.03, resid_pdrop=p_drop, embd_pdrop=p_drop,
+                                  attn_pdrop=p_drop, n_positions=L, n_ctx=L, vocab_size=1, attn_implementation="eager")
+    assert cfg.layer_norm_epsilon == 1e-5
+    m = transformers.GPT2Model(cfg).train()
+    _rand_init(m, 5)
+    torch.manual_seed(6)
+    x = torch.randn(B, L, D, requires_grad=True)
+    calls = _record_dropout_calls(monkeypatch)
+    ref = m(inputs_embeds=x)[0]
+    monkeypatch.undo()
+    masks = _masks_from_calls(calls, B, L, D, n, layers, p_drop, p_drop)
+    P = _leaf_params(O.gpt2_params_from_state(m.state_dict()))
+    xo = x.detach().clone().requires_grad_()
+    got = O.gpt2_model_dropout(xo, P, n, 1e-5, masks, p_drop)
+    torch.testing.assert_close(got, ref, rtol=1e-5, atol=2e-5)
+    w = torch.randn(B, L, D)
+    (ref * w).sum().backward()
+    (got * w).sum().backward()
+    torch.testing.assert_close(xo.grad, x.grad, rtol=1e-4, atol=2e-5)
+    torch.testing.assert_close(P["blocks"][0]["c_attn_w"].grad, m.h[0].attn.c_attn.weight.grad, rtol=1e-4, atol=2e-5)
+    torch.testing.assert_close(P["blocks"][-1]["c_proj2_w"].grad, m.h[-1].mlp.c_proj.weight.grad, rtol=1e-4, atol=2e-5)
+    torch.testing.assert_close(P["wpe"].grad, m.wpe.weight.grad, rtol=1e-4, atol=2e-5)
+    with torch.no_grad():
+        plain = O.gpt2_model(xo, P, n, 1e-5)
+        assert float((got - plain).abs().max()) > 1e-2            # the masks mattered
+        ones = dict(input=torch.ones(B, L, D), layers=[dict(prob=torch.ones(B, n, L, L), attn_out=torch.ones(B, L, D),
+                                                            ff_out=torch.ones(B, L, D)) for _ in range(layers)])
+        assert torch.equal(O.gpt2_model_dropout(xo, P, n, 1e-5, ones, 0.0), plain)      # p = 0: the eval function, exactly
+
+
+@pytest.mark.parametrize("B,L,D,n,layers,ph,pa", [(3, 20, 64, 4, 2, 0.1, 0.1), (2, 33, 32, 2, 1, 0.1, 0.1),
+                                                  (3, 20, 64, 4, 2, 0.1, 0.3)])
+def test_bert_training_mode_restatement_matches_hf(B, L, D, n, layers, ph, pa, monkeypatch):
+    """oracle bert_model_dropout against the installed HF BertModel in .train(), configured as BertConfig.build passes it
+    (HF's 0.1 / 0.1 stay, intermediate_size 3072, eps 0.03), and once with unequal rates so that the hidden and the
+    attention rate cannot be exchanged unnoticed.  Masks recovered as in the GPT-2 test.  Pins: input dropout AFTER the
+    embedding LayerNorm; prob at the attention rate; the two dense outputs dropped BEFORE add + LayerNorm."""
+    cfg = transformers.BertConfig(hidden_size=D, num_hidden_layers=layers, num_attention_heads=n, hidden_act="gelu",
+                                  initializer_range=0.01, layer_norm_eps=0.03, pad_token_id=0,
+                                  max_position_embeddings=L + 2, vocab_size=1, hidden_dropout_prob=ph,
+                                  attention_probs_dropout_prob=pa, attn_implementation="eager")
+    assert cfg.intermediate_size == 3072
+    if (ph, pa) == (0.1, 0.1):        # what the builder leaves in place: HF's own defaults
+        dflt = transformers.BertConfig()
+        assert (dflt.hidden_dropout_prob, dflt.attention_probs_dropout_prob) == (0.1, 0.1)
+    m = transformers.BertModel(cfg).train()
+    _rand_init(m, 7)
+    torch.manual_seed(8)
+    x = torch.randn(B, L, D, requires_grad=True)
+    calls = _record_dropout_calls(monkeypatch)
+    ref = m(inputs_embeds=x)[0]
+    monkeypatch.undo()
+    masks = _masks_from_calls(calls, B, L, D, n, layers, ph, pa)
+    P = _leaf_params(O.bert_params_from_state(m.state_dict()))
+    xo = x.detach().clone().requires_grad_()
+    got = O.bert_model_dropout(xo, P, n, 0.03, masks, ph, pa)
+    torch.testing.assert_close(got, ref, rtol=1e-5, atol=2e-5)
+    w = torch.randn(B, L, D)
+    (ref * w).sum().backward()
+    (got * w).sum().backward()
+    torch.testing.assert_close(xo.grad, x.grad, rtol=1e-4, atol=2e-5)
+    torch.testing.assert_close(P["layers"][0]["q_w"].grad, m.encoder.layer[0].attention.self.query.weight.grad, rtol=1e-4, atol=2e-5)
+    torch.testing.assert_close(P["layers"][-1]["o_w"].grad, m.encoder.layer[-1].output.dense.weight.grad, rtol=1e-4, atol=2e-5)
+    torch.testing.assert_close(P["pos"].grad, m.embeddings.position_embeddings.weight.grad, rtol=1e-4, atol=2e-5)
+    with torch.no_grad():
+        plain = O.bert_model(xo, P, n, 0.03)
+        assert float((got - plain).abs().max()) > 1e-2            # the masks mattered
+        if ph != pa:                                              # and so did which rate goes where
+            assert float((O.bert_model_dropout(xo, P, n, 0.03, masks, pa, ph) - got).abs().max()) > 1e-2
+        ones = dict(input=torch.ones(B, L, D), layers=[dict(prob=torch.ones(B, n, L, L), attn_out=torch.ones(B, L, D),
+                                                            ff_out=torch.ones(B, L, D)) for _ in range(layers)])
+        assert torch.equal(O.bert_model_dropout(xo, P, n, 0.03, ones, 0.0, 0.0), plain)

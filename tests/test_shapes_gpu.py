@@ -2,7 +2,8 @@
 transformer.py:218-260 GPT-2, :432-482 XLNet, :493-534 BERT): two training steps and an inference call of the module mirror must run
 through the general kernels (csrc/xlnet_attn_long.hip, the 16-word instance of mask_targets_kernel) with finite losses.  Numerical
 parity of those kernels is in tests/test_kernels_gpu.py / test_e2e_gpu.py (reference fixtures at total_seq_length 100 / 150) and
-tests/test_round6_gpu.py (dropout steps against the oracle); this file guards the COVERAGE (tools/shape_sweep.py is the full list)."""
+tests/test_round6_gpu.py (XLNet dropout steps against the oracle) / tests/test_gpt2_bert_train_gpu.py (GPT-2 / BERT bodies and whole
+steps in training mode, dropout on, against the oracle at L 20 ... 130); this file guards the COVERAGE (tools/shape_sweep.py is the full list)."""
 import os
 import sys
 
