@@ -62,7 +62,9 @@ int t4r_ragged_gather_to_padded(void* stream, const void* values, const long* of
  *            sequence (features/embedding.py:229-240 2-D branch + tabular/base.py:53-63)
  *         3: per-session dense rows, input[f] = fp32 [B, dim[f]] (a context feature after a post
  *            transformation), broadcast over the sequence
- * agg 0 concat (col[f] = first output column) | 1 sum | 2 item * sum(others) (item_feat = index)
+ * agg 0 concat (col[f] = first output column; a column of [0, W) that no feature covers is left untouched when W <= 1024
+ *       and W, every dim[f] and every col[f] are multiples of 4 -- the row buffer may hold other blocks there -- and is
+ *       written 0 otherwise) | 1 sum | 2 item * sum(others) (item_feat = index); 1, 2: every dim[f] == W
  * mask_mode 0 none | 1 MLM (out = mask ? memb : x) | 2 CLM train/eval (mask ? (l==L-1 ? 0 : x) : memb)
  *           | 3 CLM inference (mask ? x : memb).  L_out = L_in + 1 is the MLM-inference grid
  *           (position L duplicates L-1 before masking).
@@ -355,6 +357,8 @@ long t4r_colreduce_ws_floats(long rows, int ncols);
 int t4r_act_bwd_bias(void* stream, const float* dact, const float* pre, float* dpre, float* dbias,
                      float* ws, long rows, int N, int mode, float drop_p, unsigned long long seed,
                      unsigned long long ctr_hi);
+/* out[c] += sum_r x[r, c], c < N (out ACCUMULATED: the caller zeroes it for a plain sum); x rows of pitch ld >= N floats,
+ * N % 4 == 0 and ld % 4 == 0; ws: t4r_colreduce_ws_floats(rows, N) floats */
 int t4r_colsum(void* stream, const float* x, float* out, float* ws, long rows, int N, long ld);
 
 /* ----------------------------------------------------------------------------------------
@@ -571,7 +575,8 @@ int t4r_sampled_logits_fwd(void* stream, const float* x, const long* labels, con
  * id = min_id + floor(R^u) - 1, R = max_id - min_id + 1, u = Philox(seed, (i, ctr_hi)); out int64 [n] */
 int t4r_log_uniform_sample(void* stream, long* out, int n, long min_id, long max_id, unsigned long long seed,
                            unsigned long long ctr_hi);
-/* dlogits is modified in place (accidental-hit entries zeroed: they carry no gradient);
+/* dlogits is modified in place (accidental-hit entries zeroed: they carry no gradient); dx [N, D] overwritten; dW [V, D]
+ * ACCUMULATED (the negatives' rows and, with atomics, the label rows are added into it); neg_samples must be distinct ids;
  * ws = 2 * n_neg * D floats of scratch (gathered negative rows of W and their gradient). */
 int t4r_sampled_logits_bwd(void* stream, float* dlogits, const float* x, const long* labels,
                            const float* W, const long* neg_samples, float* dx, float* dW, float* ws, int N,
