@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # T4R_HIP_LIB selects another build of the same ABI (A/B timing of kernel variants on one box)
 LIB_PATH = os.environ.get("T4R_HIP_LIB") or os.path.join(_HERE, "lib", "libt4r_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip.h")
+SAMPLING_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_sampling.h")
 
 _P, _I, _L, _F, _Q = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_ulonglong
 _C = {"p": _P, "i": _I, "l": _L, "f": _F, "Q": _Q}
@@ -149,6 +150,16 @@ _SIGS = {
     "t4r_head_split_w_amax_hint": ("v", "ppi"),
 }
 
+# the second header, include/t4r_hip_sampling.h (tests/test_sampling_cpu.py checks this table against it)
+_SIGS_SAMPLING = {
+    "t4r_gumbel_add_f32": ("i", "pp" + "iill" + "i" + "QQ"),
+    "t4r_gumbel_argmax_f32": ("i", "pp" + "iill" + "QQ" + "pp"),
+    "t4r_item_sample_ws_bytes": ("l", "iiii"),
+    "t4r_item_sample_f32": ("i", "p" + "iiif" + "pl" + "pl" + "i" + "pp" + "pl" + "p" + "lQQ"),
+    "t4r_item_sample_h16_ws_bytes": ("l", "iiii"),
+    "t4r_item_sample_h16": ("i", "p" + "iiif" + "pl" + "pl" + "i" + "i" + "pp" + "pl" + "p" + "lQQ"),
+}
+
 _lib = None
 
 
@@ -156,11 +167,20 @@ class T4RHipError(RuntimeError):
     pass
 
 
-def header_symbols():
-    """Function names declared in include/t4r_hip.h."""
-    with open(HEADER_PATH) as f:
+def _declared(path):
+    with open(path) as f:
         text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
     return sorted(set(re.findall(r"\b(t4r_\w+)\s*\(", text)))
+
+
+def header_symbols():
+    """Function names declared in include/t4r_hip.h."""
+    return _declared(HEADER_PATH)
+
+
+def sampling_header_symbols():
+    """Function names declared in include/t4r_hip_sampling.h."""
+    return _declared(SAMPLING_HEADER_PATH)
 
 
 def load():
@@ -173,7 +193,7 @@ def load():
             f"{LIB_PATH} not found: the HIP extension is not built "
             "(run `python -m transformers4rec_amd.build`). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (ret, args) in _SIGS.items():
+    for name, (ret, args) in list(_SIGS.items()) + list(_SIGS_SAMPLING.items()):
         fn = getattr(lib, name)
         fn.restype = ctypes.c_char_p if ret == "s" else (None if ret == "v" else _C[ret])
         fn.argtypes = [_C[a] for a in args]

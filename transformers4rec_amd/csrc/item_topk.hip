@@ -24,15 +24,15 @@
 //
 // The four steps and the overflow bookkeeping are itk_run (item_topk_plan.h), shared with item_topk_h16.hip; this file holds the
 // fp32 head's three products (Itk32Head), the gather of the sample and the select kernel.
-#include "t4r_common.h"
+// The SAMPLING form of the same call (t4r_item_sample_f32, include/t4r_hip_sampling.h) is the same four steps over the
+// perturbed score fp32(s + g(row, item)) (gumbel_noise.h): ItkNoisyHead (item_topk_plan.h) around this head.
+#include "item_topk_plan.h"
 
 int t4r_gemm_fp32_nt_launch(hipStream_t stream, int M, int N, int K, float alpha, const float* A, long lda,
                             const float* B, long ldb, float* C, long ldc);
 int t4r_gemm_topk_collect_launch(hipStream_t stream, int n_rows, int V, int D, float alpha, const float* X, long ldx,
                                  const float* W, long ldw, const float* thr, long thr_ld, int* count, float* cand_val,
-                                 int* cand_idx, int cap);
-
-#include "item_topk_plan.h"
+                                 int* cand_idx, int cap, const GumbelCfg* noise);
 
 namespace {
 
@@ -118,8 +118,10 @@ struct Itk32Head {
         T4R_LAUNCH_CHECK();
         return t4r_gemm_fp32_nt_launch(st, n_rows, pl.M, D, alpha, X, ldx, wsamp, D, S, pl.ldS);
     }
-    int collect(hipStream_t st, const float* thr, long thr_ld, int* count, float* cand_val, int* cand_idx, int cap) const {
-        return t4r_gemm_topk_collect_launch(st, n_rows, V, D, alpha, X, ldx, W, ldw, thr, thr_ld, count, cand_val, cand_idx, cap);
+    int collect(hipStream_t st, const float* thr, long thr_ld, int* count, float* cand_val, int* cand_idx, int cap,
+                const GumbelCfg* noise = nullptr) const {
+        return t4r_gemm_topk_collect_launch(st, n_rows, V, D, alpha, X, ldx, W, ldw, thr, thr_ld, count, cand_val, cand_idx, cap,
+                                            noise);
     }
     int scores(hipStream_t st, int r0, int n, float* C, long ldv) const {
         return t4r_gemm_fp32_nt_launch(st, n, V, D, alpha, X + (long)r0 * ldx, ldx, W, ldw, C, ldv);
@@ -157,4 +159,25 @@ extern "C" int t4r_item_topk_f32(void* stream, int n_rows, int V, int D, float a
                   "item_topk: workspace too small (t4r_item_topk_ws_bytes) or not 16-byte aligned");
     Itk32Head head = {n_rows, V, D, alpha, X, ldx, W, ldw, (float*)((char*)workspace + pl.off_wsamp)};
     return itk_run("item_topk", (hipStream_t)stream, pl, workspace, n_rows, V, k, out_val, out_idx, host_stats, head);
+}
+
+extern "C" long t4r_item_sample_ws_bytes(int n_rows, int V, int D, int k) { return t4r_item_topk_ws_bytes(n_rows, V, D, k); }
+
+// t4r_item_topk_f32 over fp32(score + g(row0 + row, item)): Gumbel top-k, a sample of k items without replacement in proportion
+// to softmax(scores) (include/t4r_hip_sampling.h)
+extern "C" int t4r_item_sample_f32(void* stream, int n_rows, int V, int D, float alpha, const float* X, long ldx,
+                                   const float* W, long ldw, int k, float* out_val, long* out_idx, void* workspace,
+                                   long ws_bytes, long* host_stats, long row0, unsigned long long seed,
+                                   unsigned long long ctr_hi) {
+    if (n_rows == 0) return 0;
+    T4R_CHECK_ARG(n_rows > 0 && V > 0 && D > 0 && X && W && out_val && out_idx, "item_sample: bad arguments");
+    T4R_CHECK_ARG(k >= 1 && k <= ITK_MAX_K && k <= V, "item_sample: 1 <= k <= min(256, V)");
+    T4R_CHECK_ARG(ldx >= D && ldw >= D, "item_sample: row pitch below D");
+    T4R_CHECK_ARG(row0 >= 0, "item_sample: row0 must not be negative");
+    const Plan pl = make_plan(n_rows, V, k, (size_t)D * 4, 0);
+    T4R_CHECK_ARG(workspace && ws_bytes >= (long)pl.total && (uintptr_t)workspace % 16 == 0,
+                  "item_sample: workspace too small (t4r_item_sample_ws_bytes) or not 16-byte aligned");
+    const Itk32Head base = {n_rows, V, D, alpha, X, ldx, W, ldw, (float*)((char*)workspace + pl.off_wsamp)};
+    ItkNoisyHead<Itk32Head> head = {base, {seed, ctr_hi, row0}, n_rows, V};
+    return itk_run("item_sample", (hipStream_t)stream, pl, workspace, n_rows, V, k, out_val, out_idx, host_stats, head);
 }

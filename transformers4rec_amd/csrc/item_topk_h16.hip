@@ -27,6 +27,8 @@
 //                             half's first lane, hits stored at base + prefix.
 //                             `stride` > 1 scores the strided sample of step 1 in place (item i of the launch is image row
 //                             i * stride): no gathered copy of the sample.
+//                             EPI 2 is EPI 1 over fp32(alpha * acc + g(row, item)): the collect pass of the sampling head
+//                             (t4r_item_sample_h16; gumbel_noise.h, ItkNoisyHead in item_topk_plan.h).
 //                             The tile load and the k loop live in item_h16_tile.h, shared with item_eval_h16.hip, as do the
 //                             image's argument contract and the dtype dispatch.
 //   select / threshold top-k  itk_select_kernel (item_topk.hip) and t4r_topk, unchanged; the plan and the four-step driver
@@ -87,6 +89,7 @@ struct Itk16Params {
     float* cand_val;
     int* cand_idx;
     int cap;
+    GumbelCfg noise;                // EPI 2: EPI 1 over fp32(v + g(row, item)) (gumbel_noise.h)
 };
 
 template <int DT, int EPI>
@@ -106,7 +109,7 @@ __global__ __launch_bounds__(256) void itk16_kernel(Itk16Params p) {
         // rows beyond n_rows read the last row (a legal address) and are masked in the epilogue
         const uint4* ap = reinterpret_cast<const uint4*>(p.x16 + (long)min(rb + r, p.n_rows - 1) * p.ldp) + h;
         float thr[16];
-        if (EPI == 1) {
+        if (EPI != 0) {
 #pragma unroll
             for (int e = 0; e < 16; ++e)
                 thr[e] = p.thr[(long)min(rb + itk16_acc_row(e, h), p.n_rows - 1) * p.thr_ld];
@@ -116,6 +119,22 @@ __global__ __launch_bounds__(256) void itk16_kernel(Itk16Params p) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const long col = item0 + j * 32 + r;
+            if (EPI == 2) {
+                // elements 4 q .. 4 q + 3 of a lane are four consecutive rows of its column: one Philox block
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    float g[4];
+                    gumbel_quad(p.noise, rb + itk16_acc_row(4 * q, h), (uint32_t)(col * p.stride), g);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int row = rb + itk16_acc_row(4 * q + e, h);
+                        const float v = gumbel_perturb(alpha * acc[j][4 * q + e], g[e]);
+                        itk_collect(col < p.n_items && row < p.n_rows && v >= thr[4 * q + e], v, (int)col, row, lane, p.count,
+                                    p.cand_val, p.cand_idx, p.cap);
+                    }
+                }
+                continue;
+            }
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const int row = rb + itk16_acc_row(e, h);
@@ -131,7 +150,7 @@ __global__ __launch_bounds__(256) void itk16_kernel(Itk16Params p) {
     }
 }
 
-T4rLdsAttr g_lds_attr[2][2];
+T4rLdsAttr g_lds_attr[2][3];
 
 template <int DT, int EPI>
 int launch_t(hipStream_t st, const Itk16Params& p) {
@@ -147,7 +166,7 @@ int launch_t(hipStream_t st, const Itk16Params& p) {
 int launch(hipStream_t st, int dtype, int epi, const Itk16Params& p) {
     return itk16_dispatch(dtype, [&](auto dt) {
         constexpr int DT = decltype(dt)::value;
-        return epi ? launch_t<DT, 1>(st, p) : launch_t<DT, 0>(st, p);
+        return epi == 2 ? launch_t<DT, 2>(st, p) : (epi ? launch_t<DT, 1>(st, p) : launch_t<DT, 0>(st, p));
     });
 }
 
@@ -161,10 +180,12 @@ struct Itk16Head {
         q.n_items = pl.M; q.stride = pl.stride; q.C = S; q.ldc = pl.ldS;
         return launch(st, dtype, 0, q);
     }
-    int collect(hipStream_t st, const float* thr, long thr_ld, int* count, float* cand_val, int* cand_idx, int cap) const {
+    int collect(hipStream_t st, const float* thr, long thr_ld, int* count, float* cand_val, int* cand_idx, int cap,
+                const GumbelCfg* noise = nullptr) const {
         Itk16Params q = p;
         q.thr = thr; q.thr_ld = thr_ld; q.count = count; q.cand_val = cand_val; q.cand_idx = cand_idx; q.cap = cap;
-        return launch(st, dtype, 1, q);
+        if (noise) q.noise = *noise;
+        return launch(st, dtype, noise ? 2 : 1, q);
     }
     int scores(hipStream_t st, int r0, int n, float* C, long ldv) const {
         Itk16Params q = p;
@@ -249,4 +270,33 @@ extern "C" int t4r_item_topk_h16(void* stream, int n_rows, int V, int D, float a
     p.n_rows = n_rows; p.n_items = V; p.ldp = (int)kp; p.x16 = x16; p.img = (const uint16_t*)image; p.ldi = ldp; p.stride = 1;
     p.alpha = alpha;
     return itk_run("item_topk_h16", st, pl, workspace, n_rows, V, k, out_val, out_idx, host_stats, head);
+}
+
+extern "C" long t4r_item_sample_h16_ws_bytes(int n_rows, int V, int D, int k) { return t4r_item_topk_h16_ws_bytes(n_rows, V, D, k); }
+
+// t4r_item_topk_h16 over fp32(score + g(row0 + row, item)) (include/t4r_hip_sampling.h)
+extern "C" int t4r_item_sample_h16(void* stream, int n_rows, int V, int D, float alpha, const float* X, long ldx,
+                                   const void* image, long ldp, int dtype, int k, float* out_val, long* out_idx, void* workspace,
+                                   long ws_bytes, long* host_stats, long row0, unsigned long long seed,
+                                   unsigned long long ctr_hi) {
+    if (n_rows == 0) return 0;
+    T4R_CHECK_ARG(n_rows > 0 && V > 0 && D > 0 && X && image && out_val && out_idx, "item_sample_h16: bad arguments");
+    T4R_CHECK_ARG(itk16_supported(D), "item_sample_h16: 1 <= D <= 512 (t4r_item_topk_h16_supported)");
+    T4R_CHECK_ARG(k >= 1 && k <= ITK_MAX_K && k <= V, "item_sample_h16: 1 <= k <= min(256, V)");
+    T4R_CHECK_ARG(ldx >= D, "item_sample_h16: row pitch below D");
+    T4R_CHECK_ARG(row0 >= 0, "item_sample_h16: row0 must not be negative");
+    ITK16_CHECK_IMAGE("item_sample_h16");
+    const long kp = itk16_image_ld(D);
+    const Plan pl = make_plan(n_rows, V, k, 0, (size_t)n_rows * kp * 2);
+    T4R_CHECK_ARG(workspace && ws_bytes >= (long)pl.total && (uintptr_t)workspace % 16 == 0,
+                  "item_sample_h16: workspace too small (t4r_item_sample_h16_ws_bytes) or not 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    uint16_t* x16 = (uint16_t*)((char*)workspace + pl.off_x);
+    int rc = t4r_itk16_round_rows(st, dtype, X, ldx, n_rows, D, x16, kp);
+    if (rc) return rc;
+    ItkNoisyHead<Itk16Head> head = {{dtype, {}}, {seed, ctr_hi, row0}, n_rows, V};
+    Itk16Params& p = head.head.p;
+    p.n_rows = n_rows; p.n_items = V; p.ldp = (int)kp; p.x16 = x16; p.img = (const uint16_t*)image; p.ldi = ldp; p.stride = 1;
+    p.alpha = alpha;
+    return itk_run("item_sample_h16", st, pl, workspace, n_rows, V, k, out_val, out_idx, host_stats, head);
 }

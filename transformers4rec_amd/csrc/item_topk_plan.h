@@ -3,6 +3,7 @@
 // bookkeeping are itk_run, once; a head only says how a block of scores is computed and how the collect pass runs.
 #pragma once
 #include "t4r_common.h"
+#include "gumbel_noise.h"
 #include <algorithm>
 #include <math.h>
 #include <string>
@@ -136,3 +137,31 @@ static int itk_run(const char* name, hipStream_t st, const Plan& pl, void* works
     if (host_stats) host_stats[0] = nf;
     return 0;
 }
+
+// scores[r, c] = fp32(scores[r, c] + g(row0 + r, c * item_stride)) in place (item_sample.hip): r < n_rows, c < V, row pitch ld
+int t4r_gumbel_add_launch(hipStream_t st, float* scores, int n_rows, int V, long ld, long row0, int item_stride,
+                          unsigned long long seed, unsigned long long ctr_hi);
+
+// The sampling form of a head: every score of (row, item) becomes fp32(s + g(row0 + row, item)) -- still a pure function of
+// (row, item), so itk_run's four steps stay exact.  The materialised products are the head's own followed by the noise pass;
+// the collect pass adds the noise in its epilogue.  All three give one (row, item) the same bits (gumbel_noise.h).
+template <class Head>
+struct ItkNoisyHead {
+    Head head;
+    GumbelCfg noise;
+    int n_rows, V;
+
+    int sample(hipStream_t st, const Plan& pl, float* S) const {
+        const int rc = head.sample(st, pl, S);
+        if (rc) return rc;
+        return t4r_gumbel_add_launch(st, S, n_rows, pl.M, pl.ldS, noise.row0, pl.stride, noise.seed, noise.ctr_hi);
+    }
+    int collect(hipStream_t st, const float* thr, long thr_ld, int* count, float* cand_val, int* cand_idx, int cap) const {
+        return head.collect(st, thr, thr_ld, count, cand_val, cand_idx, cap, &noise);
+    }
+    int scores(hipStream_t st, int r0, int n, float* C, long ldv) const {
+        const int rc = head.scores(st, r0, n, C, ldv);
+        if (rc) return rc;
+        return t4r_gumbel_add_launch(st, C, n, V, ldv, noise.row0 + r0, 1, noise.seed, noise.ctr_hi);
+    }
+};

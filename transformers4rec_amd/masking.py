@@ -1,9 +1,11 @@
 """Masking modules: host-side mirror of transformers4rec/torch/masking.py for the hot path
-(MaskSequence :61-243, CausalLanguageModeling :247-337, MaskedLanguageModeling :342-498).
+(MaskSequence :61-243, CausalLanguageModeling :247-337, MaskedLanguageModeling :342-498,
+ReplacementLanguageModeling :753-870).
 Same constructor arguments, attributes (`mask_schema`, `masked_targets`, `padding_idx`,
 `masked_item_embedding`) and state_dict names; the integer work runs in
-csrc/masking.hip, the embedding replacement in csrc/embedding.hip.
-PLM / RTD are out of scope.
+csrc/masking.hip, the embedding replacement in csrc/embedding.hip, the replacement draw of RTD in
+csrc/item_sample.hip and the sampling heads (csrc/gumbel_noise.h).
+PLM is out of scope; so are RTD's discriminator and its loss, which the reference library does not hold either.
 """
 from collections import namedtuple
 from typing import Optional
@@ -278,9 +280,57 @@ class MaskedLanguageModeling(MaskSequence):
                                   ops.MASK_MLM)
 
 
+class ReplacementLanguageModeling(MaskedLanguageModeling):
+    """reference masking.py:753-870: MLM selects the positions, the generator's scores at those positions draw replacement
+    items, a discriminator (outside the library, as in the reference) learns to tell them from the originals.
+
+    The draw (`sample_from_softmax`) is one Gumbel-argmax per label row on the device: from materialised logits in one pass
+    (ops.gumbel_argmax), from the non-materialising head's LazyPredictions through the fused sampling head (ops.item_sample) --
+    the [N_m, V] logits are not needed.  Key: this module's `seed`; stream position `_sample_offset` (+1 per call, in
+    rng.get_rng_state), ctr_hi = dropout_ctr_hi(_sample_offset, 255, SITE_GUMBEL) -- disjoint from the MLM draws, whose ctr_hi is
+    0 or 1.  Same distribution as the reference's torch.rand draw, replayable, not the same bits."""
+
+    def __init__(self, hidden_size, padding_idx=0, eval_on_last_item_seq_only=True, sample_from_batch=False, **kwargs):
+        super().__init__(hidden_size=hidden_size, padding_idx=padding_idx,
+                         eval_on_last_item_seq_only=eval_on_last_item_seq_only, **kwargs)
+        self.sample_from_batch = sample_from_batch
+        self._sample_offset = 0
+
+    def sample_from_softmax(self, logits):
+        """ids [N_m] int64 of one draw per row from softmax(logits[row]) (reference :850-870).  logits: a device tensor
+        [N_m, C], or the LazyPredictions of a non-materialising head (the draw then never forms them)."""
+        self._sample_offset += 1
+        ctr_hi = ops.dropout_ctr_hi(self._sample_offset, 255, ops.SITE_GUMBEL)
+        if hasattr(logits, "sample") and hasattr(logits, "is_materialized"):        # prediction_task.LazyPredictions
+            return logits.sample(1, self.seed, ctr_hi)[1].flatten()
+        return ops.gumbel_argmax(logits, self.seed, ctr_hi)[1]
+
+    def get_fake_tokens(self, itemid_seq, target_flat, logits):
+        """(corrupted_inputs [B, L], discriminator_labels [B, L] bool, batch_updates) as reference :787-848: the label
+        positions of `target_flat` [B L] receive the drawn items; with sample_from_batch the logits are over the label rows of
+        the batch and the draw indexes them (batch_updates), else it is an item id (batch_updates == [])."""
+        drawn = self.sample_from_softmax(logits).flatten().to(target_flat.device)
+        return self._replace_tokens(itemid_seq, target_flat, drawn)
+
+    def _replace_tokens(self, itemid_seq, target_flat, drawn):
+        """the integer part of get_fake_tokens: a pure function of its arguments, ordinary torch ops on T elements"""
+        non_pad_mask = target_flat != self.padding_idx
+        if self.sample_from_batch:
+            batch_updates = drawn
+            updates = torch.masked_select(target_flat, non_pad_mask)[batch_updates]
+        else:
+            updates, batch_updates = drawn, []
+        where = non_pad_mask.nonzero().flatten()
+        corrupted_labels = target_flat.clone().detach().scatter(-1, where, updates)
+        discriminator_labels = (corrupted_labels != target_flat).view(-1, itemid_seq.size(1))
+        corrupted_inputs = itemid_seq.clone().detach().reshape(-1).scatter(-1, where, updates)
+        return corrupted_inputs.view(-1, itemid_seq.size(1)), discriminator_labels, batch_updates
+
+
 masking_registry = {
     "clm": CausalLanguageModeling, "causal": CausalLanguageModeling,
     "mlm": MaskedLanguageModeling, "masked": MaskedLanguageModeling,
+    "rtd": ReplacementLanguageModeling, "replacement": ReplacementLanguageModeling,
 }
 
 
@@ -289,5 +339,5 @@ def parse_masking(masking, hidden_size, **kwargs):
     if masking is None or isinstance(masking, MaskSequence):
         return masking
     if masking not in masking_registry:
-        raise KeyError(f"{masking} never registered with registry masking (supported: clm, causal, mlm, masked)")
+        raise KeyError(f"{masking} never registered with registry masking (supported: clm, causal, mlm, masked, rtd, replacement)")
     return masking_registry[masking](hidden_size=hidden_size, **kwargs)

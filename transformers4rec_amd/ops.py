@@ -322,6 +322,7 @@ def head_split_dx_rc(ws, x, W, lse, labels, grad_out, alpha=1.0, label_smoothing
 
 # ------------------------------------------------------------------------------------ LN / act
 SITE_INPUT, SITE_POS, SITE_PROB, SITE_ATTN_OUT, SITE_FF_ACT, SITE_FF_OUT, SITE_FINAL = range(7)
+SITE_GUMBEL = 7              # the Gumbel noise of the sampling heads: ctr_hi = dropout_ctr_hi(offset, 255, SITE_GUMBEL)
 LAYER_FUSE_FINAL = 0x100     # flag in xlnet_layer_fwd / _bwd's layer_idx: this layer also applies the model's output dropout
 LAYER_FUSE_INPUT = 0x200     # ... this (first) layer applies the model's input dropout: h is the undropped input
 NO_DROP = (0.0, 0, 0)
@@ -1193,22 +1194,29 @@ def item_topk(x, W, k, alpha=1.0):
     tensor (csrc/item_topk.hip).  x and W may be row-strided views (unit inner stride).
     W a serving image (pack_item_table, fp16 / bf16; x stays fp32): the same from one 16-bit matrix-core product per multiply,
     bit for bit topk(item_scores(x, W, alpha), k) (csrc/item_topk_h16.hip); the precision mode plays no part."""
-    _check_x_w("item_topk", x, W)
+    return _item_head("item_topk", x, W, k, alpha, None)
+
+
+def _item_head(what, x, W, k, alpha, noise):
+    """item_topk (noise None) / item_sample (noise = (row0, seed, ctr_hi)): checks, workspace, row chunks, the stats record"""
+    _check_x_w(what, x, W)
     N, D = x.shape
     V = W.shape[0]
     k = int(k)
     if W.shape[1] != D:
-        raise ValueError(f"item_topk: inner dims differ ({D} vs {W.shape[1]})")
+        raise ValueError(f"{what}: inner dims differ ({D} vs {W.shape[1]})")
     if not 1 <= k <= min(256, V):
-        raise ValueError(f"item_topk: 1 <= k <= min(256, V) (k = {k}, V = {V})")
+        raise ValueError(f"{what}: 1 <= k <= min(256, V) (k = {k}, V = {V})")
     h16 = W.dtype in _H16
-    ldw = _check_image("item_topk", W, D) if h16 else _row_pitch(W, D)
+    ldw = _check_image(what, W, D) if h16 else _row_pitch(W, D)
     vals = torch.empty((N, k), device=x.device, dtype=torch.float32)
     idx = torch.empty((N, k), device=x.device, dtype=torch.int64)
     if N == 0:
         return vals, idx
     lib = _lib.load()
-    ws_bytes = lib.t4r_item_topk_h16_ws_bytes if h16 else lib.t4r_item_topk_ws_bytes
+    stem = "t4r_item_topk" if noise is None else "t4r_item_sample"
+    entry = stem + ("_h16" if h16 else "_f32")
+    ws_bytes = getattr(lib, stem + ("_h16_ws_bytes" if h16 else "_ws_bytes"))
     rows = N
     while rows > 1 and ws_bytes(rows, V, D, k) > _ITEM_TOPK_WS_LIMIT:
         rows = (rows + 1) // 2
@@ -1219,13 +1227,10 @@ def item_topk(x, W, k, alpha=1.0):
     for s0 in range(0, N, rows):
         n = min(rows, N - s0)
         st[7] = int(_ITEM_TOPK["collect_counts"])
-        if h16:
-            call("t4r_item_topk_h16", _stream(), n, V, D, float(alpha), x[s0:].data_ptr(), ldx, W.data_ptr(), ldw,
-                 _H16[W.dtype], k, vals[s0:].data_ptr(), idx[s0:].data_ptr(), ws.data_ptr(), ws.numel(),
-                 ctypes.cast(st, ctypes.c_void_p))
-        else:
-            call("t4r_item_topk_f32", _stream(), n, V, D, float(alpha), x[s0:].data_ptr(), ldx, W.data_ptr(), ldw, k,
-                 vals[s0:].data_ptr(), idx[s0:].data_ptr(), ws.data_ptr(), ws.numel(), ctypes.cast(st, ctypes.c_void_p))
+        table = (W.data_ptr(), ldw, _H16[W.dtype]) if h16 else (W.data_ptr(), ldw)
+        tail = () if noise is None else (int(noise[0]) + s0, int(noise[1]), int(noise[2]))
+        call(entry, _stream(), n, V, D, float(alpha), x[s0:].data_ptr(), ldx, *table, k, vals[s0:].data_ptr(),
+             idx[s0:].data_ptr(), ws.data_ptr(), ws.numel(), ctypes.cast(st, ctypes.c_void_p), *tail)
         tot["fallback_rows"] += int(st[0])
         tot["cand_sum"] += int(st[3])
         tot["cand_max"] = max(tot["cand_max"], int(st[4]))
@@ -1234,6 +1239,55 @@ def item_topk(x, W, k, alpha=1.0):
     _ITEM_TOPK.update(tot, sample_rows=int(st[1]), list_capacity=int(st[2]),       # summed over the row chunks of this call
                       dtype={torch.float32: "fp32", torch.float16: "fp16", torch.bfloat16: "bf16"}[W.dtype])
     return vals, idx
+
+
+def _check_scores(what, scores):
+    if not scores.is_cuda:
+        raise _lib.T4RHipError(f"{what}: scores must be a HIP device tensor (got {scores.device}); there is no CPU path")
+    if scores.dtype != torch.float32:
+        raise TypeError(f"{what}: scores: expected torch.float32, got {scores.dtype}")
+    if scores.dim() != 2 or (scores.shape[1] > 1 and scores.stride(1) != 1):
+        raise ValueError(f"{what}: scores must be 2-D row-major with unit inner stride")
+
+
+def gumbel_add_(scores, seed, ctr_hi, row0=0):
+    """in place: scores[r, c] = fp32(scores[r, c] + g(seed, ctr_hi, row0 + r, c)), g the Gumbel noise of
+    include/t4r_hip_sampling.h (a pure function of its four arguments).  scores fp32 [N, V], row-strided views allowed;
+    returns scores.  topk(gumbel_add_(s.clone(), ...), k) is a sample of k items without replacement from softmax(s)."""
+    _check_scores("gumbel_add_", scores)
+    N, V = scores.shape
+    if N and V:
+        call("t4r_gumbel_add_f32", _stream(), scores.data_ptr(), N, V, _row_pitch(scores, V), int(row0), 1, int(seed), int(ctr_hi))
+    return scores
+
+
+def gumbel_argmax(scores, seed, ctr_hi, row0=0):
+    """(values [N] fp32, ids [N] int64): per row the largest fp32(scores[r, c] + g(seed, ctr_hi, row0 + r, c)) and its column,
+    ties to the lower column -- one draw per row from softmax(scores[r]) -- in one pass and without a perturbed copy of scores;
+    bit for bit topk(gumbel_add_(scores.clone(), ...), 1)."""
+    _check_scores("gumbel_argmax", scores)
+    N, V = scores.shape
+    if V < 1:
+        raise ValueError("gumbel_argmax: scores has no columns")
+    vals = torch.empty(N, device=scores.device, dtype=torch.float32)
+    idx = torch.empty(N, device=scores.device, dtype=torch.int64)
+    if N:
+        call("t4r_gumbel_argmax_f32", _stream(), scores.data_ptr(), N, V, _row_pitch(scores, V), int(row0), int(seed), int(ctr_hi),
+             vals.data_ptr(), idx.data_ptr())
+    return vals, idx
+
+
+def item_sample(x, W, k, seed, ctr_hi, alpha=1.0, row0=0):
+    """(values [N, k] fp32, ids [N, k] int64): k items per row drawn WITHOUT replacement in proportion to
+    softmax(alpha * x @ W^T) (Gumbel top-k), without an [N, V] tensor: item_topk over the perturbed score
+    fp32(s[r, v] + g(seed, ctr_hi, row0 + r, v)).  values are the perturbed scores, descending.  Bit for bit
+    topk(gumbel_add_(item_scores(x, W, alpha).clone(), seed, ctr_hi, row0), k) -- for an fp32 W under precision("fp32").
+    W fp32 or a serving image, x and W row-strided views as item_topk takes them; item_topk_stats() records the call.
+    ctr_hi = dropout_ctr_hi(offset, 255, SITE_GUMBEL) by convention; the same (seed, ctr_hi, row0) replays the draw, and
+    item_sample(x[a:b], ..., row0=a) is rows a..b-1 of the whole call."""
+    if int(row0) < 0:
+        raise ValueError(f"item_sample: row0 must not be negative (got {row0})")
+    return _item_head("item_sample", x, W, k, alpha, (row0, seed, ctr_hi))
 
 
 def item_eval(x, image, labels, alpha=1.0):

@@ -20,7 +20,7 @@ from ._lib import exp_env as _exp_env
 from .features import _Linear
 from .masking import MaskedLanguageModeling, _grad_buf
 from .ranking_metric import coerce as coerce_metric, default_metrics
-from .rng import SeedMixin
+from .rng import SeedMixin, default_seed
 
 
 class LogUniformSampler(SeedMixin, nn.Module):
@@ -287,8 +287,9 @@ class LazyPredictions:
     time anything looks at them -- `.materialize()`, any tensor attribute / method, indexing, or any
     torch function taking this object -- and cached.  Shape / dtype / device are known without computing."""
 
-    def __init__(self, compute, shape, device):
-        self._compute, self._value = compute, None
+    def __init__(self, compute, shape, device, rows=None):
+        # rows: () -> (x [N, D], W [V, D], alpha), the operands compute() multiplies: what sample() hands the fused sampling head
+        self._compute, self._value, self._rows = compute, None, rows
         self.shape, self.device, self.dtype = torch.Size(shape), device, torch.float32
 
     def materialize(self):
@@ -300,6 +301,21 @@ class LazyPredictions:
     @property
     def is_materialized(self):
         return self._value is not None
+
+    def sample(self, k, seed, ctr_hi):
+        """(values [N, k] fp32, ids [N, k] int64): k items per row drawn without replacement in proportion to softmax(logits[row])
+        (Gumbel top-k over logits + g(seed, ctr_hi, row, item); values = the perturbed logits, descending).  While the logits are
+        not materialised they stay that way: their rows (task block and temperature as `materialize` applies them) go through the
+        fused sampling head over the fp32 table (ops.item_sample).  Materialised logits are read in place: one pass for k = 1
+        (ops.gumbel_argmax), a perturbed copy and topk otherwise."""
+        if self._value is None and self._rows is not None:
+            xr, W, alpha = self._rows()
+            return ops.item_sample(xr, W, k, seed, ctr_hi, alpha)
+        logits = self.materialize()
+        if int(k) == 1:
+            vals, idx = ops.gumbel_argmax(logits, seed, ctr_hi)
+            return vals[:, None], idx[:, None]
+        return ops.topk(ops.gumbel_add_(logits.clone(), seed, ctr_hi), int(k))
 
     def size(self, dim=None):
         return self.shape if dim is None else self.shape[dim]
@@ -314,7 +330,7 @@ class LazyPredictions:
         return self.materialize()[idx]
 
     def __getattr__(self, name):         # only reached for names not defined above: tensor methods
-        if name.startswith("__") or name in ("_compute", "_value"):
+        if name.startswith("__") or name in ("_compute", "_value", "_rows"):
             raise AttributeError(name)
         return getattr(self.materialize(), name)
 
@@ -356,6 +372,10 @@ class NextItemPredictionTask(nn.Module):
         self._serving_image = None
         self._serving_record = None
         self.serving_packs = 0
+        # sample_items: Philox key `sample_seed` (lazy default as rng.SeedMixin's), stream position `_sample_offset` (+1 per call;
+        # both travel in rng.get_rng_state)
+        self._sample_seed = None
+        self._sample_offset = 0
         loss = loss if loss is not None else nn.CrossEntropyLoss()
         if not isinstance(loss, nn.CrossEntropyLoss):
             raise NotImplementedError("the HIP head fuses torch.nn.CrossEntropyLoss (optionally label-smoothed)")
@@ -511,16 +531,20 @@ class NextItemPredictionTask(nn.Module):
         T = float(mod.softmax_temperature) if mod.softmax_temperature else 1.0
         xd = x.detach()
 
-        def compute():
+        def rows():
             B, L, D = xd.shape
             xr = ops.gather_rows(xd.contiguous().view(B * L, D), pos, N)
             if self.task_block is not None:
                 lin = self.task_block[0][0]
                 xr = ops.gemm(xr, lin.weight.detach(), False, True, bias=lin.bias.detach(), epilogue=ops.EPI_BIAS)
-            V = W.shape[0]
-            return ops.gemm(xr, W.detach(), False, True, alpha=1.0 / T, ldc=ops.pad_ld(V))[:, :V]
+            return xr, W.detach(), 1.0 / T
 
-        return LazyPredictions(compute, (N, W.shape[0]), x.device)
+        def compute():
+            xr, Wd, alpha = rows()
+            V = Wd.shape[0]
+            return ops.gemm(xr, Wd, False, True, alpha=alpha, ldc=ops.pad_ld(V))[:, :V]
+
+        return LazyPredictions(compute, (N, W.shape[0]), x.device, rows)
 
     # ------------------------------------------------------------------ forward
     def forward(self, inputs, targets=None, training=False, testing=False, top_k=None, **kwargs):
@@ -552,6 +576,24 @@ class NextItemPredictionTask(nn.Module):
                 preds, y = logits, torch.zeros_like(labels)
             return {"loss": loss, "labels": y, "predictions": preds}
         # inference: hidden state at the last item (prediction_task.py:452-470)
+        xr, inv_t = self._inference_rows(x)
+        B = x.shape[0]
+        W = mod.output_weights.detach()
+        V = W.shape[0]
+        head = self._head_ops()
+        image = self._serving_weights()
+        if image is not None:
+            # served from the half-precision image: fused head for top-k, [B, V] fp32 scores otherwise; topk_mode plays no part
+            return head.item_scores(xr, image, inv_t) if top_k is None else head.item_topk(xr, image, inv_t, top_k)
+        if top_k is not None and self.resolve_topk_mode(B, V) == "fused":
+            return head.item_topk(xr, W, inv_t, top_k)
+        scores = head.item_scores(xr, W, inv_t)
+        return scores if top_k is None else head.topk(scores, top_k)
+
+    def _inference_rows(self, x):
+        """(xr [B, D'], 1 / T) of an inference call: the hidden state at the last item of every session of x [B, L, D]
+        (prediction_task.py:452-470) through the task block, and the inverse softmax temperature"""
+        mod = self.pre.module
         item_seq = self.embeddings.item_seq
         B, Lg, D = x.shape
         pos = ops.last_positions(item_seq.contiguous(), Lg, isinstance(self.masking, MaskedLanguageModeling),
@@ -560,18 +602,37 @@ class NextItemPredictionTask(nn.Module):
         if self.task_block is not None:
             lin = self.task_block[0][0]
             xr = ops.gemm(xr, lin.weight.detach(), False, True, bias=lin.bias.detach(), epilogue=ops.EPI_BIAS)
-        W = mod.output_weights.detach()
         T = float(mod.softmax_temperature) if mod.softmax_temperature else 1.0
-        V = W.shape[0]
-        head = self._head_ops()
+        return xr, 1.0 / T
+
+    # ------------------------------------------------------------------ sampling
+    @property
+    def sample_seed(self):
+        """Philox key of sample_items; defaults (lazily) to rng.default_seed(7): torch.manual_seed and the rank decide it"""
+        if self._sample_seed is None:
+            self._sample_seed = default_seed(7)
+        return self._sample_seed
+
+    @sample_seed.setter
+    def sample_seed(self, value):
+        self._sample_seed = None if value is None else int(value) & 0x7FFFFFFFFFFFFFFF
+
+    def sample_items(self, inputs, k=1):
+        """Stochastic recommendation: (values [B, k] fp32, ids [B, k] int64), k distinct items per session drawn in proportion
+        to softmax(scores) of an inference call (Gumbel top-k; values = the perturbed scores, descending).  `inputs` and the row
+        selection are an inference forward's; the draw runs through the fused sampling head (ops.item_sample: no [B, V] tensor)
+        over the serving image while prepare_serving stands, else over the fp32 table.  Every call advances `_sample_offset`;
+        (sample_seed, _sample_offset) replay a call (rng.get_rng_state / set_rng_state)."""
+        if self.pre is None:
+            raise RuntimeError("sample_items: the task is not built yet")
+        if isinstance(inputs, (tuple, list)):
+            inputs = inputs[0]
+        xr, inv_t = self._inference_rows(inputs.detach().float())
         image = self._serving_weights()
-        if image is not None:
-            # served from the half-precision image: fused head for top-k, [B, V] fp32 scores otherwise; topk_mode plays no part
-            return head.item_scores(xr, image, 1.0 / T) if top_k is None else head.item_topk(xr, image, 1.0 / T, top_k)
-        if top_k is not None and self.resolve_topk_mode(B, V) == "fused":
-            return head.item_topk(xr, W, 1.0 / T, top_k)
-        scores = head.item_scores(xr, W, 1.0 / T)
-        return scores if top_k is None else head.topk(scores, top_k)
+        W = image if image is not None else self.pre.module.output_weights.detach()
+        self._sample_offset += 1
+        ctr_hi = ops.dropout_ctr_hi(self._sample_offset, 255, ops.SITE_GUMBEL)
+        return ops.item_sample(xr, W, k, self.sample_seed, ctr_hi, inv_t)
 
     @staticmethod
     def _head_ops():

@@ -16,7 +16,7 @@ import os
 
 import torch
 
-_STATE_ATTRS = ("_seed", "_rng_offset", "_drop_offset", "_post_step", "_step")
+_STATE_ATTRS = ("_seed", "_rng_offset", "_drop_offset", "_post_step", "_step", "_sample_offset", "_sample_seed")
 _MASK63 = 0x7FFFFFFFFFFFFFFF
 
 
@@ -60,6 +60,8 @@ def get_rng_state(model):
         st = {a: getattr(m, a) for a in _STATE_ATTRS if isinstance(getattr(m, a, None), int)}
         if isinstance(m, SeedMixin):
             st["_seed"] = m.seed          # resolve the lazy default so that the resumed run replays it
+        if "_sample_offset" in st and hasattr(type(m), "sample_seed"):
+            st["_sample_seed"] = m.sample_seed          # the task's sampling key (NextItemPredictionTask.sample_items), likewise
         if st:
             out[name] = st
     return out

@@ -90,6 +90,34 @@ def _(x, weight, alpha, k):
     return x.new_empty((x.shape[0], k)), x.new_empty((x.shape[0], k), dtype=torch.int64)
 
 
+@torch.library.custom_op(f"{NS}::item_sample", mutates_args=())
+def item_sample(x: torch.Tensor, weight: torch.Tensor, alpha: float, k: int, seed: int, ctr_hi: int,
+                row0: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """k items per row drawn without replacement in proportion to softmax(x [N, D] @ weight[V, D]^T * alpha) (Gumbel top-k),
+    with their perturbed scores (descending), without the [N, V] scores: item_topk over score + g(seed, ctr_hi, row0 + row, item)
+    (masking.py:866-870 for k = 1; csrc/gumbel_noise.h).  weight fp32 or a 16-bit serving image"""
+    vals, idx = ops.item_sample(x, weight, k, seed, ctr_hi, alpha, row0)
+    return vals, idx
+
+
+@item_sample.register_fake
+def _(x, weight, alpha, k, seed, ctr_hi, row0):
+    return x.new_empty((x.shape[0], k)), x.new_empty((x.shape[0], k), dtype=torch.int64)
+
+
+@torch.library.custom_op(f"{NS}::gumbel_argmax", mutates_args=())
+def gumbel_argmax(scores: torch.Tensor, seed: int, ctr_hi: int, row0: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """one draw per row from softmax(scores [N, V]): (max of score + g(seed, ctr_hi, row0 + row, column), its column), in one pass
+    and without a perturbed copy (masking.py:866-870; csrc/item_sample.hip)"""
+    vals, idx = ops.gumbel_argmax(scores, seed, ctr_hi, row0)
+    return vals, idx
+
+
+@gumbel_argmax.register_fake
+def _(scores, seed, ctr_hi, row0):
+    return scores.new_empty((scores.shape[0],)), scores.new_empty((scores.shape[0],), dtype=torch.int64)
+
+
 @torch.library.custom_op(f"{NS}::item_eval", mutates_args=())
 def item_eval(x: torch.Tensor, weight: torch.Tensor, labels: torch.Tensor,
               alpha: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -711,7 +739,7 @@ def _am_backward(ctx, dy):
 apply_mask.register_autograd(_am_backward, setup_context=_am_setup)
 
 
-OPERATORS = ("gemm", "item_scores", "topk", "item_topk", "item_eval", "pack_item_table", "rank_of_target", "embedding_gather", "embedding_bag", "ragged_to_padded",
+OPERATORS = ("gemm", "item_scores", "topk", "item_topk", "item_sample", "gumbel_argmax", "item_eval", "pack_item_table", "rank_of_target", "embedding_gather", "embedding_bag", "ragged_to_padded",
              "xlnet_layer_infer", "xlnet_layer_fwd", "xlnet_layer_bwd", "mlm_targets", "seq_item_embedding",
              "seq_item_embedding_bwd", "xlnet_layer_grad", "gather_label_rows", "scatter_label_rows", "linear_softmax_ce",
              "linear_softmax_ce_bwd", "dropout", "pos_emb_dropout", "next_item_head", "next_item_head_bwd",
