@@ -692,7 +692,10 @@ int t4r_seq_sum_cols(void* stream, const float* wide, long ldw, int col, float* 
 /* ----------------------------------------------------------------------------------------
  * optimizer: fused Adam over a flat parameter buffer (torch.optim.Adam semantics, the optimizer
  * of the reference's Model.fit, torch/model/base.py:669-718).  grad is multiplied by grad_scale
- * first (1/world_size after the RCCL sum); zero_grad clears grad in the same pass. */
+ * first (1/world_size after the RCCL sum); zero_grad clears grad in the same pass.  step is 1-based; the four buffers are
+ * 16-byte aligned.  The bias corrections 1 - beta1^step and sqrt(1 - beta2^step) are computed in double on the host from the
+ * float betas and handed to the kernel rounded once to float (in fp32, 1 - beta2^step is a cancellation: 6.7e-6 relative at
+ * step 2); the element-wise arithmetic is fp32. */
 int t4r_adam_step(void* stream, float* param, float* grad, float* exp_avg, float* exp_avg_sq, long n,
                   int step, float lr, float beta1, float beta2, float eps, float weight_decay,
                   float grad_scale, int zero_grad);

@@ -17,7 +17,10 @@ from the device, tests/test_device_rng_oracle.py against the published Philox kn
   * dropout site masks: element idx keeps its value iff word (idx & 3) of block (ctr_lo = idx >> 2, ctr_hi) is
     >= ceil(p * 2^24) << 8, ctr_hi = (forward offset << 16) | (layer << 8) | site;
   * MLM training draws: bernoulli word x of block (offset + b*L + l, 0); j1 / j2 selectors words x / y of block
-    (offset + b, 1), index = min(n - 1, int(float32(word >> 8) * 2^-24 * n)).
+    (offset + b, 1), index = min(n - 1, int(float32(word >> 8) * 2^-24 * n));
+  * the sampled-softmax head's negatives (csrc/head.hip: log_uniform_sample_kernel): draw i takes words x, y of block
+    (i, ctr_hi), u = (x * 2^32 + y) * 2^-64 in double, id = min_id + clamp(floor(R^u) - 1, 0, R - 2) -- the one rule here
+    with floating-point in it (exp, log in double); tests/test_sampled_head_gpu.py compares it with the device draw.
 
 `xlnet_dropout_masks` / `gpt2_dropout_masks` / `bert_dropout_masks` lay the site masks of one training forward out for the three
 bodies; their site lists come from the HF sources, not from the HIP path's host code (tests/test_round6_gpu.py and
@@ -86,6 +89,26 @@ def _mlm_draws_np(seed, offset, B, L, p):
     r = philox4x32_10(seed, np.uint64(offset) + np.arange(B, dtype=np.uint64), 1)
     u = (r[:, :2] >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
     return bern, u[:, 0].copy(), u[:, 1].copy()
+
+
+def log_uniform_pow(seed, ctr_hi, n, min_id, max_id):
+    """float64 [n]: R^u of draw i, u = (x * 2^32 + y) * 2^-64 from words x, y of block (i, ctr_hi), R = max_id - min_id + 1.
+    The draw is its floor; a value within an ulp-class distance of an integer is a draw the device's exp may round the
+    other way (tests/test_sampled_head_gpu.py counts those)."""
+    R = int(max_id) - int(min_id) + 1
+    w = philox4x32_10(seed, np.arange(int(n), dtype=np.uint64), ctr_hi)
+    u = (w[:, 0].astype(np.float64) * 4294967296.0 + w[:, 1].astype(np.float64)) * (1.0 / 18446744073709551616.0)
+    return np.exp(u * np.log(np.float64(R)))
+
+
+def log_uniform_draws(seed, ctr_hi, n, min_id, max_id):
+    """int64 [n]: the ids t4r_log_uniform_sample draws at stream position ctr_hi (csrc/head.hip: the closed-form inverse CDF
+    of LogUniformSampler.dist): j = clamp(floor(R^u) - 1, 0, R - 2), id = min_id + j -- ids in [min_id, max_id)."""
+    R = int(max_id) - int(min_id) + 1
+    if R < 2:
+        raise ValueError("log_uniform_draws: need at least two ids")
+    j = np.floor(log_uniform_pow(seed, ctr_hi, n, min_id, max_id)).astype(np.int64) - 1
+    return int(min_id) + np.clip(j, 0, R - 2)
 
 
 # ---------------------------------------------------------------------------------------------- C form

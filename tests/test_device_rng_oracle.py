@@ -92,6 +92,40 @@ def test_mlm_targets_from_device_draws_follow_the_reference_rule():
     assert torch.equal(labels, torch.where(mask, ids, torch.zeros_like(ids)))
 
 
+def test_log_uniform_draws_follow_the_reference_distribution():
+    """log_uniform_draws restates the device's closed-form draw; here it is held to LogUniformSampler's distribution
+    (O.log_uniform_dist) by itself: bin masses of 400 k draws within 5 sigma (the rule of tests/test_kernels_gpu.py:
+    test_log_uniform_device_sampler_matches_the_reference_distribution), the range, R = 2, the prefix property."""
+    V, n = 100_001, 400_000
+    for min_id in (0, 1, 5):
+        ids = torch.from_numpy(R.log_uniform_draws(1234, 7, n, min_id, V))
+        assert ids.dtype == torch.int64 and ids.shape == (n,)
+        assert int(ids.min()) >= min_id and int(ids.max()) < V
+        dist = O.log_uniform_dist(V, min_id)
+        assert dist.numel() == V and float(dist[:min_id].sum()) == 0.0
+        cdf = torch.cat([torch.zeros(1, dtype=torch.float64), dist.double().cumsum(0)])
+        edges = torch.unique(torch.logspace(0, 5, 26).long().clamp_(min_id, V))
+        for lo, hi in zip(edges[:-1].tolist(), edges[1:].tolist()):
+            want = float(cdf[hi] - cdf[lo]) * n
+            got = int(((ids >= lo) & (ids < hi)).sum())
+            assert abs(got - want) < 5 * (want ** 0.5) + 5, (min_id, lo, hi, got, want)
+    # the two smallest ranges: R = 2 has one id; R = 3 has two with masses ln 2 / ln 3 and 1 - ln 2 / ln 3
+    for min_id in (0, 1, 5):
+        assert np.array_equal(R.log_uniform_draws(99, 3, 4099, min_id, min_id + 1), np.full(4099, min_id))
+        two = R.log_uniform_draws(99, 3, 40_000, min_id, min_id + 2)
+        assert set(np.unique(two).tolist()) == {min_id, min_id + 1}
+        want = 40_000 * np.log(2.0) / np.log(3.0)
+        assert abs(int((two == min_id).sum()) - want) < 5 * (want ** 0.5) + 5
+    with pytest.raises(ValueError):
+        R.log_uniform_draws(99, 3, 4, 5, 5)
+    # draw i depends on (seed, position, i) only; other seeds / positions are other streams; min_id only shifts
+    a = R.log_uniform_draws(5, 9, 1000, 1, V)
+    assert np.array_equal(a[:37], R.log_uniform_draws(5, 9, 37, 1, V))
+    assert not np.array_equal(a, R.log_uniform_draws(5, 10, 1000, 1, V))
+    assert not np.array_equal(a, R.log_uniform_draws(6, 9, 1000, 1, V))
+    assert np.array_equal(a + 4, R.log_uniform_draws(5, 9, 1000, 5, V + 4))
+
+
 def test_mask_dictionary_shapes():
     m = R.xlnet_dropout_masks(3, 5, 8, 2, 2, 0.3, seed=1, offset=1)
     assert m["input"].shape == (3, 5, 8) and m["pos"].shape == (3, 10, 8) and m["final"].shape == (3, 5, 8)

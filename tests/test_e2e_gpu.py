@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import device_rng as R
 import golden_utils as gu
 import t4r_oracle as O
 
@@ -740,7 +741,8 @@ def _gpt2_oracle_params(sd):
 def test_c4_full_size_step_vs_oracle():
     """BASELINE.json configs[3] at FULL size on one GPU's share: GPT-2 d_model 256, 6 layers, 1 M items, seq 50,
     batch 1024, causal LM, sampled softmax (100 negatives, log-uniform), tied weights.  One training step (dropout 0)
-    on the HIP path vs the CPU oracle with the same negatives: loss, labels, table gradient, a layer gradient."""
+    on the HIP path vs the CPU oracle with the negatives the device sampler drew, restated on the CPU (device_rng.
+    log_uniform_draws): loss, labels, table gradient, a layer gradient."""
     import transformers4rec_amd as tr
 
     torch.manual_seed(0)
@@ -754,11 +756,12 @@ def test_c4_full_size_step_vs_oracle():
     model.to(DEV)
     data = tr.random_data_from_schema(schema, B, L, seed=21)
     sampler = model.prediction_task.pre.module.sampler
-    torch.manual_seed(3)
-    neg = sampler.sample(torch.ones(4, dtype=torch.long, device=DEV))
-    sampler.sample = lambda labels: neg
+    sampler.seed = 3
     out = model({k: v.to(DEV) for k, v in data.items()}, training=True)
     out["loss"].backward()
+    # the negatives the device drew, restated on the CPU (oracle/device_rng.py): the sampler's first call, unique, truncated
+    assert sampler._step == 1 and (sampler.min_id, sampler.max_id, sampler.n_sample) == (1, V + 1, 200)
+    neg = torch.from_numpy(np.unique(R.log_uniform_draws(sampler.seed, R.dropout_ctr_hi(1, 0xFC, 0), 200, 1, V + 1))[:100])
     ids = data["item_id"]
     mask, labels = O.clm_targets(ids, True, False)
     m = model.input_features.masking

@@ -583,6 +583,21 @@ extern "C" int t4r_add_pos_bwd(void* stream, const float* dy, float* d_pos, int 
 //   g = grad (+ wd * p) ; m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2
 //   p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 // grad_scale multiplies grad first (1/world_size for the DP mean).  Optionally zeroes the grad.
+// The two bias corrections 1 - b1^t and sqrt(1 - b2^t) are computed in DOUBLE on the host (from the float betas the ABI
+// takes) and passed to the kernel rounded once to float: in fp32 `1.f - powf(b2, t)` is a cancellation of a rounded power --
+// 6.7e-6 relative at t = 2, which put p tens of fp32 roundings away from an exact Adam step during the first steps
+// (tests/test_adam_gpu.py counts them).
+// One element's step.  Every multiply-add is written out as the fmaf it is meant to be: left to the compiler's contraction, the
+// two instantiations of the kernel (and its float4 body and scalar tail) fused different pairs and rounded m, v and p differently
+// -- the two entry points disagreed in the last bit from the second step on (tests/test_adam_gpu.py holds them to one arithmetic).
+__device__ __forceinline__ void adam_element(float& p, float g, float& m, float& v, float step_size, float b1, float b2,
+                                             float eps, float wd, float bc2_sqrt, float grad_scale) {
+    const float gr = fmaf(wd, p, g * grad_scale);
+    m = fmaf(b1, m, (1.f - b1) * gr);
+    v = fmaf(b2, v, ((1.f - b2) * gr) * gr);
+    const float denom = sqrtf(v) / bc2_sqrt + eps;
+    p = fmaf(-step_size, m / denom, p);
+}
 // AMAX (round 6): the launch also leaves, per workgroup, the largest |p| AFTER the update among the elements [amax_lo, amax_hi)
 // in amax_part[blockIdx.x] -- the tied item table's maximum, which the next step's head needs to position its fp16 images
 // (csrc/head_split.hip: split_w_images_kernel reduces the <= 1024 partials) and used to get from a memset + a 21 us pass over
@@ -595,6 +610,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
                                                     float grad_scale, int zero_grad, long amax_lo, long amax_hi,
                                                     float* __restrict__ amax_part) {
     float mx = 0.f;
+    const float step_size = lr / bc1;
     const long stride = (long)gridDim.x * blockDim.x * 4;
     for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
         if (i + 4 <= n) {
@@ -605,11 +621,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
             float* P = &pp.x; float* G = &gg.x; float* M = &mm.x; float* V = &vv.x;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                float gr = G[e] * grad_scale + wd * P[e];
-                M[e] = b1 * M[e] + (1.f - b1) * gr;
-                V[e] = b2 * V[e] + (1.f - b2) * gr * gr;
-                const float denom = sqrtf(V[e]) / bc2_sqrt + eps;
-                P[e] -= (lr / bc1) * (M[e] / denom);
+                adam_element(P[e], G[e], M[e], V[e], step_size, b1, b2, eps, wd, bc2_sqrt, grad_scale);
                 if (AMAX && i + e >= amax_lo && i + e < amax_hi) mx = fmaxf(mx, fabsf(P[e]));
             }
             *reinterpret_cast<float4*>(p + i) = pp;
@@ -618,11 +630,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
             if (zero_grad) *reinterpret_cast<float4*>(g + i) = make_float4(0.f, 0.f, 0.f, 0.f);
         } else {
             for (long j = i; j < n; ++j) {
-                float gr = g[j] * grad_scale + wd * p[j];
-                m[j] = b1 * m[j] + (1.f - b1) * gr;
-                v[j] = b2 * v[j] + (1.f - b2) * gr * gr;
-                const float denom = sqrtf(v[j]) / bc2_sqrt + eps;
-                p[j] -= (lr / bc1) * (m[j] / denom);
+                adam_element(p[j], g[j], m[j], v[j], step_size, b1, b2, eps, wd, bc2_sqrt, grad_scale);
                 if (AMAX && j >= amax_lo && j < amax_hi) mx = fmaxf(mx, fabsf(p[j]));
                 if (zero_grad) g[j] = 0.f;
             }
@@ -644,8 +652,8 @@ extern "C" int t4r_adam_step(void* stream, float* param, float* grad, float* exp
     T4R_CHECK_ARG(step >= 1, "adam: step is 1-based");
     T4R_CHECK_ARG(((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) % 16 == 0,
                   "adam: buffers must be 16-byte aligned");
-    const float bc1 = 1.f - powf(beta1, (float)step);
-    const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
+    const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+    const float bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
     long blocks = (n / 4 + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
@@ -667,8 +675,8 @@ extern "C" int t4r_adam_step_amax(void* stream, float* param, float* grad, float
         t4r_set_error("adam_step_amax: buffers must be 16-byte aligned, the range inside the buffer, amax_part non-null");
         return -1;
     }
-    const float bc1 = 1.f - powf(beta1, (float)step);
-    const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
+    const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+    const float bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
     long blocks = (n / 4 + 255) / 256;
     if (blocks > 512) blocks = 512;      // (the consumer reduces the partials in every workgroup: 512 x 4 bytes)
     if (blocks < 1) blocks = 1;
