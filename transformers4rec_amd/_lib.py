@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("T4R_HIP_LIB") or os.path.join(_HERE, "lib", "libt4r_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip.h")
 SAMPLING_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_sampling.h")
+FILTER_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_filter.h")
 
 _P, _I, _L, _F, _Q = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_ulonglong
 _C = {"p": _P, "i": _I, "l": _L, "f": _F, "Q": _Q}
@@ -160,6 +161,19 @@ _SIGS_SAMPLING = {
     "t4r_item_sample_h16": ("i", "p" + "iiif" + "pl" + "pl" + "i" + "i" + "pp" + "pl" + "p" + "lQQ"),
 }
 
+# the third header, include/t4r_hip_filter.h (tests/test_item_filter_cpu.py checks this table against it); the filter tail is
+# allow_bits, excl, n_excl, ld_excl
+_FILT = "ppil"
+_SIGS_FILTER = {
+    "t4r_item_allow_words": ("l", "i"),
+    "t4r_item_allow_pack": ("i", "ppip"),
+    "t4r_item_mask_f32": ("i", "pp" + "iili" + _FILT),
+    "t4r_item_topk_filtered_f32": ("i", _SIGS["t4r_item_topk_f32"][1] + _FILT),
+    "t4r_item_topk_filtered_h16": ("i", _SIGS["t4r_item_topk_h16"][1] + _FILT),
+    "t4r_item_sample_filtered_f32": ("i", _SIGS_SAMPLING["t4r_item_sample_f32"][1] + _FILT),
+    "t4r_item_sample_filtered_h16": ("i", _SIGS_SAMPLING["t4r_item_sample_h16"][1] + _FILT),
+}
+
 _lib = None
 
 
@@ -183,6 +197,11 @@ def sampling_header_symbols():
     return _declared(SAMPLING_HEADER_PATH)
 
 
+def filter_header_symbols():
+    """Function names declared in include/t4r_hip_filter.h."""
+    return _declared(FILTER_HEADER_PATH)
+
+
 def load():
     """Loads the library and sets ctypes prototypes.  Raises if it is not built."""
     global _lib
@@ -193,7 +212,7 @@ def load():
             f"{LIB_PATH} not found: the HIP extension is not built "
             "(run `python -m transformers4rec_amd.build`). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (ret, args) in list(_SIGS.items()) + list(_SIGS_SAMPLING.items()):
+    for name, (ret, args) in list(_SIGS.items()) + list(_SIGS_SAMPLING.items()) + list(_SIGS_FILTER.items()):
         fn = getattr(lib, name)
         fn.restype = ctypes.c_char_p if ret == "s" else (None if ret == "v" else _C[ret])
         fn.argtypes = [_C[a] for a in args]

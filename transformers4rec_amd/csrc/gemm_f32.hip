@@ -24,6 +24,9 @@ static int launch_cfg(const GemmParams& p, int batch, hipStream_t stream) {
         return -1;
     }
     if (p.tk_thr) {
+        if (BM == 64 && BN == 64 && !TA && TB && p.splitk == 1 && p.tk_filtered)
+            return p.tk_noisy ? launch_feat<64, 64, BK, false, true, 56>(p, batch, stream)
+                              : launch_feat<64, 64, BK, false, true, 40>(p, batch, stream);
         if (BM == 64 && BN == 64 && !TA && TB && p.splitk == 1)
             return p.tk_noisy ? launch_feat<64, 64, BK, false, true, 24>(p, batch, stream)
                               : launch_feat<64, 64, BK, false, true, 8>(p, batch, stream);
@@ -361,7 +364,7 @@ struct SoftmaxGradA { const float* lse; const long* labels; const float* gout; i
 static thread_local const SoftmaxGradA* g_sg = nullptr;   // set only by t4r_gemm_softmax_grad_f32
 struct RankEpi { const float* thr; const long* label; int* count; };
 static thread_local const RankEpi* g_rank = nullptr;      // set only by t4r_rank_of_target_f32
-struct TopkEpi { const float* thr; long thr_ld; int* count; float* val; int* idx; int cap; const GumbelCfg* noise; };
+struct TopkEpi { const float* thr; long thr_ld; int* count; float* val; int* idx; int cap; const GumbelCfg* noise; const ItkFilter* filt; };
 
 // topk / force_fp32: the two products of the fused top-k head (end of this file); null / false everywhere else
 static int gemm_launch_impl(hipStream_t stream, int transA, int transB, int M, int N, int K, float alpha,
@@ -386,10 +389,12 @@ static int gemm_launch_impl(hipStream_t stream, int transA, int transB, int M, i
     if (g_rank) { p.rk_thr = g_rank->thr; p.rk_label = g_rank->label; p.rk_count = g_rank->count; }
     p.tk_thr = nullptr; p.tk_thr_ld = 0; p.tk_count = nullptr; p.tk_val = nullptr; p.tk_idx = nullptr; p.tk_cap = 0;
     p.tk_noisy = 0; p.tk_noise = GumbelCfg{0, 0, 0};
+    p.tk_filtered = 0; p.tk_filt = ItkFilter{nullptr, nullptr, 0, 0};
     if (topk) {
         p.tk_thr = topk->thr; p.tk_thr_ld = topk->thr_ld; p.tk_count = topk->count;
         p.tk_val = topk->val; p.tk_idx = topk->idx; p.tk_cap = topk->cap;
         if (topk->noise) { p.tk_noisy = 1; p.tk_noise = *topk->noise; }
+        if (topk->filt) { p.tk_filtered = 1; p.tk_filt = *topk->filt; }
     }
     if (g_sg) {
         p.sg_lse = g_sg->lse; p.sg_labels = g_sg->labels; p.sg_gout = g_sg->gout;
@@ -494,8 +499,16 @@ int t4r_gemm_fp32_nt_launch(hipStream_t stream, int M, int N, int K, float alpha
 int t4r_gemm_topk_collect_launch(hipStream_t stream, int n_rows, int V, int D, float alpha, const float* X, long ldx,
                                  const float* W, long ldw, const float* thr, long thr_ld, int* count, float* cand_val,
                                  int* cand_idx, int cap, const GumbelCfg* noise) {
-    const TopkEpi te{thr, thr_ld, count, cand_val, cand_idx, cap, noise};
+    const TopkEpi te{thr, thr_ld, count, cand_val, cand_idx, cap, noise, nullptr};
     // C is never written by the collect epilogue; a non-null dummy keeps the argument check happy
+    return gemm_launch_impl(stream, 0, 1, n_rows, V, D, alpha, X, ldx, W, ldw, cand_val, V, nullptr, EPI_NONE, nullptr, 0, 1, 0,
+                            1, 0, 0, 0, nullptr, &te, true);
+}
+// ... and under an item filter (item_filter.h): only allowed items are appended
+int t4r_gemm_topk_collect_filtered_launch(hipStream_t stream, int n_rows, int V, int D, float alpha, const float* X, long ldx,
+                                          const float* W, long ldw, const float* thr, long thr_ld, int* count, float* cand_val,
+                                          int* cand_idx, int cap, const GumbelCfg* noise, const ItkFilter* filt) {
+    const TopkEpi te{thr, thr_ld, count, cand_val, cand_idx, cap, noise, filt};
     return gemm_launch_impl(stream, 0, 1, n_rows, V, D, alpha, X, ldx, W, ldw, cand_val, V, nullptr, EPI_NONE, nullptr, 0, 1, 0,
                             1, 0, 0, 0, nullptr, &te, true);
 }

@@ -94,6 +94,10 @@ struct GemmParams {
     // (gumbel_noise.h); read by that instantiation only
     int tk_noisy;
     GumbelCfg tk_noise;
+    // FEAT bit 5 on top of bit 3 (filtered heads, include/t4r_hip_filter.h): only allowed items are collected (item_filter.h);
+    // read by those instantiations only
+    int tk_filtered;
+    ItkFilter tk_filt;
 };
 
 // softmax-gradient transform of four consecutive columns col0..col0+3 of one logits row.
@@ -138,7 +142,8 @@ __device__ __forceinline__ float4 mask4(float4 v, int valid) {   // keep the fir
 }
 
 // FEAT bit 0: softmax-gradient A operand ; bit 1: dropout in the epilogue ; bit 2: rank-of-target epilogue ; bit 3: top-k
-// collect epilogue ; bit 4 (with bit 3): Gumbel noise on the collected score.  Compile-time so that the
+// collect epilogue ; bit 4 (with bit 3): Gumbel noise on the collected score ; bit 5 (with bit 3): item filter on the collected
+// items.  Compile-time so that the
 // plain GEMM does not carry the Philox / exp code (measured: +12 % step time when it did).
 // VEC: both operands can be staged with 16-byte loads (decided by the host from pointers / pitches);
 // the scalar-load variant is its own instantiation so that it does not set the register budget.
@@ -224,8 +229,9 @@ constexpr size_t gemm_lds_bytes() {
 template <int BM, int BN, int BK, bool TA, bool TB, int FEAT, bool VEC, int PREC = 0>
 __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
     constexpr bool SG = (FEAT & 1) != 0, EDROP = (FEAT & 2) != 0, RANK = (FEAT & 4) != 0, TOPK = (FEAT & 8) != 0,
-                   NOISY = (FEAT & 16) != 0;
+                   NOISY = (FEAT & 16) != 0, FILT = (FEAT & 32) != 0;
     static_assert(!NOISY || TOPK, "the noise is the collect epilogue's");
+    static_assert(!FILT || TOPK, "the item filter is the collect epilogue's");
     constexpr int WM = BM / 64, WN = BN / 64;          // MFMA tiles per wave per dim
     constexpr bool A_MK = !TA, B_MK = TB;              // operand image is S[m][k] (k contiguous)
     // S[m][k] images: row pitch BK (no padding) with the 16-byte chunk index XOR-swizzled by the row,
@@ -715,6 +721,35 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
                     const unsigned long long m = __ballot(beats);
                     const int cnt = __popc((unsigned)(khalf ? (m >> 32) : (m & 0xffffffffull)));
                     if ((lane & 31) == 0 && row < p.M && cnt) atomicAdd(p.rk_count + row, cnt);
+                }
+            }
+        }
+        return;
+    }
+    if constexpr (TOPK && FILT) {
+        // the TOPK / NOISY epilogues below under an item filter.  A lane's column is fixed over the 16 elements of a block and
+        // the 32 lanes of a half hold the 32 columns from a multiple of 32: one allow word per lane and block, the half's.
+#pragma unroll
+        for (int i = 0; i < WM; ++i) {
+#pragma unroll
+            for (int j = 0; j < WN; ++j) {
+                const int col = n0 + wn * (BN / 2) + j * 32 + (lane & 31);
+                const bool ok = col < p.N && ((itk_allow_word(p.tk_filt.allow_bits, col & ~31) >> (lane & 31)) & 1u);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int rowb = m0 + wm * (BM / 2) + i * 32 + 8 * q + 4 * khalf;
+                    float g[4];
+                    if constexpr (NOISY) gumbel_quad(p.tk_noise, rowb, (uint32_t)col, g);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int row = rowb + e;
+                        const int rr = min(row, p.M - 1);
+                        float v = alpha * acc[i][j][4 * q + e];
+                        if constexpr (NOISY) v = gumbel_perturb(v, g[e]);
+                        const float t = p.tk_thr[(long)rr * p.tk_thr_ld];
+                        itk_collect_filtered(ok && row < p.M && v >= t, v, col, row, lane, p.tk_count, p.tk_val, p.tk_idx, p.tk_cap,
+                                             p.tk_filt);
+                    }
                 }
             }
         }

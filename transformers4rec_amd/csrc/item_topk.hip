@@ -33,6 +33,9 @@ int t4r_gemm_fp32_nt_launch(hipStream_t stream, int M, int N, int K, float alpha
 int t4r_gemm_topk_collect_launch(hipStream_t stream, int n_rows, int V, int D, float alpha, const float* X, long ldx,
                                  const float* W, long ldw, const float* thr, long thr_ld, int* count, float* cand_val,
                                  int* cand_idx, int cap, const GumbelCfg* noise);
+int t4r_gemm_topk_collect_filtered_launch(hipStream_t stream, int n_rows, int V, int D, float alpha, const float* X, long ldx,
+                                          const float* W, long ldw, const float* thr, long thr_ld, int* count, float* cand_val,
+                                          int* cand_idx, int cap, const GumbelCfg* noise, const ItkFilter* filt);
 
 namespace {
 
@@ -119,7 +122,10 @@ struct Itk32Head {
         return t4r_gemm_fp32_nt_launch(st, n_rows, pl.M, D, alpha, X, ldx, wsamp, D, S, pl.ldS);
     }
     int collect(hipStream_t st, const float* thr, long thr_ld, int* count, float* cand_val, int* cand_idx, int cap,
-                const GumbelCfg* noise = nullptr) const {
+                const GumbelCfg* noise = nullptr, const ItkFilter* filt = nullptr) const {
+        if (filt)
+            return t4r_gemm_topk_collect_filtered_launch(st, n_rows, V, D, alpha, X, ldx, W, ldw, thr, thr_ld, count, cand_val,
+                                                         cand_idx, cap, noise, filt);
         return t4r_gemm_topk_collect_launch(st, n_rows, V, D, alpha, X, ldx, W, ldw, thr, thr_ld, count, cand_val, cand_idx, cap,
                                             noise);
     }
@@ -180,4 +186,45 @@ extern "C" int t4r_item_sample_f32(void* stream, int n_rows, int V, int D, float
     const Itk32Head base = {n_rows, V, D, alpha, X, ldx, W, ldw, (float*)((char*)workspace + pl.off_wsamp)};
     ItkNoisyHead<Itk32Head> head = {base, {seed, ctr_hi, row0}, n_rows, V};
     return itk_run("item_sample", (hipStream_t)stream, pl, workspace, n_rows, V, k, out_val, out_idx, host_stats, head);
+}
+
+// The two entries above under an item filter (include/t4r_hip_filter.h): noise null = t4r_item_topk_filtered_f32
+static int itk32_filtered(const char* name, void* stream, int n_rows, int V, int D, float alpha, const float* X, long ldx,
+                          const float* W, long ldw, int k, float* out_val, long* out_idx, void* workspace, long ws_bytes,
+                          long* host_stats, const GumbelCfg* noise, const ItkFilter& filt) {
+    auto bad = [&](const char* what) {
+        t4r_set_error((std::string(name) + ": " + what).c_str());
+        return -1;
+    };
+    if (n_rows == 0) return 0;
+    if (!(n_rows > 0 && V > 0 && D > 0 && X && W && out_val && out_idx)) return bad("bad arguments");
+    if (!(k >= 1 && k <= ITK_MAX_K && k <= V)) return bad("1 <= k <= min(256, V)");
+    if (!(ldx >= D && ldw >= D)) return bad("row pitch below D");
+    if (noise && noise->row0 < 0) return bad("row0 must not be negative");
+    if (t4r_item_filter_check(name, filt.allow_bits, filt.excl, filt.n_excl, filt.ld_excl)) return -1;
+    const Plan pl = make_plan(n_rows, V, k, (size_t)D * 4, 0);
+    if (!(workspace && ws_bytes >= (long)pl.total && (uintptr_t)workspace % 16 == 0))
+        return bad("workspace too small (the unfiltered entry's ws_bytes) or not 16-byte aligned");
+    const Itk32Head base = {n_rows, V, D, alpha, X, ldx, W, ldw, (float*)((char*)workspace + pl.off_wsamp)};
+    if (!noise) return itk_run_filtered(name, (hipStream_t)stream, pl, workspace, n_rows, V, k, out_val, out_idx, host_stats, base, filt);
+    const ItkNoisyHead<Itk32Head> noisy = {base, *noise, n_rows, V};
+    return itk_run_filtered(name, (hipStream_t)stream, pl, workspace, n_rows, V, k, out_val, out_idx, host_stats, noisy, filt);
+}
+
+extern "C" int t4r_item_topk_filtered_f32(void* stream, int n_rows, int V, int D, float alpha, const float* X, long ldx,
+                                          const float* W, long ldw, int k, float* out_val, long* out_idx, void* workspace,
+                                          long ws_bytes, long* host_stats, const unsigned* allow_bits, const long* excl,
+                                          int n_excl, long ld_excl) {
+    return itk32_filtered("item_topk_filtered", stream, n_rows, V, D, alpha, X, ldx, W, ldw, k, out_val, out_idx, workspace,
+                          ws_bytes, host_stats, nullptr, ItkFilter{allow_bits, excl, n_excl, ld_excl});
+}
+
+extern "C" int t4r_item_sample_filtered_f32(void* stream, int n_rows, int V, int D, float alpha, const float* X, long ldx,
+                                            const float* W, long ldw, int k, float* out_val, long* out_idx, void* workspace,
+                                            long ws_bytes, long* host_stats, long row0, unsigned long long seed,
+                                            unsigned long long ctr_hi, const unsigned* allow_bits, const long* excl, int n_excl,
+                                            long ld_excl) {
+    const GumbelCfg noise = {seed, ctr_hi, row0};
+    return itk32_filtered("item_sample_filtered", stream, n_rows, V, D, alpha, X, ldx, W, ldw, k, out_val, out_idx, workspace,
+                          ws_bytes, host_stats, &noise, ItkFilter{allow_bits, excl, n_excl, ld_excl});
 }

@@ -29,6 +29,8 @@
 //                             i * stride): no gathered copy of the sample.
 //                             EPI 2 is EPI 1 over fp32(alpha * acc + g(row, item)): the collect pass of the sampling head
 //                             (t4r_item_sample_h16; gumbel_noise.h, ItkNoisyHead in item_topk_plan.h).
+//                             EPI 3 / 4 are EPI 1 / 2 under an item filter (include/t4r_hip_filter.h, item_filter.h): the allow
+//                             bit is folded into the compare, the row's exclusion list is searched behind a non-empty ballot.
 //                             The tile load and the k loop live in item_h16_tile.h, shared with item_eval_h16.hip, as do the
 //                             image's argument contract and the dtype dispatch.
 //   select / threshold top-k  itk_select_kernel (item_topk.hip) and t4r_topk, unchanged; the plan and the four-step driver
@@ -90,6 +92,7 @@ struct Itk16Params {
     int* cand_idx;
     int cap;
     GumbelCfg noise;                // EPI 2: EPI 1 over fp32(v + g(row, item)) (gumbel_noise.h)
+    ItkFilter filt;                 // EPI 3 / 4: EPI 1 / 2 over the allowed items only (item_filter.h)
 };
 
 template <int DT, int EPI>
@@ -119,6 +122,25 @@ __global__ __launch_bounds__(256) void itk16_kernel(Itk16Params p) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const long col = item0 + j * 32 + r;
+            if (EPI >= 3) {
+                // the collect pass runs at stride 1: col is the item.  A lane's column is fixed over the 16 elements and the 32
+                // lanes of a half hold the 32 columns from item0 + 32 j: one allow word per lane and block, the half's.
+                const bool ok = col < p.n_items && ((itk_allow_word(p.filt.allow_bits, item0 + j * 32) >> r) & 1u);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    float g[4];
+                    if (EPI == 4) gumbel_quad(p.noise, rb + itk16_acc_row(4 * q, h), (uint32_t)col, g);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int row = rb + itk16_acc_row(4 * q + e, h);
+                        float v = alpha * acc[j][4 * q + e];
+                        if (EPI == 4) v = gumbel_perturb(v, g[e]);
+                        itk_collect_filtered(ok && row < p.n_rows && v >= thr[4 * q + e], v, (int)col, row, lane, p.count,
+                                             p.cand_val, p.cand_idx, p.cap, p.filt);
+                    }
+                }
+                continue;
+            }
             if (EPI == 2) {
                 // elements 4 q .. 4 q + 3 of a lane are four consecutive rows of its column: one Philox block
 #pragma unroll
@@ -150,7 +172,7 @@ __global__ __launch_bounds__(256) void itk16_kernel(Itk16Params p) {
     }
 }
 
-T4rLdsAttr g_lds_attr[2][3];
+T4rLdsAttr g_lds_attr[2][5];
 
 template <int DT, int EPI>
 int launch_t(hipStream_t st, const Itk16Params& p) {
@@ -166,6 +188,7 @@ int launch_t(hipStream_t st, const Itk16Params& p) {
 int launch(hipStream_t st, int dtype, int epi, const Itk16Params& p) {
     return itk16_dispatch(dtype, [&](auto dt) {
         constexpr int DT = decltype(dt)::value;
+        if (epi >= 3) return epi == 4 ? launch_t<DT, 4>(st, p) : launch_t<DT, 3>(st, p);
         return epi == 2 ? launch_t<DT, 2>(st, p) : (epi ? launch_t<DT, 1>(st, p) : launch_t<DT, 0>(st, p));
     });
 }
@@ -181,11 +204,12 @@ struct Itk16Head {
         return launch(st, dtype, 0, q);
     }
     int collect(hipStream_t st, const float* thr, long thr_ld, int* count, float* cand_val, int* cand_idx, int cap,
-                const GumbelCfg* noise = nullptr) const {
+                const GumbelCfg* noise = nullptr, const ItkFilter* filt = nullptr) const {
         Itk16Params q = p;
         q.thr = thr; q.thr_ld = thr_ld; q.count = count; q.cand_val = cand_val; q.cand_idx = cand_idx; q.cap = cap;
         if (noise) q.noise = *noise;
-        return launch(st, dtype, noise ? 2 : 1, q);
+        if (filt) q.filt = *filt;
+        return launch(st, dtype, (noise ? 2 : 1) + (filt ? 2 : 0), q);
     }
     int scores(hipStream_t st, int r0, int n, float* C, long ldv) const {
         Itk16Params q = p;
@@ -299,4 +323,57 @@ extern "C" int t4r_item_sample_h16(void* stream, int n_rows, int V, int D, float
     p.n_rows = n_rows; p.n_items = V; p.ldp = (int)kp; p.x16 = x16; p.img = (const uint16_t*)image; p.ldi = ldp; p.stride = 1;
     p.alpha = alpha;
     return itk_run("item_sample_h16", st, pl, workspace, n_rows, V, k, out_val, out_idx, host_stats, head);
+}
+
+// The two heads above under an item filter (include/t4r_hip_filter.h): noise null = t4r_item_topk_filtered_h16
+static int itk16_filtered(const char* name, void* stream, int n_rows, int V, int D, float alpha, const float* X, long ldx,
+                          const void* image, long ldp, int dtype, int k, float* out_val, long* out_idx, void* workspace,
+                          long ws_bytes, long* host_stats, const GumbelCfg* noise, const ItkFilter& filt) {
+    auto bad = [&](const char* what) {
+        t4r_set_error((std::string(name) + ": " + what).c_str());
+        return -1;
+    };
+    if (n_rows == 0) return 0;
+    if (!(n_rows > 0 && V > 0 && D > 0 && X && image && out_val && out_idx)) return bad("bad arguments");
+    if (!itk16_supported(D)) return bad("1 <= D <= 512 (t4r_item_topk_h16_supported)");
+    if (!(k >= 1 && k <= ITK_MAX_K && k <= V)) return bad("1 <= k <= min(256, V)");
+    if (ldx < D) return bad("row pitch below D");
+    if (noise && noise->row0 < 0) return bad("row0 must not be negative");
+    if (dtype != 2 && dtype != 3) return bad("dtype is 2 (bf16) or 3 (fp16), the codes of T4R_GEMM_PREC");
+    if (!(ldp >= itk16_image_ld(D) && ldp % 8 == 0 && (uintptr_t)image % 16 == 0))
+        return bad("image rows must be 16-byte aligned with pitch >= t4r_item_table_image_ld(D)");
+    if (t4r_item_filter_check(name, filt.allow_bits, filt.excl, filt.n_excl, filt.ld_excl)) return -1;
+    const long kp = itk16_image_ld(D);
+    const Plan pl = make_plan(n_rows, V, k, 0, (size_t)n_rows * kp * 2);
+    if (!(workspace && ws_bytes >= (long)pl.total && (uintptr_t)workspace % 16 == 0))
+        return bad("workspace too small (the unfiltered entry's ws_bytes) or not 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    uint16_t* x16 = (uint16_t*)((char*)workspace + pl.off_x);
+    const int rc = t4r_itk16_round_rows(st, dtype, X, ldx, n_rows, D, x16, kp);
+    if (rc) return rc;
+    Itk16Head base = {dtype, {}};
+    Itk16Params& p = base.p;
+    p.n_rows = n_rows; p.n_items = V; p.ldp = (int)kp; p.x16 = x16; p.img = (const uint16_t*)image; p.ldi = ldp; p.stride = 1;
+    p.alpha = alpha;
+    if (!noise) return itk_run_filtered(name, st, pl, workspace, n_rows, V, k, out_val, out_idx, host_stats, base, filt);
+    const ItkNoisyHead<Itk16Head> noisy = {base, *noise, n_rows, V};
+    return itk_run_filtered(name, st, pl, workspace, n_rows, V, k, out_val, out_idx, host_stats, noisy, filt);
+}
+
+extern "C" int t4r_item_topk_filtered_h16(void* stream, int n_rows, int V, int D, float alpha, const float* X, long ldx,
+                                          const void* image, long ldp, int dtype, int k, float* out_val, long* out_idx,
+                                          void* workspace, long ws_bytes, long* host_stats, const unsigned* allow_bits,
+                                          const long* excl, int n_excl, long ld_excl) {
+    return itk16_filtered("item_topk_filtered_h16", stream, n_rows, V, D, alpha, X, ldx, image, ldp, dtype, k, out_val, out_idx,
+                          workspace, ws_bytes, host_stats, nullptr, ItkFilter{allow_bits, excl, n_excl, ld_excl});
+}
+
+extern "C" int t4r_item_sample_filtered_h16(void* stream, int n_rows, int V, int D, float alpha, const float* X, long ldx,
+                                            const void* image, long ldp, int dtype, int k, float* out_val, long* out_idx,
+                                            void* workspace, long ws_bytes, long* host_stats, long row0,
+                                            unsigned long long seed, unsigned long long ctr_hi, const unsigned* allow_bits,
+                                            const long* excl, int n_excl, long ld_excl) {
+    const GumbelCfg noise = {seed, ctr_hi, row0};
+    return itk16_filtered("item_sample_filtered_h16", stream, n_rows, V, D, alpha, X, ldx, image, ldp, dtype, k, out_val, out_idx,
+                          workspace, ws_bytes, host_stats, &noise, ItkFilter{allow_bits, excl, n_excl, ld_excl});
 }

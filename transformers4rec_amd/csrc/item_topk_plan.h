@@ -4,6 +4,7 @@
 #pragma once
 #include "t4r_common.h"
 #include "gumbel_noise.h"
+#include "item_filter.h"
 #include <algorithm>
 #include <math.h>
 #include <string>
@@ -159,9 +160,54 @@ struct ItkNoisyHead {
     int collect(hipStream_t st, const float* thr, long thr_ld, int* count, float* cand_val, int* cand_idx, int cap) const {
         return head.collect(st, thr, thr_ld, count, cand_val, cand_idx, cap, &noise);
     }
+    // the signature a plain head's collect has, for ItkFilteredHead: the noise is this head's own, the argument is ignored
+    int collect(hipStream_t st, const float* thr, long thr_ld, int* count, float* cand_val, int* cand_idx, int cap,
+                const GumbelCfg*, const ItkFilter* filt) const {
+        return head.collect(st, thr, thr_ld, count, cand_val, cand_idx, cap, &noise, filt);
+    }
     int scores(hipStream_t st, int r0, int n, float* C, long ldv) const {
         const int rc = head.scores(st, r0, n, C, ldv);
         if (rc) return rc;
         return t4r_gumbel_add_launch(st, C, n, V, ldv, noise.row0 + r0, 1, noise.seed, noise.ctr_hi);
     }
 };
+
+// The filtered form of a head (Itk32Head, Itk16Head or their noisy forms): every score of (row, item) becomes the score where
+// allowed(row, item), -inf otherwise (item_filter.h) -- again a pure function of (row, item), so itk_run's four steps stay exact:
+// a finite threshold from the masked sample means k allowed sampled items with those bits exist in the full pass; a -inf
+// threshold makes every allowed item a candidate; a row with fewer than k allowed items has fewer than k candidates and takes
+// the materialised path like any row the select kernel flags.  The materialised products are the head's own followed by the
+// mask; the collect pass tests the filter in its epilogue, so an excluded item never takes a slot of a list.
+template <class Head>
+struct ItkFilteredHead {
+    Head head;
+    ItkFilter filt;
+    int n_rows, V;
+
+    int sample(hipStream_t st, const Plan& pl, float* S) const {
+        const int rc = head.sample(st, pl, S);
+        if (rc) return rc;
+        return t4r_item_mask_launch(st, S, n_rows, pl.M, pl.ldS, pl.stride, filt);
+    }
+    int collect(hipStream_t st, const float* thr, long thr_ld, int* count, float* cand_val, int* cand_idx, int cap) const {
+        return head.collect(st, thr, thr_ld, count, cand_val, cand_idx, cap, nullptr, &filt);
+    }
+    int scores(hipStream_t st, int r0, int n, float* C, long ldv) const {
+        const int rc = head.scores(st, r0, n, C, ldv);
+        if (rc) return rc;
+        ItkFilter f = filt;
+        if (f.excl) f.excl += (long)r0 * f.ld_excl;
+        return t4r_item_mask_launch(st, C, n, V, ldv, 1, f);
+    }
+};
+
+// a filtered entry: itk_run over the filtered head, then the tail rule -- ids of -inf slots become -1 (t4r_topk's three paths
+// do not agree on them) -- as the call's last launch, after the overflow path
+template <class Head>
+static int itk_run_filtered(const char* name, hipStream_t st, const Plan& pl, void* workspace, int n_rows, int V, int k,
+                            float* out_val, long* out_idx, long* host_stats, const Head& base, const ItkFilter& filt) {
+    ItkFilteredHead<Head> head = {base, filt, n_rows, V};
+    const int rc = itk_run(name, st, pl, workspace, n_rows, V, k, out_val, out_idx, host_stats, head);
+    if (rc) return rc;
+    return t4r_itk_mark_empty_launch(st, out_val, out_idx, n_rows, k);
+}

@@ -521,7 +521,7 @@ class _HipTaskMixin:
         sh.masking = hm
         return sh.evaluate_batch(inputs)
 
-    def forward(self, inputs, targets=None, training=False, testing=False, top_k=None, **kwargs):
+    def forward(self, inputs, targets=None, training=False, testing=False, top_k=None, exclude_seen=False, **kwargs):
         sh = self.hip_shadow()
         hm = self.masking.__dict__.get("_t4r_hip_masking") if self.masking is not None else None
         if (training or testing) and (hm is None or hm.masked_targets is not self.masking.masked_targets):
@@ -533,7 +533,7 @@ class _HipTaskMixin:
         tm = self.__dict__.get("topk_mode")          # `task.topk_mode = "fused"` on the converted reference task
         if tm is not None and tm != sh.topk_mode:
             sh.set_topk_mode(tm)
-        return sh(inputs, targets=targets, training=training, testing=testing, top_k=top_k)
+        return sh(inputs, targets=targets, training=training, testing=testing, top_k=top_k, exclude_seen=exclude_seen)
 
 
 def make_dropin(tr):

@@ -33,7 +33,7 @@ class Head(nn.Module):
 
 class Model(nn.Module):
     def __init__(self, input_features, transformer_block, prediction_task, max_sequence_length: Optional[int] = None,
-                 top_k: Optional[int] = None):
+                 top_k: Optional[int] = None, exclude_seen: bool = False):
         super().__init__()
         body = _Body([input_features, transformer_block])
         hidden = transformer_block.transformer.config.hidden_size
@@ -41,6 +41,7 @@ class Model(nn.Module):
         self.heads = nn.ModuleList([Head(body, prediction_task)])
         self.max_sequence_length = max_sequence_length or getattr(input_features, "max_sequence_length", None)
         self.top_k = top_k
+        self.exclude_seen = exclude_seen      # inference: drop the session's own items (NextItemPredictionTask.forward)
 
     @property
     def input_features(self):
@@ -79,7 +80,7 @@ class Model(nn.Module):
         task = self.prediction_task
         if training or testing:
             return task(h, targets=targets, training=training, testing=testing)
-        return task(h, training=False, testing=False, top_k=self.top_k)
+        return task(h, training=False, testing=False, top_k=self.top_k, exclude_seen=self.exclude_seen)
 
     def calculate_metrics(self, predictions, targets):
         return self.prediction_task.calculate_metrics(predictions, targets)

@@ -1188,18 +1188,93 @@ def item_scores(x, W, alpha=1.0):
     return out[:, :V]
 
 
-def item_topk(x, W, k, alpha=1.0):
+def item_topk(x, W, k, alpha=1.0, *, allow_bits=None, exclude=None):
     """(values [N, k] fp32, ids [N, k] int64) of the k best items per row of alpha * x[N, D] @ W[V, D]^T, values descending,
     ties to the lower index: bit for bit topk(gemm(x, W, False, True, alpha), k) under precision("fp32"), without an [N, V]
     tensor (csrc/item_topk.hip).  x and W may be row-strided views (unit inner stride).
     W a serving image (pack_item_table, fp16 / bf16; x stays fp32): the same from one 16-bit matrix-core product per multiply,
-    bit for bit topk(item_scores(x, W, alpha), k) (csrc/item_topk_h16.hip); the precision mode plays no part."""
-    return _item_head("item_topk", x, W, k, alpha, None)
+    bit for bit topk(item_scores(x, W, alpha), k) (csrc/item_topk_h16.hip); the precision mode plays no part.
+    allow_bits (pack_item_filter) / exclude (int64 [N, E], the items row n must not return; any order, -1 pads): only allowed
+    items come back -- bit for bit topk(item_mask_(item_scores(x, W, alpha).clone(), allow_bits, exclude), k) with id -1 in
+    every slot whose value is -inf (a row with fewer than k allowed items).  Both None: the unfiltered entry, as before."""
+    return _item_head("item_topk", x, W, k, alpha, None, allow_bits, exclude)
 
 
-def _item_head(what, x, W, k, alpha, noise):
-    """item_topk (noise None) / item_sample (noise = (row0, seed, ctr_hi)): checks, workspace, row chunks, the stats record"""
+def pack_item_filter(allow):
+    """The catalogue filter of item_topk / item_sample / item_mask_: allow [V] bool or uint8 on the device (non-zero = the item
+    may be returned) -> int32 [2 * ceil(V / 64)] bit words, bit (v & 31) of word (v >> 5) for item v, pad bits zero
+    (include/t4r_hip_filter.h).  Pack once per catalogue state; every call reads it."""
+    if not allow.is_cuda:
+        raise _lib.T4RHipError(f"pack_item_filter: allow must be a HIP device tensor (got {allow.device}); there is no CPU path")
+    if allow.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"pack_item_filter: allow: expected torch.bool or torch.uint8, got {allow.dtype}")
+    if allow.dim() != 1:
+        raise ValueError(f"pack_item_filter: allow must be [V] (got {tuple(allow.shape)})")
+    V = allow.shape[0]
+    bits = torch.empty(int(_lib.load().t4r_item_allow_words(V)), device=allow.device, dtype=torch.int32)
+    if V:
+        call("t4r_item_allow_pack", _stream(), allow.contiguous().view(torch.uint8).data_ptr(), V, bits.data_ptr())
+    return bits
+
+
+def _item_filter(what, ref, n_items, allow_bits, exclude):
+    """checks of the two filter tensors against ref (a device tensor of the call with one row per list row) and the number of
+    items the bits must cover; None if there is no filter, else (allow_bits or None, exclude sorted per row or None)"""
+    if allow_bits is None and exclude is None:
+        return None
+    if allow_bits is not None:
+        if not allow_bits.is_cuda:
+            raise _lib.T4RHipError(f"{what}: allow_bits must be a HIP device tensor (got {allow_bits.device}); there is no CPU path")
+        if allow_bits.dtype != torch.int32:
+            raise TypeError(f"{what}: allow_bits: expected torch.int32 (ops.pack_item_filter), got {allow_bits.dtype}")
+        words = int(_lib.load().t4r_item_allow_words(int(n_items)))
+        if allow_bits.dim() != 1 or not allow_bits.is_contiguous() or allow_bits.shape[0] < words:
+            raise ValueError(f"{what}: allow_bits must be a contiguous [>= {words}] word tensor for {n_items} items "
+                             f"(ops.pack_item_filter; got {tuple(allow_bits.shape)})")
+        if allow_bits.device != ref.device:
+            raise ValueError(f"{what}: allow_bits is on {allow_bits.device}, the call on {ref.device}")
+    if exclude is not None:
+        if not exclude.is_cuda:
+            raise _lib.T4RHipError(f"{what}: exclude must be a HIP device tensor (got {exclude.device}); there is no CPU path")
+        if exclude.dtype != torch.int64:
+            raise TypeError(f"{what}: exclude: expected torch.int64, got {exclude.dtype}")
+        if exclude.dim() != 2 or exclude.shape[0] != ref.shape[0] or exclude.shape[1] > 1024:
+            raise ValueError(f"{what}: exclude must be [N, E] = [{ref.shape[0]}, <= 1024] (got {tuple(exclude.shape)})")
+        if exclude.device != ref.device:
+            raise ValueError(f"{what}: exclude is on {exclude.device}, the call on {ref.device}")
+        exclude = torch.sort(exclude, dim=1).values.contiguous() if exclude.shape[1] else None
+    return allow_bits, exclude
+
+
+def _filter_args(filt, s0):
+    """the four trailing C arguments (allow_bits, excl, n_excl, ld_excl) with the list advanced to row s0"""
+    bits, excl = filt
+    if excl is None:
+        return _p(bits), None, 0, 0
+    return _p(bits), excl[s0:].data_ptr(), excl.shape[1], excl.shape[1]
+
+
+def item_mask_(scores, allow_bits=None, exclude=None, item_stride=1):
+    """in place: scores[r, c] = -inf where item c * item_stride is not allowed for row r -- its bit of allow_bits
+    (pack_item_filter) is clear or it is in exclude[r] (int64 [N, E], any order, entries outside the items ignored) -- whatever
+    the column held; allowed columns are not touched and the scores are never read (csrc/item_filter.hip).  scores fp32 [N, V],
+    row-strided views allowed; returns scores.  The materialised form of the filter of item_topk / item_sample."""
+    item_stride = int(item_stride)
+    if item_stride < 1:
+        raise ValueError(f"item_mask_: item_stride >= 1 (got {item_stride})")
+    _check_scores("item_mask_", scores)
+    N, V = scores.shape
+    filt = _item_filter("item_mask_", scores, (V - 1) * item_stride + 1 if V else 0, allow_bits, exclude)
+    if filt is not None and N and V:
+        call("t4r_item_mask_f32", _stream(), scores.data_ptr(), N, V, _row_pitch(scores, V), item_stride, *_filter_args(filt, 0))
+    return scores
+
+
+def _item_head(what, x, W, k, alpha, noise, allow_bits=None, exclude=None):
+    """item_topk (noise None) / item_sample (noise = (row0, seed, ctr_hi)): checks, workspace, row chunks, the stats record;
+    with a filter part: the filtered entries, same workspaces"""
     _check_x_w(what, x, W)
+    filt = _item_filter(what, x, W.shape[0], allow_bits, exclude)
     N, D = x.shape
     V = W.shape[0]
     k = int(k)
@@ -1215,7 +1290,7 @@ def _item_head(what, x, W, k, alpha, noise):
         return vals, idx
     lib = _lib.load()
     stem = "t4r_item_topk" if noise is None else "t4r_item_sample"
-    entry = stem + ("_h16" if h16 else "_f32")
+    entry = stem + ("_filtered" if filt is not None else "") + ("_h16" if h16 else "_f32")
     ws_bytes = getattr(lib, stem + ("_h16_ws_bytes" if h16 else "_ws_bytes"))
     rows = N
     while rows > 1 and ws_bytes(rows, V, D, k) > _ITEM_TOPK_WS_LIMIT:
@@ -1229,6 +1304,8 @@ def _item_head(what, x, W, k, alpha, noise):
         st[7] = int(_ITEM_TOPK["collect_counts"])
         table = (W.data_ptr(), ldw, _H16[W.dtype]) if h16 else (W.data_ptr(), ldw)
         tail = () if noise is None else (int(noise[0]) + s0, int(noise[1]), int(noise[2]))
+        if filt is not None:
+            tail += _filter_args(filt, s0)
         call(entry, _stream(), n, V, D, float(alpha), x[s0:].data_ptr(), ldx, *table, k, vals[s0:].data_ptr(),
              idx[s0:].data_ptr(), ws.data_ptr(), ws.numel(), ctypes.cast(st, ctypes.c_void_p), *tail)
         tot["fallback_rows"] += int(st[0])
@@ -1277,17 +1354,19 @@ def gumbel_argmax(scores, seed, ctr_hi, row0=0):
     return vals, idx
 
 
-def item_sample(x, W, k, seed, ctr_hi, alpha=1.0, row0=0):
+def item_sample(x, W, k, seed, ctr_hi, alpha=1.0, row0=0, *, allow_bits=None, exclude=None):
     """(values [N, k] fp32, ids [N, k] int64): k items per row drawn WITHOUT replacement in proportion to
     softmax(alpha * x @ W^T) (Gumbel top-k), without an [N, V] tensor: item_topk over the perturbed score
     fp32(s[r, v] + g(seed, ctr_hi, row0 + r, v)).  values are the perturbed scores, descending.  Bit for bit
     topk(gumbel_add_(item_scores(x, W, alpha).clone(), seed, ctr_hi, row0), k) -- for an fp32 W under precision("fp32").
     W fp32 or a serving image, x and W row-strided views as item_topk takes them; item_topk_stats() records the call.
     ctr_hi = dropout_ctr_hi(offset, 255, SITE_GUMBEL) by convention; the same (seed, ctr_hi, row0) replays the draw, and
-    item_sample(x[a:b], ..., row0=a) is rows a..b-1 of the whole call."""
+    item_sample(x[a:b], ..., row0=a) is rows a..b-1 of the whole call.
+    allow_bits / exclude as item_topk takes them: the draw is over the allowed items only (exclude[a:b] goes with x[a:b]);
+    slots of value -inf have id -1."""
     if int(row0) < 0:
         raise ValueError(f"item_sample: row0 must not be negative (got {row0})")
-    return _item_head("item_sample", x, W, k, alpha, (row0, seed, ctr_hi))
+    return _item_head("item_sample", x, W, k, alpha, (row0, seed, ctr_hi), allow_bits, exclude)
 
 
 def item_eval(x, image, labels, alpha=1.0):

@@ -117,6 +117,8 @@ _HEAD_RECOMPUTE = _exp_env("T4R_HEAD_RECOMPUTE", "1") != "0"
 _EAGER_HEAD_OPS = types.SimpleNamespace(
     item_scores=ops.item_scores, item_eval=ops.item_eval,
     item_topk=lambda x, W, alpha, k: ops.item_topk(x, W, k, alpha),
+    item_topk_filtered=lambda x, W, alpha, k, bits, excl: ops.item_topk(x, W, k, alpha, allow_bits=bits, exclude=excl),
+    item_mask_=ops.item_mask_,
     topk=lambda scores, k: ops.topk(scores, k, scores.shape[1]))
 
 
@@ -376,6 +378,8 @@ class NextItemPredictionTask(nn.Module):
         # both travel in rng.get_rng_state)
         self._sample_seed = None
         self._sample_offset = 0
+        # catalogue filter of the inference routes (set_item_filter): the packed bit words, not a state-dict key
+        self.register_buffer("item_filter_bits", None, persistent=False)
         loss = loss if loss is not None else nn.CrossEntropyLoss()
         if not isinstance(loss, nn.CrossEntropyLoss):
             raise NotImplementedError("the HIP head fuses torch.nn.CrossEntropyLoss (optionally label-smoothed)")
@@ -499,6 +503,24 @@ class NextItemPredictionTask(nn.Module):
             self.serving_packs += 1
         return self._serving_image
 
+    # ------------------------------------------------------------------ item filter
+    def set_item_filter(self, allow):
+        """Catalogue filter of every inference route (forward without targets, sample_items): allow [V] bool / uint8 over the
+        items of the output table, non-zero = the item may be returned (out of stock, region, category ...); None removes it.
+        Packed once into bit words (ops.pack_item_filter) and kept as the non-persistent buffer `item_filter_bits`: it follows
+        .to(device) and is not in state_dict.  Disallowed items score -inf; a session with fewer than top_k allowed items gets
+        (-inf, -1) in the remaining slots."""
+        if allow is None:
+            self.item_filter_bits = None
+            return self
+        if self.pre is None:
+            raise RuntimeError("set_item_filter: the task is not built yet")
+        W = self.pre.module.output_weights
+        if allow.dim() != 1 or allow.shape[0] != W.shape[0]:
+            raise ValueError(f"set_item_filter: allow must be [V] = [{W.shape[0]}] (got {tuple(allow.shape)})")
+        self.item_filter_bits = ops.pack_item_filter(allow.to(W.device))
+        return self
+
     def resolve_topk_mode(self, B, V):
         """'materialize' or 'fused' for an inference call that returns top-k of B sessions over V items"""
         return self.size_head_mode(B, V) if self.topk_mode == "auto" else self.topk_mode
@@ -547,7 +569,12 @@ class NextItemPredictionTask(nn.Module):
         return LazyPredictions(compute, (N, W.shape[0]), x.device, rows)
 
     # ------------------------------------------------------------------ forward
-    def forward(self, inputs, targets=None, training=False, testing=False, top_k=None, **kwargs):
+    def forward(self, inputs, targets=None, training=False, testing=False, top_k=None, exclude_seen=False, **kwargs):
+        """Training / evaluation: {"loss", "labels", "predictions"}.  Inference (neither flag): scores [B, V] at the last item of
+        every session, or (values, ids) [B, top_k] with top_k set (topk_mode, prepare_serving).  exclude_seen=True excludes
+        the ids of the session's own `item_seq` row -- the padding id is in that list and is therefore excluded too -- and a
+        filter set by set_item_filter applies on every route: excluded items score -inf, and top-k slots of value -inf have
+        id -1.  Without either the routes are what they were."""
         if isinstance(inputs, (tuple, list)):
             inputs = inputs[0]
         x = inputs.float()
@@ -582,6 +609,18 @@ class NextItemPredictionTask(nn.Module):
         V = W.shape[0]
         head = self._head_ops()
         image = self._serving_weights()
+        bits, seen = self.item_filter_bits, self._seen_items(exclude_seen)
+        if bits is not None or seen is not None:
+            # the same three routes under the filter: the fused heads take it as an argument, materialised scores are masked
+            Wf = image if image is not None else W
+            if top_k is not None and (image is not None or self.resolve_topk_mode(B, V) == "fused"):
+                return head.item_topk_filtered(xr, Wf, inv_t, top_k, bits, seen)
+            scores = head.item_scores(xr, Wf, inv_t)
+            head.item_mask_(scores, bits, seen, 1)
+            if top_k is None:
+                return scores
+            vals, idx = head.topk(scores, top_k)
+            return vals, idx.masked_fill_(vals == float("-inf"), -1)      # the tail rule of the fused entries
         if image is not None:
             # served from the half-precision image: fused head for top-k, [B, V] fp32 scores otherwise; topk_mode plays no part
             return head.item_scores(xr, image, inv_t) if top_k is None else head.item_topk(xr, image, inv_t, top_k)
@@ -589,6 +628,15 @@ class NextItemPredictionTask(nn.Module):
             return head.item_topk(xr, W, inv_t, top_k)
         scores = head.item_scores(xr, W, inv_t)
         return scores if top_k is None else head.topk(scores, top_k)
+
+    def _seen_items(self, exclude_seen):
+        """the per-row exclusion lists of exclude_seen: the sessions' own item ids [B, L] (padding id included), or None"""
+        if not exclude_seen:
+            return None
+        item_seq = self.embeddings.item_seq
+        if item_seq.shape[1] > 1024:
+            raise ValueError(f"exclude_seen: sessions of at most 1024 items (got {item_seq.shape[1]})")
+        return item_seq.to(torch.int64).contiguous()
 
     def _inference_rows(self, x):
         """(xr [B, D'], 1 / T) of an inference call: the hidden state at the last item of every session of x [B, L, D]
@@ -617,12 +665,14 @@ class NextItemPredictionTask(nn.Module):
     def sample_seed(self, value):
         self._sample_seed = None if value is None else int(value) & 0x7FFFFFFFFFFFFFFF
 
-    def sample_items(self, inputs, k=1):
+    def sample_items(self, inputs, k=1, exclude_seen=False):
         """Stochastic recommendation: (values [B, k] fp32, ids [B, k] int64), k distinct items per session drawn in proportion
         to softmax(scores) of an inference call (Gumbel top-k; values = the perturbed scores, descending).  `inputs` and the row
         selection are an inference forward's; the draw runs through the fused sampling head (ops.item_sample: no [B, V] tensor)
         over the serving image while prepare_serving stands, else over the fp32 table.  Every call advances `_sample_offset`;
-        (sample_seed, _sample_offset) replay a call (rng.get_rng_state / set_rng_state)."""
+        (sample_seed, _sample_offset) replay a call (rng.get_rng_state / set_rng_state).
+        exclude_seen=True draws from the items outside the session's own `item_seq` row only (the padding id is in that list and
+        is excluded too); a filter set by set_item_filter applies as well.  Slots of value -inf have id -1."""
         if self.pre is None:
             raise RuntimeError("sample_items: the task is not built yet")
         if isinstance(inputs, (tuple, list)):
@@ -632,7 +682,8 @@ class NextItemPredictionTask(nn.Module):
         W = image if image is not None else self.pre.module.output_weights.detach()
         self._sample_offset += 1
         ctr_hi = ops.dropout_ctr_hi(self._sample_offset, 255, ops.SITE_GUMBEL)
-        return ops.item_sample(xr, W, k, self.sample_seed, ctr_hi, inv_t)
+        return ops.item_sample(xr, W, k, self.sample_seed, ctr_hi, inv_t, allow_bits=self.item_filter_bits,
+                               exclude=self._seen_items(exclude_seen))
 
     @staticmethod
     def _head_ops():

@@ -105,6 +105,59 @@ def _(x, weight, alpha, k, seed, ctr_hi, row0):
     return x.new_empty((x.shape[0], k)), x.new_empty((x.shape[0], k), dtype=torch.int64)
 
 
+@torch.library.custom_op(f"{NS}::pack_item_filter", mutates_args=())
+def pack_item_filter(allow: torch.Tensor) -> torch.Tensor:
+    """the catalogue filter of the filtered heads: allow [V] bool / uint8 (non-zero = may be returned) -> int32 bit words
+    (include/t4r_hip_filter.h; csrc/item_filter.hip)"""
+    return ops.pack_item_filter(allow)
+
+
+@pack_item_filter.register_fake
+def _(allow):
+    return allow.new_empty(((allow.shape[0] + 63) // 64 * 2,), dtype=torch.int32)
+
+
+@torch.library.custom_op(f"{NS}::item_mask_", mutates_args=("scores",))
+def item_mask_(scores: torch.Tensor, allow_bits: Optional[torch.Tensor], exclude: Optional[torch.Tensor],
+               item_stride: int) -> None:
+    """in place: scores[r, c] = -inf where item c * item_stride is not allowed for row r -- the `scores[mask] = -inf` a caller
+    writes on the scores of prediction_task.py:452-470 before torch.topk, without reading the scores (csrc/item_filter.hip)"""
+    ops.item_mask_(scores, allow_bits, exclude, item_stride)
+
+
+@item_mask_.register_fake
+def _(scores, allow_bits, exclude, item_stride):
+    return None
+
+
+@torch.library.custom_op(f"{NS}::item_topk_filtered", mutates_args=())
+def item_topk_filtered(x: torch.Tensor, weight: torch.Tensor, alpha: float, k: int, allow_bits: Optional[torch.Tensor],
+                       exclude: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """item_topk over the allowed items only (allow_bits: pack_item_filter; exclude: int64 [N, E] per-row lists): topk of the
+    masked scores without the [N, V] scores, id -1 in slots of value -inf (include/t4r_hip_filter.h)"""
+    vals, idx = ops.item_topk(x, weight, k, alpha, allow_bits=allow_bits, exclude=exclude)
+    return vals, idx
+
+
+@item_topk_filtered.register_fake
+def _(x, weight, alpha, k, allow_bits, exclude):
+    return x.new_empty((x.shape[0], k)), x.new_empty((x.shape[0], k), dtype=torch.int64)
+
+
+@torch.library.custom_op(f"{NS}::item_sample_filtered", mutates_args=())
+def item_sample_filtered(x: torch.Tensor, weight: torch.Tensor, alpha: float, k: int, seed: int, ctr_hi: int, row0: int,
+                         allow_bits: Optional[torch.Tensor], exclude: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """item_sample over the allowed items only: k draws without replacement in proportion to the softmax over the allowed
+    items, id -1 in slots of value -inf (include/t4r_hip_filter.h)"""
+    vals, idx = ops.item_sample(x, weight, k, seed, ctr_hi, alpha, row0, allow_bits=allow_bits, exclude=exclude)
+    return vals, idx
+
+
+@item_sample_filtered.register_fake
+def _(x, weight, alpha, k, seed, ctr_hi, row0, allow_bits, exclude):
+    return x.new_empty((x.shape[0], k)), x.new_empty((x.shape[0], k), dtype=torch.int64)
+
+
 @torch.library.custom_op(f"{NS}::gumbel_argmax", mutates_args=())
 def gumbel_argmax(scores: torch.Tensor, seed: int, ctr_hi: int, row0: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """one draw per row from softmax(scores [N, V]): (max of score + g(seed, ctr_hi, row0 + row, column), its column), in one pass
@@ -739,7 +792,8 @@ def _am_backward(ctx, dy):
 apply_mask.register_autograd(_am_backward, setup_context=_am_setup)
 
 
-OPERATORS = ("gemm", "item_scores", "topk", "item_topk", "item_sample", "gumbel_argmax", "item_eval", "pack_item_table", "rank_of_target", "embedding_gather", "embedding_bag", "ragged_to_padded",
+OPERATORS = ("gemm", "item_scores", "topk", "item_topk", "item_sample", "gumbel_argmax", "item_eval", "pack_item_table",
+             "pack_item_filter", "item_mask_", "item_topk_filtered", "item_sample_filtered", "rank_of_target", "embedding_gather", "embedding_bag", "ragged_to_padded",
              "xlnet_layer_infer", "xlnet_layer_fwd", "xlnet_layer_bwd", "mlm_targets", "seq_item_embedding",
              "seq_item_embedding_bwd", "xlnet_layer_grad", "gather_label_rows", "scatter_label_rows", "linear_softmax_ce",
              "linear_softmax_ce_bwd", "dropout", "pos_emb_dropout", "next_item_head", "next_item_head_bwd",
