@@ -246,8 +246,8 @@ int t4r_get_tok_gemm_min_rows(void);
 typedef struct t4r_head_note { unsigned long long w[8]; } t4r_head_note;
 int t4r_head_note_dw_form(const void* note);
 int t4r_head_split_supported(int D);
-/* matrix instructions per fp32-equivalent one in the forward logits / d X products of csrc/head_split.hip: 3 = two-way fp16
- * split with power-of-two tensor scales (default), 6 = three bf16 planes (T4R_HEAD_FWD_FP16X2=0); d W always 6 */
+/* matrix instructions per fp32-equivalent one in the forward logits / d X products of csrc/head_split.hip: always 3 (two-way
+ * fp16 split with power-of-two tensor scales).  d W: 3 in form 2, 6 in form 1 (t4r_head_note_dw_form). */
 int t4r_head_split_fwd_products(void);
 long t4r_head_split_ws_bytes(int N, int V, int D);
 int t4r_head_split_prepare(void* stream, const float* X, long ldx, int N, int D, int V, void* ws);
@@ -268,7 +268,7 @@ int t4r_head_split_dx(void* stream, void* ws, const float* logits, long ld, cons
                       const float* grad_out, float label_smoothing, const float* W, long ldw, float* dX, long lddx,
                       int N, int Vc, int V, int yoff, int D, float alpha, int accumulate, void* note);
 
-/* The ONE-PASS forward of the same head (round 5; csrc/head_split.hip: head_fwd_dx_kernel): logits, loss rows, lse, the mean
+/* The ONE-PASS forward of the same head (csrc/head_split.hip: head_fwd_dx_kernel): logits, loss rows, lse, the mean
  * loss AND dX [N, D] = d (mean loss) / d X for grad_out = 1 from one launch over (128-row tile x item range) workgroups --
  * the score tile comes off the matrix cores once, is stored, and its probabilities against a running row reference feed the
  * d X product from registers (flash-attention style; a small kernel merges the per-range statistics and partial sums).  The
@@ -277,7 +277,7 @@ int t4r_head_split_dx(void* stream, void* ws, const float* logits, long ld, cons
  * half of their autograd.  X: the rows t4r_head_split_prepare was given (same ws); wsum: column sums of W [D], required when
  * label_smoothing > 0, else NULL; the caller's backward is dX * grad_out and t4r_head_split_dw with the same ws / note.
  * labels == NULL: the dominant kernel alone on a workspace a full call has filled (bench.py's roofline timing).
- * t4r_head_split_fdx_supported: 1 when this form takes the width (two-way fp16 products on; T4R_HEAD_FDX=0 switches it off). */
+ * t4r_head_split_fdx_supported: 1 when this form takes the width (the widths of t4r_head_split_supported). */
 int t4r_head_split_fdx_supported(int D);
 /* The next t4r_head_split_logits_ce_dx of this thread ON TABLE W takes max |W| from part[0 .. n) -- the per-workgroup maxima
  * t4r_adam_step_amax left over exactly W's elements; the caller promises that nothing has written W since -- instead of a memset
@@ -286,7 +286,7 @@ void t4r_head_split_w_amax_hint(const float* W, const float* part, int n);
 int t4r_head_split_logits_ce_dx(void* stream, void* ws, const float* X, long ldx, const float* W, long ldw, float* C, long ldc,
                                 const long* labels, float* loss_rows, float* lse, float* loss_mean, float* dX, long lddx,
                                 const float* wsum, int N, int V, int D, float alpha, float label_smoothing, void* note);
-/* The RECOMPUTING form of the same head (round 4; two-way fp16 products only: t4r_head_split_recompute_supported): nothing
+/* The RECOMPUTING form of the same head (t4r_head_split_recompute_supported: the widths of t4r_head_split_supported): nothing
  * of size [N, V] is written or read.  _ce: loss rows, lse (and the mean) from per-tile statistics, each row's label logit
  * captured inside the product; _dw_rc / _dx_rc: the two backward products with their score tiles recomputed on the matrix
  * cores in the orientation whose accumulator layout is the A operand of the product that follows (1.1 GB of logits written

@@ -146,3 +146,9 @@ def test_product_build_reads_no_experiment_switch(monkeypatch):
     for f in glob.glob(os.path.join(root, "transformers4rec_amd", "*.py")):
         host |= set(re.findall(r'environ\.get\("(T4R_[A-Z0-9_]+)"', open(f).read()))
     assert host == {"T4R_HIP_LIB", "T4R_HEAD_MODE", "T4R_HEAD_AUTO_GB", "T4R_HEAD_CHUNK_MB", "T4R_HEAD_WS_GB"}, host
+    # the full-softmax head has no switch at all: its kernel forms are selected from what the code observes
+    named = [os.path.basename(f) for f in glob.glob(os.path.join(root, "transformers4rec_amd", "csrc", "*")) if "T4R_HEAD_" in open(f).read()]
+    assert not named, named
+    assert "t4r_exp_getenv" not in open(os.path.join(root, "transformers4rec_amd", "csrc", "head_split.hip")).read()
+    head_py = open(os.path.join(root, "transformers4rec_amd", "prediction_task.py")).read()
+    assert not re.findall(r'_exp_env\("(T4R_HEAD_[A-Z0-9_]+)"', head_py)

@@ -157,8 +157,7 @@ def test_head_one_pass_forward_gives_logits_loss_and_dx(N, V, D, smooth, T):
     forward leaves) against fp64 per item row."""
     from transformers4rec_amd import ops
 
-    if not ops.head_split_fdx_supported(D):
-        pytest.skip("one-pass head switched off (T4R_HEAD_FDX=0 / fp16 forms off)")
+    assert ops.head_split_fdx_supported(D)
     g = torch.Generator().manual_seed(N + V)
     x = torch.randn(N, D, generator=g)
     # item norms over two decades (rare items: d W rows far below the tensor's maximum)

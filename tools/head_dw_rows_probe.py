@@ -1,8 +1,9 @@
 #!/usr/bin/env python
 """Per-ROW accuracy of the head's d W (one row = one item) against fp64, rows bucketed by their magnitude relative to the
-largest row: what would the two-way fp16 split (T4R_HEAD_DW_FP16X2=1, an experiment switch) cost the rare items' rows,
-next to the three bf16 planes (default) and the fp32 matrix cores (general GEMM)?  Also times the kernel.
-    python tools/head_dw_rows_probe.py            # run once per setting of T4R_HEAD_DW_FP16X2"""
+largest row: what does the two-way fp16 split with per-item scales (form 2, what runs after a forward that left its column
+maxima) cost the rare items' rows, next to the three bf16 planes (form 1, selected here through a zeroed note: the backward
+then knows nothing about the forward) and the fp32 matrix cores (general GEMM)?  Also times both kernels.
+    python tools/head_dw_rows_probe.py"""
 import os
 import sys
 
@@ -40,18 +41,23 @@ def report(name, dW):
                   f"median {float(e.median()):.1e}  99 % {float(e.quantile(0.99)):.1e}  max {float(e.max()):.1e}")
 
 
+fwd_note = ws.t4r_note
 dW = torch.zeros(V, D, device=dev)
-ops.head_split_dw(ws, logits, lse, labels, gout, V, D, dW, accumulate=False)
-report(f"head_split d W (T4R_HEAD_DW_FP16X2={os.environ.get('T4R_HEAD_DW_FP16X2', '0')})", dW)
+for form in (2, 1):
+    # form 1: a fresh (zeroed) note, as tests/test_round4_gpu.py selects it
+    ws.t4r_note = fwd_note if form == 2 else torch.zeros(8, dtype=torch.int64)
+    ops.head_split_dw(ws, logits, lse, labels, gout, V, D, dW, accumulate=False)
+    assert ops.head_split_dw_form(ws) == form
+    report(f"head_split d W form {form}", dW)
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(3):
+        ops.head_split_dw(ws, logits, lse, labels, gout, V, D, dW, accumulate=False)
+    s.record()
+    for _ in range(20):
+        ops.head_split_dw(ws, logits, lse, labels, gout, V, D, dW, accumulate=False)
+    e.record()
+    torch.cuda.synchronize()
+    print(f"head_split d W form {form}: {1e3 * s.elapsed_time(e) / 20:.1f} us per launch")
 with ops.precision("fp32"):
     dWg = ops.gemm_softmax_grad(logits, lse, labels, gout, V, x, True)
 report("general GEMM, fp32 matrix cores", dWg)
-s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-for _ in range(3):
-    ops.head_split_dw(ws, logits, lse, labels, gout, V, D, dW, accumulate=False)
-s.record()
-for _ in range(20):
-    ops.head_split_dw(ws, logits, lse, labels, gout, V, D, dW, accumulate=False)
-e.record()
-torch.cuda.synchronize()
-print(f"head_split d W: {1e3 * s.elapsed_time(e) / 20:.1f} us per launch")

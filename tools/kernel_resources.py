@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""Registers, LDS, scratch and waves per SIMD of every kernel of the library, as the compiler reports them
+"""Registers, spills, LDS, scratch and waves per SIMD of every kernel of the library, as the compiler reports them for the
+flags the library is built with (build.py: FLAGS + the per-source EXTRA_FLAGS)
 (hipcc -Rpass-analysis=kernel-resource-usage; no GPU needed):
 
     python tools/kernel_resources.py [substring ...]        # default: the kernels of the training step
@@ -18,7 +19,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from transformers4rec_amd.build import FLAGS, _hipcc  # noqa: E402
+from transformers4rec_amd.build import EXTRA_FLAGS, FLAGS, _hipcc  # noqa: E402
 
 STEP = ["head_fwd_dx", "head_dw_split", "head_fdx_finalize", "split_w_images", "split_x_images", "xlnet_attn_block_fwd",
         "xlnet_ff_fwd", "xlnet_ff_bwd", "xlnet_ln1_bwd", "xlnet_dh_kernel", "xlnet_attn_mfma_bwd", "xlnet_proj_kernel",
@@ -29,14 +30,15 @@ STEP = ["head_fwd_dx", "head_dw_split", "head_fdx_finalize", "split_w_images", "
 
 def one(src):
     with tempfile.TemporaryDirectory() as d:
-        r = subprocess.run([_hipcc()] + FLAGS + ["-c", src, "-o", os.path.join(d, "o.o"), "-Rpass-analysis=kernel-resource-usage"],
+        r = subprocess.run([_hipcc()] + FLAGS + EXTRA_FLAGS.get(os.path.basename(src), []) +
+                           ["-c", src, "-o", os.path.join(d, "o.o"), "-Rpass-analysis=kernel-resource-usage"],
                            capture_output=True, text=True)
     out = []
     for b in re.split(r"remark: [^\n]*Function Name: ", r.stderr)[1:]:
         name = b.split()[0]
         g = lambda k: int(m.group(1)) if (m := re.search(k + r": (\d+)", b)) else -1      # noqa: E731
-        out.append((os.path.basename(src), name, g("VGPRs"), g("AGPRs"), g(r"LDS Size \[bytes/block\]"),
-                    g(r"ScratchSize \[bytes/lane\]"), g(r"Occupancy \[waves/SIMD\]")))
+        out.append((os.path.basename(src), name, g("VGPRs"), g("AGPRs"), g("SGPRs"), g("SGPRs Spill"), g("VGPRs Spill"),
+                    g(r"LDS Size \[bytes/block\]"), g(r"ScratchSize \[bytes/lane\]"), g(r"Occupancy \[waves/SIMD\]")))
     return out
 
 
@@ -45,10 +47,11 @@ def main():
     srcs = sorted(glob.glob(os.path.join(ROOT, "transformers4rec_amd", "csrc", "*.hip")))
     with ThreadPoolExecutor(8) as ex:
         rows = [r for rs in ex.map(one, srcs) for r in rs]
-    print(f"{'file':24s} {'kernel (mangled, cut)':70s} {'VGPR':>5s} {'AGPR':>5s} {'LDS B':>7s} {'scratch':>7s} {'waves/SIMD':>10s}")
-    for f, n, v, a, l, s, o in rows:
+    print(f"{'file':24s} {'kernel (mangled, cut)':70s} {'VGPR':>5s} {'AGPR':>5s} {'SGPR':>5s} {'s-spill':>7s} {'v-spill':>7s} {'LDS B':>7s} "
+          f"{'scratch':>7s} {'waves/SIMD':>10s}")
+    for f, n, v, a, sg, ss, vs, l, s, o in rows:
         if any(w in n for w in want):
-            print(f"{f:24s} {n[:70]:70s} {v:5d} {a:5d} {l:7d} {s:7d} {o:10d}")
+            print(f"{f:24s} {n[:70]:70s} {v:5d} {a:5d} {sg:5d} {ss:7d} {vs:7d} {l:7d} {s:7d} {o:10d}")
     print("(LDS B = static LDS only: the token-tile kernels take theirs at launch -- csrc/xlnet_fused*.hip, ~77-159 KB, one workgroup per CU)")
 
 

@@ -1,20 +1,25 @@
 // Next-item head (tied full softmax) for d_model <= 128, fp32-class accuracy on the 16-bit matrix cores.
 //
-// Two operand forms live here.  Round 2 (described first, still selectable with T4R_HEAD_FWD_FP16X2=0 /
-// T4R_HEAD_DW_FP16X2=0): three bf16 planes per operand, six products.  Round 3 (default, see mfma_split below): a two-way
-// fp16 split with exact power-of-two scales -- one per tensor for the forward and d X, one per ITEM for d W -- three
-// products; same or smaller error against fp64, half the matrix instructions (these kernels run at the package power limit).
+// Two operand forms live here, each where its accuracy argument holds:
+//   * the two-way fp16 split (mfma_split<true> below) with exact power-of-two scales, three products per K = 16 step: the
+//     forward (logits, statistics, the one-pass and the recomputing heads), d X, and d W "form 2" with one scale per ITEM;
+//   * three bf16 planes per operand, six products (mfma6): d W "form 1".  Form 2's per-item scales come from the column maxima
+//     of the logits, which only a forward over the SAME logits leaves behind; form 1 needs nothing from the forward and runs
+//     whenever those maxima are missing -- no note or a zeroed note, a chunk of the vocabulary, a misaligned logits pitch, or
+//     a row split that differs from the workspace's (t4r_head_split_dw).
+// The fp16 form has the same or a smaller error against fp64 at half the matrix instructions (these kernels run at the package
+// power limit).
 //
 // Replaces, for D = 32 / 64 / 96 / 128, the three vocabulary-wide contractions of
 // transformers4rec/torch/model/prediction_task.py:664 (logits = X @ W^T) and of its autograd
 // (d X = dlogits @ W, d W = dlogits^T @ X, with CrossEntropyLoss' backward :446 formed on the fly from the
 // stored logits) -- 2.1 of the 4.8 ms training step at BASELINE configs[1] when they ran through the general
-// GEMM (gemm_kernel.h, PREC 1).  Same arithmetic as PREC 1: every operand is cut into three bf16 pieces
-// (x = hi + mid + lo exactly, round-to-nearest cuts) and the six largest partial products are accumulated in
-// fp32 by v_mfma_f32_32x32x16_bf16.  What changes is WHERE the cutting happens: the general kernel re-cuts every
+// GEMM (gemm_kernel.h, PREC 1).  Every operand is cut into pieces that sum to it (two fp16 pieces of the scaled value, or
+// x = hi + mid + lo in bf16, round-to-nearest cuts) and the largest partial products are accumulated in fp32 on the matrix
+// cores.  What differs from the general kernel is WHERE the cutting happens: that one re-cuts every
 // operand tile each time a workgroup stages it (the VALU work equals the matrix-core time), here
 //   * X [N, D] (a few thousand label rows) is cut ONCE per step into fragment-ordered plane blocks
-//     (split_mk / split_km kernels: 24 KB per 32 rows);
+//     (split_x_images_kernel: 16 or 24 KB per 32 rows);
 //   * logits: a workgroup keeps its 128 rows of W as MFMA B fragments IN REGISTERS for its whole life (cut once per
 //     workgroup, the whole K = D extent: 96 VGPRs at D = 128) and streams the X plane blocks through LDS --
 //     no conversion and one ds_read_b128 per two MFMAs in the loop;
@@ -68,8 +73,9 @@ __device__ __forceinline__ f32x16 mfma6(const u32x4 (&a)[3], const u32x4 (&b)[3]
 // hi hi + hi lo + lo hi (the dropped lo lo <= 2^-22 |x w|): per product term <= 2^-21 |x w| in the worst case, measured
 // 2-3 x the error of the fp32 matrix cores against fp64 (tools/head_split_bench.py).  Entries below 2^-17 of the
 // tensor's maximum keep fewer than 22 bits (fp16 subnormals in lo) -- irrelevant for a dot product's norm-wise error, NOT
-// acceptable for the gradient operand, whose rare-item columns lie 10^-6 below its maximum: the backward products stay
-// on the three bf16 planes.  T4R_HEAD_FWD_FP16X2=0 puts the forward back on them too.
+// acceptable for d W's gradient operand under one scale per tensor: its rare-item columns lie 10^-6 below the maximum, so
+// d W positions every item on its own (head_dw_split_kernel) or, without the column maxima for that, runs on the three
+// bf16 planes (HS = false: split8 / mfma6).
 __device__ __forceinline__ f32x16 mfma_f16(u32x4 a, u32x4 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, a), __builtin_bit_cast(half8_t, b), c, 0, 0, 0);
 }
@@ -156,15 +162,16 @@ __device__ __forceinline__ float scale_of(const unsigned* amax_bits) {
     return ldexpf(1.f, min(14 - e, 100));    // a maximum below 2^-86 (the d W bound of an item far below every row's lse) must not overflow the scale
 }
 
-// ---- plane blocks.  One block = 32 rows of a row-major fp32 matrix [n_rows, D], as three bf16 planes:
+// ---- plane blocks.  One block = 32 rows of a row-major fp32 matrix [n_rows, D], as two fp16 planes (HS) or three bf16 planes:
 //   MK image (rows are the M / N index of the product, D is K):  [plane][chunk = d / 8][row % 32] x 16 bytes = 8 consecutive d
 //   KM image (rows are K, D is the N index):                     [plane][kc = (row % 32) / 8][d] x 16 bytes = 8 consecutive rows
-// Both are 12 D u32x4 (24 KB at D = 128); rows >= n_rows are zero.
-template <int NB, bool HS = false>
+// Both are 4 D u32x4 per plane (24 KB at D = 128 with three planes); rows >= n_rows are zero.  The MK image exists in the fp16
+// form only.
+template <int NB>
 __device__ __forceinline__ void split_mk_body(int b, const float* __restrict__ src, long ld, int n_rows,
                                               u32x4* __restrict__ dst, const unsigned* __restrict__ amax) {
-    constexpr int D = 32 * NB, CH = D / 8, NPL = HS ? 2 : 3;
-    const float scale = HS ? scale_of(amax) : 1.f;
+    constexpr int D = 32 * NB, CH = D / 8, NPL = 2;
+    const float scale = scale_of(amax);
     for (int idx = threadIdx.x; idx < CH * 32; idx += 256) {
         const int r = idx & 31, c = idx >> 5, row = b * 32 + r;
         float x[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -174,17 +181,17 @@ __device__ __forceinline__ void split_mk_body(int b, const float* __restrict__ s
             x[0] = u.x; x[1] = u.y; x[2] = u.z; x[3] = u.w; x[4] = v.x; x[5] = v.y; x[6] = v.z; x[7] = v.w;
         }
         u32x4 w[NPL];
-        split8s<HS>(x, scale, w);
+        split8s<true>(x, scale, w);
 #pragma unroll
         for (int pl = 0; pl < NPL; ++pl) dst[((long)b * NPL + pl) * (CH * 32) + c * 32 + r] = w[pl];
     }
 }
-template <int NB, bool HS = false>
+template <int NB>
 __global__ __launch_bounds__(256) void split_mk_kernel(const float* __restrict__ src, long ld, int n_rows,
-                                                        u32x4* __restrict__ dst, const unsigned* __restrict__ amax = nullptr) {
-    split_mk_body<NB, HS>(blockIdx.x, src, ld, n_rows, dst, amax);
+                                                        u32x4* __restrict__ dst, const unsigned* __restrict__ amax) {
+    split_mk_body<NB>(blockIdx.x, src, ld, n_rows, dst, amax);
 }
-template <int NB, bool HS = false>
+template <int NB, bool HS>
 __device__ __forceinline__ void split_km_body(int b, const float* __restrict__ src, long ld, int n_rows,
                                               u32x4* __restrict__ dst, const unsigned* __restrict__ amax) {
     constexpr int D = 32 * NB, NPL = HS ? 2 : 3;
@@ -203,10 +210,10 @@ __device__ __forceinline__ void split_km_body(int b, const float* __restrict__ s
         for (int pl = 0; pl < NPL; ++pl) dst[(((long)b * NPL + pl) * 4 + kc) * D + d] = w[pl];
     }
 }
-template <int NB, bool HS = false>
+template <int NB>
 __global__ __launch_bounds__(256) void split_km_kernel(const float* __restrict__ src, long ld, int n_rows,
-                                                        u32x4* __restrict__ dst, const unsigned* __restrict__ amax = nullptr) {
-    split_km_body<NB, HS>(blockIdx.x, src, ld, n_rows, dst, amax);
+                                                        u32x4* __restrict__ dst, const unsigned* __restrict__ amax) {
+    split_km_body<NB, true>(blockIdx.x, src, ld, n_rows, dst, amax);
 }
 // the three images of the head's input rows in ONE launch (blockIdx.y picks the image): fp16 MK (logits), bf16 KM and fp16 KM
 // (d W in either form) -- three 5 us launches on the critical stream otherwise
@@ -214,21 +221,21 @@ template <int NB>
 __global__ __launch_bounds__(256) void split_x_images_kernel(const float* __restrict__ src, long ld, int n_rows, u32x4* __restrict__ xa,
                                                               u32x4* __restrict__ xt, u32x4* __restrict__ xth,
                                                               const unsigned* __restrict__ amax) {
-    if (blockIdx.y == 0) split_mk_body<NB, true>(blockIdx.x, src, ld, n_rows, xa, amax);
+    if (blockIdx.y == 0) split_mk_body<NB>(blockIdx.x, src, ld, n_rows, xa, amax);
     else if (blockIdx.y == 1) split_km_body<NB, false>(blockIdx.x, src, ld, n_rows, xt, nullptr);
     else split_km_body<NB, true>(blockIdx.x, src, ld, n_rows, xth, amax);
 }
 
-// KMP image (round 4, the recomputing backward kernels): as the KM image, with the 32 rows of a block in the order the
+// KMP image (the recomputing backward kernels; fp16 form): as the KM image, with the 32 rows of a block in the order the
 // 32 x 32 ACCUMULATOR hands them to a lane -- position (kc = 2 s + khalf, e) holds row 16 s + 4 khalf + (e & 3) + 8 (e >> 2),
 // i.e. accumulator register 8 s + e of lane half khalf.  A score tile recomputed on the matrix cores then IS (after the
 // softmax-gradient transform, in registers) the A operand of the product that contracts over its rows, against this image.
-template <int NB, bool HS = false>
+template <int NB>
 __global__ __launch_bounds__(256) void split_kmp_kernel(const float* __restrict__ src, long ld, int n_rows,
-                                                         u32x4* __restrict__ dst, const unsigned* __restrict__ amax = nullptr) {
-    constexpr int D = 32 * NB, NPL = HS ? 2 : 3;
+                                                         u32x4* __restrict__ dst, const unsigned* __restrict__ amax) {
+    constexpr int D = 32 * NB, NPL = 2;
     const int b = blockIdx.x;
-    const float scale = HS ? scale_of(amax) : 1.f;
+    const float scale = scale_of(amax);
     for (int idx = threadIdx.x; idx < 4 * D; idx += 256) {
         const int d = idx % D, kc = idx / D;
         float x[8];
@@ -238,22 +245,22 @@ __global__ __launch_bounds__(256) void split_kmp_kernel(const float* __restrict_
             x[e] = row < n_rows ? src[(long)row * ld + d] : 0.f;
         }
         u32x4 w[NPL];
-        split8s<HS>(x, scale, w);
+        split8s<true>(x, scale, w);
 #pragma unroll
         for (int pl = 0; pl < NPL; ++pl) dst[(((long)b * NPL + pl) * 4 + kc) * D + d] = w[pl];
     }
 }
 
 // ---- logits:  C[N, V] = alpha * X @ W^T.  grid (ceil(V / 128), row splits); X as MK plane blocks.
-template <int NB, bool HS = false>
+template <int NB>
 __global__ __launch_bounds__(256) void head_logits_split_kernel(const u32x4* __restrict__ XA, const float* __restrict__ W,
                                                                  long ldw, float* __restrict__ C, long ldc, int N, int V,
                                                                  float alpha, int nblk, int blk_per,
-                                                                 const unsigned* __restrict__ amax = nullptr) {
-    constexpr int KS = 2 * NB, CH = 4 * NB, NPL = HS ? 2 : 3;
+                                                                 const unsigned* __restrict__ amax) {
+    constexpr int KS = 2 * NB, CH = 4 * NB, NPL = 2;
     constexpr int BLK = 4 * NPL * 32 * NB;      // u32x4 per plane block
-    const float sw = HS ? scale_of(amax + 1) : 1.f;
-    if (HS) alpha = (alpha / scale_of(amax)) / sw;      // two exact divisions by powers of two (their product may overflow)
+    const float sw = scale_of(amax + 1);
+    alpha = (alpha / scale_of(amax)) / sw;      // two exact divisions by powers of two (their product may overflow)
     constexpr int SN = (BLK + 255) / 256;
     __shared__ u32x4 lds[2][BLK];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l32 = lane & 31, khalf = lane >> 5;
@@ -270,7 +277,7 @@ __global__ __launch_bounds__(256) void head_logits_split_kernel(const u32x4* __r
             const float4 u = *reinterpret_cast<const float4*>(wr + 16 * s);
             const float4 v = *reinterpret_cast<const float4*>(wr + 16 * s + 4);
             const float x[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
-            split8s<HS>(x, sw, Bf[s]);
+            split8s<true>(x, sw, Bf[s]);
         }
     }
 
@@ -303,7 +310,7 @@ __global__ __launch_bounds__(256) void head_logits_split_kernel(const u32x4* __r
             u32x4 a[NPL];
 #pragma unroll
             for (int pl = 0; pl < NPL; ++pl) a[pl] = lds[buf][(pl * CH + 2 * s + khalf) * 32 + l32];
-            acc = mfma_split<HS>(a, Bf[s], acc);
+            acc = mfma_split<true>(a, Bf[s], acc);
         }
         // next block -> LDS before the logits are stored: the wait for its loads must not cover the HBM stores
         s_store(buf ^ 1);
@@ -366,7 +373,7 @@ __device__ __forceinline__ void quad_transpose4(float (&x)[4], int t) {
     }
 }
 
-template <int NB, bool HS, bool ZL = false>
+template <int NB, bool ZL = false>
 __device__ __forceinline__ void head_logits_ce_body(const u32x4* __restrict__ XA, const float* __restrict__ W,
                                                     long ldw, float* __restrict__ C, long ldc, int N, int V,
                                                     float alpha, int nblk, int blk_per, int vec_ok,
@@ -374,12 +381,12 @@ __device__ __forceinline__ void head_logits_ce_body(const u32x4* __restrict__ XA
                                                     float* __restrict__ st_t, int n_tile, int n_split,
                                                     const unsigned* __restrict__ amax, float* __restrict__ colmax, int vpad,
                                                     const long* __restrict__ labels = nullptr, float* __restrict__ zlab = nullptr) {
-    // C == NULL (the recomputing head, round 4): nothing is stored but the statistics -- and, with `labels`, each row's
+    // C == NULL (the recomputing head): nothing is stored but the statistics -- and, with `labels`, each row's
     // label logit (zlab [N]: the loss needs it, and the lane that holds it writes it: exact, no second product)
-    constexpr int KS = 2 * NB, CH = 4 * NB, NPL = HS ? 2 : 3;
+    constexpr int KS = 2 * NB, CH = 4 * NB, NPL = 2;
     constexpr int BLK = 4 * NPL * 32 * NB;
-    const float sw = HS ? scale_of(amax + 1) : 1.f;
-    if (HS) alpha = (alpha / scale_of(amax)) / sw;      // two exact divisions by powers of two (their product may overflow)
+    const float sw = scale_of(amax + 1);
+    alpha = (alpha / scale_of(amax)) / sw;      // two exact divisions by powers of two (their product may overflow)
     constexpr int SN = (BLK + 255) / 256;
     __shared__ u32x4 lds[2][BLK];
     __shared__ float4 sst[2][4][32];
@@ -403,7 +410,7 @@ __device__ __forceinline__ void head_logits_ce_body(const u32x4* __restrict__ XA
             const float4 u = *reinterpret_cast<const float4*>(wr + 16 * s);
             const float4 v = *reinterpret_cast<const float4*>(wr + 16 * s + 4);
             const float x[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
-            split8s<HS>(x, sw, Wf[s]);
+            split8s<true>(x, sw, Wf[s]);
         }
     }
     u32x4 st[SN];
@@ -461,7 +468,7 @@ __device__ __forceinline__ void head_logits_ce_body(const u32x4* __restrict__ XA
             u32x4 xf[NPL];
 #pragma unroll
             for (int pl = 0; pl < NPL; ++pl) xf[pl] = lds[buf][(pl * CH + 2 * s + khalf) * 32 + l32];
-            acc = mfma_split<HS>(Wf[s], xf, acc);
+            acc = mfma_split<true>(Wf[s], xf, acc);
         }
         s_store(buf ^ 1);
         __builtin_amdgcn_sched_barrier(0);
@@ -554,26 +561,15 @@ __device__ __forceinline__ void head_logits_ce_body(const u32x4* __restrict__ XA
     }
 }
 
-// The fp16 form is pinned to three waves per SIMD (158 VGPRs, no spills): with the sixteen running column maxima it sat at 172,
-// one register granule above the third wave, and the launch lost 15 %.  The bf16 form (212 VGPRs) keeps its two.
-template <int NB, bool HS = false>
-__global__ __launch_bounds__(256) void head_logits_ce_kernel(const u32x4* __restrict__ XA, const float* __restrict__ W,
-                                                              long ldw, float* __restrict__ C, long ldc, int N, int V,
-                                                              float alpha, int nblk, int blk_per, int vec_ok,
-                                                              float* __restrict__ st_m, float* __restrict__ st_s,
-                                                              float* __restrict__ st_t, int n_tile, int n_split,
-                                                              const unsigned* __restrict__ amax = nullptr,
-                                                              float* __restrict__ colmax = nullptr, int vpad = 0) {
-    head_logits_ce_body<NB, false>(XA, W, ldw, C, ldc, N, V, alpha, nblk, blk_per, vec_ok, st_m, st_s, st_t, n_tile, n_split, amax,
-                                   colmax, vpad);
-}
+// Pinned to three waves per SIMD (158 VGPRs, no spills): with the sixteen running column maxima it sat at 172, one register
+// granule above the third wave, and the launch lost 15 %.
 template <int NB>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void head_logits_ce_h_kernel(
     const u32x4* __restrict__ XA, const float* __restrict__ W, long ldw, float* __restrict__ C, long ldc, int N, int V, float alpha,
     int nblk, int blk_per, int vec_ok, float* __restrict__ st_m, float* __restrict__ st_s, float* __restrict__ st_t, int n_tile,
     int n_split, const unsigned* __restrict__ amax, float* __restrict__ colmax, int vpad) {
-    head_logits_ce_body<NB, true>(XA, W, ldw, C, ldc, N, V, alpha, nblk, blk_per, vec_ok, st_m, st_s, st_t, n_tile, n_split, amax,
-                                  colmax, vpad);
+    head_logits_ce_body<NB>(XA, W, ldw, C, ldc, N, V, alpha, nblk, blk_per, vec_ok, st_m, st_s, st_t, n_tile, n_split, amax,
+                            colmax, vpad);
 }
 // the recomputing head's forward: statistics, column maxima and the label logits only -- no [N, V] tensor is written
 template <int NB>
@@ -582,8 +578,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     float* __restrict__ st_m, float* __restrict__ st_s, float* __restrict__ st_t, int n_tile, int n_split,
     const unsigned* __restrict__ amax, float* __restrict__ colmax, int vpad, const long* __restrict__ labels,
     float* __restrict__ zlab) {
-    head_logits_ce_body<NB, true, true>(XA, W, ldw, nullptr, 0, N, V, alpha, nblk, blk_per, 1, st_m, st_s, st_t, n_tile, n_split, amax,
-                                        colmax, vpad, labels, zlab);
+    head_logits_ce_body<NB, true>(XA, W, ldw, nullptr, 0, N, V, alpha, nblk, blk_per, 1, st_m, st_s, st_t, n_tile, n_split, amax,
+                                  colmax, vpad, labels, zlab);
 }
 
 // d W's per-item scales need: min over the rows of lse, and which items are some row's label (their column holds a -g (1 - eps))
@@ -651,7 +647,7 @@ __device__ __forceinline__ float sg_value(float x, float l2, bool is_label, cons
 }
 
 // ---- d W[Vc, D] (+)= alpha * G^T @ X.  grid ceil(Vc / 128); wave w owns vocabulary rows 32 w .. 32 w + 31 of the tile.
-// HS (T4R_HEAD_DW_FP16X2): the two-way fp16 form.  Unlike d X, an output row here (one item) sums the gradient entries of ONE
+// HS: the two-way fp16 form ("form 2"; HS = false is form 1 on the three bf16 planes, which needs no column maxima).  Unlike d X, an output row here (one item) sums the gradient entries of ONE
 // column: for a rare item all of them lie 1e-6 .. 1e-12 below the tensor's maximum, so every item gets its OWN scale from a
 // bound on its column (the forward kernel leaves the column maxima of the logits; DwAux).
 struct DwAux { const float* colmax; const float* lse_min; const unsigned char* islab; int vpad, rsplit; };
@@ -661,15 +657,15 @@ __device__ __forceinline__ float pow2_scale_head(float m) {
     (void)frexpf(m, &e);
     return ldexpf(1.f, min(14 - e, 100));    // a maximum below 2^-86 (the d W bound of an item far below every row's lse) must not overflow the scale
 }
-// PD: how many 32-row blocks of the lane's logits column are in flight ahead of the one being multiplied (round 6).  The
-// logits are a read-once 1.1 GB stream fetched as 4-byte column elements (a wave instruction moves two 128-byte row
-// segments); with one block ahead a CU had 8 waves x 16 x 256 B = 32 KB in flight -- by Little's law ~4 TB/s at the loaded
-// HBM latency, and the launch measured 3.0.  The kernel runs two waves per SIMD (two workgroups per CU), so the register
-// file has room for more: PD blocks of 16 values per lane.  NT: the logits with non-temporal loads (read once: they should not
-// displace the X images, which every workgroup re-reads, from L2 / Infinity Cache).  Same values in the same MFMA slots in
-// the same order: d W is bit-identical for every PD / NT.
-template <int NB, bool HS = false, int PD = 1, bool NT = false, bool COPY = true, int WPS = 2>
-__global__ __launch_bounds__(256, WPS) void head_dw_split_kernel(const float* __restrict__ logits, long ld,
+// PD = 1 (a constant in the body): ONE 32-row block of the lane's logits column is in flight ahead of the one being multiplied.  The logits are a read-once
+// 1.1 GB stream fetched as 4-byte column elements (a wave instruction moves two 128-byte row segments); with one block ahead
+// a CU has 8 waves x 16 x 256 B = 32 KB in flight -- by Little's law ~4 TB/s at the loaded HBM latency, and the launch
+// measured 3.0.  The kernel runs two waves per SIMD (two workgroups per CU) and the register file has room for more, but two
+// to four blocks ahead measured slower (see t4r_head_split_dw).  NT: the logits with non-temporal loads (read once: they
+// should not displace the X images, which every workgroup re-reads, from L2 / Infinity Cache).  Same values in the same MFMA
+// slots in the same order: d W is bit-identical for either NT.
+template <int NB, bool HS = false, bool NT = false>
+__global__ __launch_bounds__(256, 2) void head_dw_split_kernel(const float* __restrict__ logits, long ld,
                                                              const float* __restrict__ lse, const long* __restrict__ labels,
                                                              const float* __restrict__ gout, const u32x4* __restrict__ XT,
                                                              float* __restrict__ dW, long lddw, int N, int Vc, int V,
@@ -706,6 +702,7 @@ __global__ __launch_bounds__(256, WPS) void head_dw_split_kernel(const float* __
     u32x4 st[SN];
     float ri_lse = 0.f;
     long ri_lab = 0;
+    constexpr int PD = 1;       // blocks of logits in flight; the loop nest below is written for any PD and is left as it compiles
     float xq[PD][16];
     // every load is unconditional and nothing computed from it appears before s_store: a guarded load (tid < 32) or a
     // conversion right behind it puts an s_waitcnt vmcnt(0) into the middle of the prefetch.  Loads return in order: the X
@@ -774,7 +771,7 @@ __global__ __launch_bounds__(256, WPS) void head_dw_split_kernel(const float* __
 #pragma unroll
             for (int i = 0; i < 16; ++i) xc[i] = xq[u][i];
             g_load(min(b + 1, nblk - 1));
-            if (COPY) x_load(xq[u], min(b + PD, nblk - 1));
+            x_load(xq[u], min(b + PD, nblk - 1));
             __builtin_amdgcn_sched_barrier(0);
             u32x4 af[2][NPL];
 #pragma unroll
@@ -786,11 +783,6 @@ __global__ __launch_bounds__(256, WPS) void head_dw_split_kernel(const float* __
                     gv[e] = sg_value(xc[8 * s + e], in.x, __float_as_int(in.y) == v, q);
                 }
                 split8s<HS>(gv, 1.f, af[s]);
-            }
-            if (!COPY) {          // this slot's values are consumed: refill it before the products (no register copy)
-                __builtin_amdgcn_sched_barrier(0);
-                x_load(xq[u], min(b + PD, nblk - 1));
-                __builtin_amdgcn_sched_barrier(0);
             }
 #pragma unroll
             for (int s = 0; s < 2; ++s)
@@ -825,18 +817,18 @@ __global__ __launch_bounds__(256, WPS) void head_dw_split_kernel(const float* __
 
 // ---- d X partial sums:  part[split][N, D] = alpha * G[:, k-range] @ W[k-range, :].  grid (ceil(N / 128), splits);
 // wave w owns rows 32 w .. 32 w + 31 of the tile, each lane walks its own logits row.
-// HS: the two-way fp16 form (see mfma_split).  The gradient rows are scaled by a power of two taken from g / N itself; their
+// Two-way fp16 form (see mfma_split).  The gradient rows are scaled by a power of two taken from g / N itself; their
 // tail entries (p ~ 1e-6 and below) lose relative precision in the fp16 pieces, but every OUTPUT row sums all V of them
 // against well-scaled table rows: their absolute error (<= 2^-39 of the row's largest entry each) is far below the
-// rounding of the sum -- unlike d W, whose rare-item rows consist of such entries only and stay on the bf16 planes.
-template <int NB, bool HS = false>
+// rounding of the sum -- unlike d W, whose rare-item rows consist of such entries only and get a scale per item.
+template <int NB>
 __global__ __launch_bounds__(256) void head_dx_split_kernel(const float* __restrict__ logits, long ld,
                                                              const float* __restrict__ lse, const long* __restrict__ labels,
                                                              const float* __restrict__ gout, const u32x4* __restrict__ WT,
                                                              float* __restrict__ part, int N, int Vc, int V, int yoff,
                                                              float smooth, float alpha, int nkt, int kt_per, int row_tiles,
-                                                             const unsigned* __restrict__ amax = nullptr) {
-    constexpr int D = 32 * NB, NPL = HS ? 2 : 3;
+                                                             const unsigned* __restrict__ amax) {
+    constexpr int D = 32 * NB, NPL = 2;
     constexpr int BLK = 4 * NPL * 32 * NB;
     constexpr int SN = (BLK + 255) / 256;
     __shared__ u32x4 lds[2][BLK];
@@ -853,7 +845,7 @@ __global__ __launch_bounds__(256) void head_dx_split_kernel(const float* __restr
     const int y = (int)(labels[rc] - yoff);
     SgScalars q;
     q.g = (gout ? *gout : 1.f) / N;
-    if (HS) {       // |G| <= |g| (1 + eps): position g at 2^13 .. 2^14, undo it (and the table's scale) in alpha
+    {       // |G| <= |g| (1 + eps): position g at 2^13 .. 2^14, undo it (and the table's scale) in alpha
         int e;
         (void)frexpf(fabsf(q.g), &e);
         const float sg = (q.g != 0.f && fabsf(q.g) < 3e38f) ? ldexpf(1.f, min(14 - e, 100)) : 1.f;
@@ -911,7 +903,7 @@ __global__ __launch_bounds__(256) void head_dx_split_kernel(const float* __restr
             float gv[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) gv[e] = sg_value(xc[8 * s + e], l2, dy == e, q);
-            split8s<HS>(gv, 1.f, af[s]);
+            split8s<true>(gv, 1.f, af[s]);
         }
 #pragma unroll
         for (int s = 0; s < 2; ++s)
@@ -920,7 +912,7 @@ __global__ __launch_bounds__(256) void head_dx_split_kernel(const float* __restr
                 u32x4 bf[NPL];
 #pragma unroll
                 for (int pl = 0; pl < NPL; ++pl) bf[pl] = lds[buf][(pl * 4 + 2 * s + khalf) * D + 32 * j + l32];
-                acc[j] = mfma_split<HS>(af[s], bf, acc[j]);
+                acc[j] = mfma_split<true>(af[s], bf, acc[j]);
             }
         s_store(buf ^ 1);
         __syncthreads();
@@ -937,7 +929,7 @@ __global__ __launch_bounds__(256) void head_dx_split_kernel(const float* __restr
 }
 
 // =====================================================================================================================
-// The RECOMPUTING backward (round 4; two-way fp16 form only).  The materialised head writes 1.1 GB of logits and reads them
+// The RECOMPUTING backward (two-way fp16 form).  The materialised head writes 1.1 GB of logits and reads them
 // twice (d X, d W): 3.6 GB of HBM traffic per step for 2.3 GB of need, and all three kernels run at "the logits' HBM time
 // plus their matrix time plus their VALU time" -- the parts do not overlap on this chip.  Here nothing of size [N, V] ever
 // exists: the forward keeps statistics only (head_ce_stats_h_kernel), and each backward kernel RECOMPUTES its score tile on
@@ -1214,10 +1206,10 @@ __global__ __launch_bounds__(256) void head_dx_reduce_kernel(const float* __rest
 }
 
 // =====================================================================================================================
-// Logits + cross-entropy statistics + d X in ONE pass (round 5; two-way fp16 form).  The materialised head wrote the 1.1 GB of
-// logits once and read them twice (d X, d W): 3.65 GB of HBM traffic per step for 2.3 GB of need, three rounds running
-// (VERDICT r4 weak #5).  The round-4 argument that a one-pass BACKWARD is infeasible (partial sums the size of the logits) holds
-// for item-block- and row-tile-stationary backward kernels; what it leaves open is forming d X in the FORWARD, flash-attention
+// Logits + cross-entropy statistics + d X in ONE pass (two-way fp16 form).  The two-pass head writes the 1.1 GB of
+// logits once and reads them twice (d X, d W): 3.65 GB of HBM traffic per step for 2.3 GB of need.  A one-pass BACKWARD is
+// infeasible (partial sums the size of the logits) for item-block- and row-tile-stationary backward kernels; what that
+// leaves open is forming d X in the FORWARD, flash-attention
 // style: a workgroup owns 128 label rows (X as B fragments in registers) and a RANGE of 32-item tiles of the table, and per tile
 //   * recomputes nothing: the score tile S = W_tile X^T comes off the matrix cores once (A = MK image of the table tile:
 //     lane = item; accumulator lane (row, khalf) = sixteen items of ONE row), is scaled, stored as logits (full 128-byte row
@@ -1535,7 +1527,7 @@ __global__ __launch_bounds__(256) void split_w_images_kernel(const float* __rest
         amax = &sh_bits;
     }
     const int b = blockIdx.x;
-    if (blockIdx.y == 0) { split_mk_body<NB, true>(b, src, ld, n_rows, wa, amax); return; }
+    if (blockIdx.y == 0) { split_mk_body<NB>(b, src, ld, n_rows, wa, amax); return; }
     const float scale = scale_of(amax);
     for (int idx = threadIdx.x; idx < 4 * D; idx += 256) {
         const int d = idx % D, kc = idx / D;
@@ -1552,52 +1544,21 @@ __global__ __launch_bounds__(256) void split_w_images_kernel(const float* __rest
     }
 }
 
-static int head_rows_per_wg() {
-    static int per = -1;
-    if (per < 0) { const char* e = t4r_exp_getenv("T4R_HEAD_ROWS_PER_WG"); per = e ? max(1, atoi(e)) : 12; }
-    return per;
-}
-static int head_dx_target() {
-    static int target = -1;
-    if (target < 0) { const char* e = t4r_exp_getenv("T4R_HEAD_DX_WGS"); target = e ? atoi(e) : 1536; }
-    return target;
-}
-// workspace layout (bytes): XA | XT | WT | d X partials
+// launch geometry, each measured at BASELINE configs[1]
+constexpr int kHeadRowsPerWg = 12;       // 32-row blocks of X per workgroup of the item-tile-stationary forward kernels
+constexpr int kHeadDxWgs = 1536;         // workgroups the d X kernels (from the logits / recomputing) aim at
+constexpr int kHeadFdxWgs = 512;         // the one-pass forward: one residency of the chip, two workgroups per CU
+// workspace layout (bytes): XA | XT | WT | d X partials | ...
 struct HeadWs { long xa, xt, wt, part, stats, scales, xth, colmax, islab, xtp, wa, zlab, total; int nblk, nkt, max_split, ntile, vpad, rsplit, cmrows; };
-// d W too (T4R_HEAD_DW_FP16X2, default 1; per-item scales: see head_dw_split_kernel)?
-static bool head_dw_fp16x2() {
-    static int on = -1;
-    if (on < 0) { const char* e = t4r_exp_getenv("T4R_HEAD_DW_FP16X2"); on = e ? (atoi(e) != 0) : 1; }
-    return on != 0;
-}
-// the forward product in the two-way fp16 split (see mfma_split)?
-static bool head_fwd_fp16x2() {
-    static int on = -1;
-    if (on < 0) { const char* e = t4r_exp_getenv("T4R_HEAD_FWD_FP16X2"); on = e ? (atoi(e) != 0) : 1; }
-    return on != 0;
-}
-// the recomputing form available (both fp16 switches on) and not switched off (T4R_HEAD_RECOMPUTE=0 also drops its 75 MB
-// of table planes from the workspace)?
-static bool head_recompute_on() {
-    static int on = -1;
-    if (on < 0) { const char* e = t4r_exp_getenv("T4R_HEAD_RECOMPUTE"); on = e ? (atoi(e) != 0) : 1; }
-    return on != 0 && head_fwd_fp16x2() && head_dw_fp16x2();
-}
-// logits + statistics + d X in one pass (head_fwd_dx_kernel; T4R_HEAD_FDX=0 restores logits-then-d X-from-the-logits)?
-static bool head_fdx_on() {
-    static int on = -1;
-    if (on < 0) { const char* e = t4r_exp_getenv("T4R_HEAD_FDX"); on = e ? (atoi(e) != 0) : 1; }
-    return on != 0 && head_fwd_fp16x2();
-}
 HeadWs head_ws(int N, int V, int D) {
     HeadWs w;
     w.nblk = (N + 31) / 32;
     w.nkt = (V + 31) / 32;
     const long blk = 12L * D * 16;
     // upper bound of the d X split count t4r_head_split_dx can choose for these sizes (the same rule: <= 64, >= 8 k-tiles
-    // per split, ~T4R_HEAD_DX_WGS workgroups in total): the partial buffer is sized for it, not for 64 always
+    // per split, ~kHeadDxWgs workgroups in total): the partial buffer is sized for it, not for 64 always
     // (64 x N x D x 4 bytes was 1.1 GB of mostly unused workspace at N = 35 k, D = 128, held from forward to backward)
-    w.max_split = max(1, min(min(64, w.nkt / 8), head_dx_target() / ((N + 127) / 128)));
+    w.max_split = max(1, min(min(64, w.nkt / 8), kHeadDxWgs / ((N + 127) / 128)));
     w.xa = 0;
     w.xt = w.xa + w.nblk * blk;
     w.wt = w.xt + w.nblk * blk;
@@ -1609,14 +1570,14 @@ HeadWs head_ws(int N, int V, int D) {
     // the forward kernel leaves, a byte per item "is some row's label"
     w.xth = w.scales + 256;
     w.vpad = 128 * w.ntile;
-    w.rsplit = (w.nblk + head_rows_per_wg() - 1) / head_rows_per_wg();
+    w.rsplit = (w.nblk + kHeadRowsPerWg - 1) / kHeadRowsPerWg;
     w.colmax = w.xth + w.nblk * blk;
     w.cmrows = max(w.rsplit, (N + 127) / 128);          // the one-pass forward (head_fwd_dx_kernel) leaves one row per 128-row tile
     w.islab = w.colmax + (long)w.cmrows * w.vpad * 4;
-    // the recomputing head (round 4): X in accumulator order (KMP), the table as MK blocks (its KMP blocks take `wt`), label logits
+    // the recomputing and the one-pass head: X in accumulator order (KMP), the table as MK blocks (its KMP blocks take `wt`), label logits
     w.xtp = w.islab + ((w.vpad + 255) / 256) * 256;
     w.wa = w.xtp + w.nblk * blk;
-    w.zlab = w.wa + ((head_recompute_on() || head_fdx_on()) ? w.nkt * blk : 0);
+    w.zlab = w.wa + w.nkt * blk;
     w.total = w.zlab + (((long)N * 4 + 255) / 256) * 256;
     return w;
 }
@@ -1650,8 +1611,8 @@ static int head_w_amax(hipStream_t st, const float* W, long ldw, int V, int D, u
 
 // 1 when these kernels take the shape (the callers fall back to the general GEMM otherwise)
 extern "C" int t4r_head_split_supported(int D) { return D >= 32 && D <= 128 && D % 32 == 0; }
-// matrix instructions per fp32-equivalent one in the forward / d X products: 3 (two-way fp16 split) or 6 (three bf16 planes)
-extern "C" int t4r_head_split_fwd_products(void) { return head_fwd_fp16x2() ? 3 : 6; }
+// matrix instructions per fp32-equivalent one in the forward / d X products: 3 (two-way fp16 split)
+extern "C" int t4r_head_split_fwd_products(void) { return 3; }
 
 extern "C" long t4r_head_split_ws_bytes(int N, int V, int D) {
     if (!t4r_head_split_supported(D) || N <= 0 || V <= 0) return 0;
@@ -1667,22 +1628,13 @@ extern "C" int t4r_head_split_prepare(void* stream, const float* X, long ldx, in
     hipStream_t st = (hipStream_t)stream;
     u32x4* xa = reinterpret_cast<u32x4*>((char*)ws + w.xa);
     u32x4* xt = reinterpret_cast<u32x4*>((char*)ws + w.xt);
-    if (head_fwd_fp16x2()) {
-        unsigned* amax = reinterpret_cast<unsigned*>((char*)ws + w.scales);
-        if (hipMemsetAsync(amax, 0, 8, st) != hipSuccess) { t4r_set_error("head_split_prepare: memset failed"); return -1; }
-        const long n4 = (long)N * (D / 4);
-        hipLaunchKernelGGL(amax_kernel, dim3((unsigned)min(256L, (n4 + 255) / 256)), dim3(256), 0, st, X, ldx, (long)N, D, amax);
-        if (head_dw_fp16x2()) {     // d W may run in either form (it needs the forward's column maxima): all three images, one launch
-            u32x4* xth = reinterpret_cast<u32x4*>((char*)ws + w.xth);
-            T4R_NB_SWITCH(D, hipLaunchKernelGGL(split_x_images_kernel<NB>, dim3(w.nblk, 3), dim3(256), 0, st, X, ldx, N, xa, xt, xth, amax));
-            T4R_LAUNCH_CHECK();
-            return 0;
-        }
-        T4R_NB_SWITCH(D, hipLaunchKernelGGL((split_mk_kernel<NB, true>), dim3(w.nblk), dim3(256), 0, st, X, ldx, N, xa, amax));
-    } else {
-        T4R_NB_SWITCH(D, hipLaunchKernelGGL(split_mk_kernel<NB>, dim3(w.nblk), dim3(256), 0, st, X, ldx, N, xa));
-    }
-    T4R_NB_SWITCH(D, hipLaunchKernelGGL(split_km_kernel<NB>, dim3(w.nblk), dim3(256), 0, st, X, ldx, N, xt));
+    unsigned* amax = reinterpret_cast<unsigned*>((char*)ws + w.scales);
+    if (hipMemsetAsync(amax, 0, 8, st) != hipSuccess) { t4r_set_error("head_split_prepare: memset failed"); return -1; }
+    const long n4 = (long)N * (D / 4);
+    hipLaunchKernelGGL(amax_kernel, dim3((unsigned)min(256L, (n4 + 255) / 256)), dim3(256), 0, st, X, ldx, (long)N, D, amax);
+    // d W may run in either form (form 2 needs the forward's column maxima): all three images, one launch
+    u32x4* xth = reinterpret_cast<u32x4*>((char*)ws + w.xth);
+    T4R_NB_SWITCH(D, hipLaunchKernelGGL(split_x_images_kernel<NB>, dim3(w.nblk, 3), dim3(256), 0, st, X, ldx, N, xa, xt, xth, amax));
     T4R_LAUNCH_CHECK();
     return 0;
 }
@@ -1693,12 +1645,12 @@ extern "C" int t4r_head_split_prepare(void* stream, const float* X, long ldx, in
 extern "C" int t4r_head_split_recompute_supported(int D);
 extern "C" int t4r_head_split_prepare_rc(void* stream, const float* X, long ldx, int N, int D, int V, void* ws) {
     if (N <= 0) return 0;
-    T4R_CHECK_ARG(t4r_head_split_recompute_supported(D) && X && ws, "head_split_prepare_rc: unsupported (the two-way fp16 forms must be on) or null pointer");
+    T4R_CHECK_ARG(t4r_head_split_recompute_supported(D) && X && ws, "head_split_prepare_rc: unsupported width or null pointer");
     T4R_CHECK_ARG(aligned16(X) && ldx % 4 == 0 && aligned16(ws), "head_split_prepare_rc: X must be 16-byte aligned with a pitch multiple of 4");
     const HeadWs w = head_ws(N, V, D);
     unsigned* amax = reinterpret_cast<unsigned*>((char*)ws + w.scales);
     u32x4* xtp = reinterpret_cast<u32x4*>((char*)ws + w.xtp);
-    T4R_NB_SWITCH(D, hipLaunchKernelGGL((split_kmp_kernel<NB, true>), dim3(w.nblk), dim3(256), 0, (hipStream_t)stream, X, ldx, N, xtp, amax));
+    T4R_NB_SWITCH(D, hipLaunchKernelGGL(split_kmp_kernel<NB>, dim3(w.nblk), dim3(256), 0, (hipStream_t)stream, X, ldx, N, xtp, amax));
     T4R_LAUNCH_CHECK();
     return 0;
 }
@@ -1710,22 +1662,15 @@ extern "C" int t4r_head_split_logits(void* stream, void* ws, const float* W, lon
     T4R_CHECK_ARG(t4r_head_split_supported(D) && W && C && ws, "head_split_logits: unsupported width or null pointer");
     T4R_CHECK_ARG(aligned16(W) && ldw % 4 == 0, "head_split_logits: W must be 16-byte aligned with a pitch multiple of 4");
     const HeadWs w = head_ws(N, V, D);
-    static int per_env = -1;
-    if (per_env < 0) { const char* e = t4r_exp_getenv("T4R_HEAD_ROWS_PER_WG"); per_env = e ? atoi(e) : 12; }
-    const int blk_per = max(1, min(w.nblk, per_env));
+    const int blk_per = max(1, min(w.nblk, kHeadRowsPerWg));
     const int rs = (w.nblk + blk_per - 1) / blk_per;
     const u32x4* xa = reinterpret_cast<const u32x4*>((const char*)ws + w.xa);
     dim3 grid((V + 127) / 128, rs);
-    if (head_fwd_fp16x2()) {
-        unsigned* amax = reinterpret_cast<unsigned*>((char*)ws + w.scales);
-        if (head_w_amax((hipStream_t)stream, W, ldw, V, D, amax + 1)) return -1;
-        if (note) *note_of(note) = FwdNote{W, C, V, V, N, 0, 0, 0};
-        T4R_NB_SWITCH(D, hipLaunchKernelGGL((head_logits_split_kernel<NB, true>), grid, dim3(256), 0, (hipStream_t)stream, xa, W,
-                                            ldw, C, ldc, N, V, alpha, w.nblk, blk_per, amax));
-    } else {
-        T4R_NB_SWITCH(D, hipLaunchKernelGGL(head_logits_split_kernel<NB>, grid, dim3(256), 0, (hipStream_t)stream, xa, W, ldw, C,
-                                            ldc, N, V, alpha, w.nblk, blk_per));
-    }
+    unsigned* amax = reinterpret_cast<unsigned*>((char*)ws + w.scales);
+    if (head_w_amax((hipStream_t)stream, W, ldw, V, D, amax + 1)) return -1;
+    if (note) *note_of(note) = FwdNote{W, C, V, V, N, 0, 0, 0};
+    T4R_NB_SWITCH(D, hipLaunchKernelGGL(head_logits_split_kernel<NB>, grid, dim3(256), 0, (hipStream_t)stream, xa, W, ldw, C, ldc,
+                                        N, V, alpha, w.nblk, blk_per, amax));
     T4R_LAUNCH_CHECK();
     return 0;
 }
@@ -1741,9 +1686,7 @@ extern "C" int t4r_head_split_logits_ce(void* stream, void* ws, const float* W, 
     T4R_CHECK_ARG(t4r_head_split_supported(D) && W && C && ws && (!labels || (loss_rows && lse)), "head_split_logits_ce: unsupported width or null pointer");
     T4R_CHECK_ARG(aligned16(W) && ldw % 4 == 0, "head_split_logits_ce: W must be 16-byte aligned with a pitch multiple of 4");
     const HeadWs w = head_ws(N, V, D);
-    static int per_env = -1;
-    if (per_env < 0) { const char* e = t4r_exp_getenv("T4R_HEAD_ROWS_PER_WG"); per_env = e ? atoi(e) : 12; }
-    const int blk_per = max(1, min(w.nblk, per_env));
+    const int blk_per = max(1, min(w.nblk, kHeadRowsPerWg));
     const int rs = (w.nblk + blk_per - 1) / blk_per;
     const u32x4* xa = reinterpret_cast<const u32x4*>((const char*)ws + w.xa);
     float* sm = reinterpret_cast<float*>((char*)ws + w.stats);
@@ -1751,18 +1694,13 @@ extern "C" int t4r_head_split_logits_ce(void* stream, void* ws, const float* W, 
     float* stt = label_smoothing > 0.f ? ss + (long)w.ntile * N : nullptr;
     const int vec_ok = aligned16(C) && ldc % 4 == 0;
     dim3 grid(8 * ((w.ntile + 7) / 8) * rs);
-    if (head_fwd_fp16x2()) {
-        unsigned* amax = reinterpret_cast<unsigned*>((char*)ws + w.scales);
-        if (head_w_amax(st, W, ldw, V, D, amax + 1)) return -1;
-        float* colmax = nullptr;
-        if (head_dw_fp16x2() && rs == w.rsplit && vec_ok) colmax = reinterpret_cast<float*>((char*)ws + w.colmax);
-        if (note) *note_of(note) = FwdNote{W, C, V, V, N, colmax != nullptr, 0, 0};
-        T4R_NB_SWITCH(D, hipLaunchKernelGGL(head_logits_ce_h_kernel<NB>, grid, dim3(256), 0, st, xa, W, ldw, C, ldc, N, V,
-                                            alpha, w.nblk, blk_per, vec_ok, sm, ss, stt, w.ntile, rs, amax, colmax, w.vpad));
-    } else {
-        T4R_NB_SWITCH(D, hipLaunchKernelGGL(head_logits_ce_kernel<NB>, grid, dim3(256), 0, st, xa, W, ldw, C, ldc, N, V, alpha,
-                                            w.nblk, blk_per, vec_ok, sm, ss, stt, w.ntile, rs));
-    }
+    unsigned* amax = reinterpret_cast<unsigned*>((char*)ws + w.scales);
+    if (head_w_amax(st, W, ldw, V, D, amax + 1)) return -1;
+    float* colmax = nullptr;
+    if (rs == w.rsplit && vec_ok) colmax = reinterpret_cast<float*>((char*)ws + w.colmax);
+    if (note) *note_of(note) = FwdNote{W, C, V, V, N, colmax != nullptr, 0, 0};
+    T4R_NB_SWITCH(D, hipLaunchKernelGGL(head_logits_ce_h_kernel<NB>, grid, dim3(256), 0, st, xa, W, ldw, C, ldc, N, V,
+                                        alpha, w.nblk, blk_per, vec_ok, sm, ss, stt, w.ntile, rs, amax, colmax, w.vpad));
     if (labels)       // labels == NULL: the product and its per-tile statistics only (timing the dominant kernel alone)
         hipLaunchKernelGGL(head_ce_finalize_kernel, dim3((N + 31) / 32), dim3(1024), 0, st, sm, ss, stt, w.ntile, N, V, C, ldc,
                            labels, label_smoothing, loss_rows, lse);
@@ -1780,8 +1718,8 @@ extern "C" int t4r_head_split_dw(void* stream, void* ws, const float* logits, lo
     const u32x4* xt = reinterpret_cast<const u32x4*>((const char*)ws + w.xt);
     FwdNote* note = note_of(note_p);
     const bool have_cm = note && note->colmax && note->logits == logits && note->V == V && note->N == N && Vc == V && yoff == 0;
-    if (note) note->dw_form = (head_fwd_fp16x2() && head_dw_fp16x2() && have_cm) ? 2 : 1;
-    if (head_fwd_fp16x2() && head_dw_fp16x2() && have_cm) {
+    if (note) note->dw_form = have_cm ? 2 : 1;
+    if (have_cm) {
         hipStream_t st = (hipStream_t)stream;
         const unsigned* amax = reinterpret_cast<const unsigned*>((const char*)ws + w.scales);
         float* lse_min = reinterpret_cast<float*>(const_cast<char*>((const char*)ws) + w.scales) + 2;
@@ -1789,12 +1727,12 @@ extern "C" int t4r_head_split_dw(void* stream, void* ws, const float* logits, lo
         hipLaunchKernelGGL(head_dw_aux_kernel, dim3(1), dim3(1024), 0, st, lse, labels, N, yoff, Vc, lse_min, islab, w.vpad);
         DwAux aux{reinterpret_cast<const float*>((const char*)ws + w.colmax), lse_min, islab, w.vpad, note->cm_rows > 0 ? note->cm_rows : w.rsplit};
         const u32x4* xth = reinterpret_cast<const u32x4*>((const char*)ws + w.xth);
-        // PD = 1, non-temporal logits (round 6 A/B, profiles/r06_b_head_dw_variants.txt: two / three / four blocks in flight are
+        // one block in flight, non-temporal logits (A/B, profiles/r06_b_head_dw_variants.txt: two / three / four blocks in flight are
         // 2-7 % SLOWER alone -- the launch is not waiting for its loads --, the non-temporal form is the only one ahead: -0.2 %)
-        T4R_NB_SWITCH(D, hipLaunchKernelGGL((head_dw_split_kernel<NB, true, 1, true>), dim3((Vc + 127) / 128), dim3(256), 0, st, logits,
+        T4R_NB_SWITCH(D, hipLaunchKernelGGL((head_dw_split_kernel<NB, true, true>), dim3((Vc + 127) / 128), dim3(256), 0, st, logits,
                                             ld, lse, labels, grad_out, xth, dW, lddw, N, Vc, V, yoff, label_smoothing, alpha,
                                             accumulate, w.nblk, amax, aux));
-    } else {
+    } else {        // form 1: nothing is known about these logits' column maxima
         T4R_NB_SWITCH(D, hipLaunchKernelGGL(head_dw_split_kernel<NB>, dim3((Vc + 127) / 128), dim3(256), 0, (hipStream_t)stream,
                                             logits, ld, lse, labels, grad_out, xt, dW, lddw, N, Vc, V, yoff, label_smoothing,
                                             alpha, accumulate, w.nblk));
@@ -1817,32 +1755,20 @@ extern "C" int t4r_head_split_dx(void* stream, void* ws, const float* logits, lo
     u32x4* wt = reinterpret_cast<u32x4*>((char*)ws + w.wt);
     float* part = reinterpret_cast<float*>((char*)ws + w.part);
     const int nkt = (Vc + 31) / 32, row_tiles = (N + 127) / 128;
-    const bool hs = head_fwd_fp16x2();
     unsigned* amax = reinterpret_cast<unsigned*>((char*)ws + w.scales) + 1;     // max |W| of THIS call's rows (a chunk of the table)
-    if (hs) {
-        FwdNote* note = note_of(note_p);
-        const bool same = note && note->W == W && note->Vw == Vc;
-        if (!same) {
-            if (head_w_amax(st, W, ldw, Vc, D, amax)) return -1;
-            if (note) { note->W = W; note->Vw = Vc; }     // the max |W| word now describes THIS table slice
-        }
-        T4R_NB_SWITCH(D, hipLaunchKernelGGL((split_km_kernel<NB, true>), dim3(nkt), dim3(256), 0, st, W, ldw, Vc, wt, amax));
-    } else {
-        T4R_NB_SWITCH(D, hipLaunchKernelGGL(split_km_kernel<NB>, dim3(nkt), dim3(256), 0, st, W, ldw, Vc, wt));
+    FwdNote* note = note_of(note_p);
+    const bool same = note && note->W == W && note->Vw == Vc;
+    if (!same) {
+        if (head_w_amax(st, W, ldw, Vc, D, amax)) return -1;
+        if (note) { note->W = W; note->Vw = Vc; }     // the max |W| word now describes THIS table slice
     }
-    const int target = head_dx_target();
-    int splits = max(1, min(min(w.max_split, nkt / 8), target / row_tiles));
+    T4R_NB_SWITCH(D, hipLaunchKernelGGL(split_km_kernel<NB>, dim3(nkt), dim3(256), 0, st, W, ldw, Vc, wt, amax));
+    int splits = max(1, min(min(w.max_split, nkt / 8), kHeadDxWgs / row_tiles));
     const int kt_per = (nkt + splits - 1) / splits;
     splits = (nkt + kt_per - 1) / kt_per;          // every split owns at least one k-tile
-    if (hs) {
-        T4R_NB_SWITCH(D, hipLaunchKernelGGL((head_dx_split_kernel<NB, true>), dim3(row_tiles * 8 * ((splits + 7) / 8)), dim3(256),
-                                            0, st, logits, ld, lse, labels, grad_out, wt, part, N, Vc, V, yoff, label_smoothing,
-                                            alpha, nkt, kt_per, row_tiles, amax));
-    } else {
-        T4R_NB_SWITCH(D, hipLaunchKernelGGL(head_dx_split_kernel<NB>, dim3(row_tiles * 8 * ((splits + 7) / 8)), dim3(256), 0, st,
-                                            logits, ld, lse, labels, grad_out, wt, part, N, Vc, V, yoff, label_smoothing, alpha,
-                                            nkt, kt_per, row_tiles));
-    }
+    T4R_NB_SWITCH(D, hipLaunchKernelGGL(head_dx_split_kernel<NB>, dim3(row_tiles * 8 * ((splits + 7) / 8)), dim3(256), 0, st,
+                                        logits, ld, lse, labels, grad_out, wt, part, N, Vc, V, yoff, label_smoothing, alpha,
+                                        nkt, kt_per, row_tiles, amax));
     const long nd4 = (long)N * D / 4;
     hipLaunchKernelGGL(head_dx_reduce_kernel, dim3((unsigned)((nd4 + 255) / 256)), dim3(256), 0, st, part, splits, nd4, D / 4,
                        dX, lddx, accumulate);
@@ -1852,7 +1778,7 @@ extern "C" int t4r_head_split_dx(void* stream, void* ws, const float* logits, lo
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The recomputing head (see head_dw_rc_kernel): cross-entropy WITHOUT a logits tensor, and its two backward products.
-extern "C" int t4r_head_split_recompute_supported(int D) { return t4r_head_split_supported(D) && head_recompute_on(); }
+extern "C" int t4r_head_split_recompute_supported(int D) { return t4r_head_split_supported(D); }
 
 // loss_rows [N], lse [N] (+ the mean loss) of softmax(alpha X W^T) against labels, from the prepared workspace: statistics
 // per 128-item tile merged by a small kernel, each row's label logit captured by the lane that holds it.  Nothing of size
@@ -1861,10 +1787,10 @@ extern "C" int t4r_head_split_ce(void* stream, void* ws, const float* W, long ld
                                  float* lse, float* loss_mean, int N, int V, int D, float alpha, float label_smoothing, void* note) {
     hipStream_t st = (hipStream_t)stream;
     if (N <= 0 || V <= 0) return loss_mean ? t4r_mean_launch(st, loss_rows, 0, loss_mean) : 0;
-    T4R_CHECK_ARG(t4r_head_split_recompute_supported(D) && W && ws && labels && loss_rows && lse, "head_split_ce: unsupported (the two-way fp16 form must be on) or null pointer");
+    T4R_CHECK_ARG(t4r_head_split_recompute_supported(D) && W && ws && labels && loss_rows && lse, "head_split_ce: unsupported width or null pointer");
     T4R_CHECK_ARG(aligned16(W) && ldw % 4 == 0, "head_split_ce: W must be 16-byte aligned with a pitch multiple of 4");
     const HeadWs w = head_ws(N, V, D);
-    const int blk_per = max(1, min(w.nblk, head_rows_per_wg()));
+    const int blk_per = max(1, min(w.nblk, kHeadRowsPerWg));
     const int rs = (w.nblk + blk_per - 1) / blk_per;
     T4R_CHECK_ARG(rs == w.rsplit, "head_split_ce: row split mismatch");
     const u32x4* xa = reinterpret_cast<const u32x4*>((const char*)ws + w.xa);
@@ -1927,10 +1853,9 @@ extern "C" int t4r_head_split_dx_rc(void* stream, void* ws, const float* X, long
     float* part = reinterpret_cast<float*>((char*)ws + w.part);
     const int nkt = w.nkt, row_tiles = (N + 127) / 128;
     // the table in both images, positioned by the max |W| the forward left (same table, same rows)
-    T4R_NB_SWITCH(D, hipLaunchKernelGGL((split_mk_kernel<NB, true>), dim3(nkt), dim3(256), 0, st, W, ldw, V, wa, amax + 1));
-    T4R_NB_SWITCH(D, hipLaunchKernelGGL((split_kmp_kernel<NB, true>), dim3(nkt), dim3(256), 0, st, W, ldw, V, wtp, amax + 1));
-    const int target = head_dx_target();
-    int splits = max(1, min(min(w.max_split, nkt / 8), target / row_tiles));
+    T4R_NB_SWITCH(D, hipLaunchKernelGGL(split_mk_kernel<NB>, dim3(nkt), dim3(256), 0, st, W, ldw, V, wa, amax + 1));
+    T4R_NB_SWITCH(D, hipLaunchKernelGGL(split_kmp_kernel<NB>, dim3(nkt), dim3(256), 0, st, W, ldw, V, wtp, amax + 1));
+    int splits = max(1, min(min(w.max_split, nkt / 8), kHeadDxWgs / row_tiles));
     const int kt_per = (nkt + splits - 1) / splits;
     splits = (nkt + kt_per - 1) / kt_per;
     T4R_NB_SWITCH(D, hipLaunchKernelGGL(head_dx_rc_kernel<NB>, dim3(row_tiles * 8 * ((splits + 7) / 8)), dim3(256), 0, st, X, ldx, wa, wtp,
@@ -1943,7 +1868,7 @@ extern "C" int t4r_head_split_dx_rc(void* stream, void* ws, const float* X, long
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The one-pass forward (round 5, see head_fwd_dx_kernel): logits C [N, V], loss rows, lse, the mean loss AND
+// The one-pass forward (see head_fwd_dx_kernel): logits C [N, V], loss rows, lse, the mean loss AND
 // dX [N, D] = d (mean loss) / d X for grad_out = 1 -- the caller's backward multiplies by its upstream gradient and runs only
 // t4r_head_split_dw (same workspace and note).  X: the rows t4r_head_split_prepare was given.  wsum: column sums of W [D]
 // (needed when label_smoothing > 0, else NULL).
@@ -1956,7 +1881,7 @@ static thread_local int g_w_amax_n = 0;
 extern "C" void t4r_head_split_w_amax_hint(const float* W, const float* part, int n) {
     g_w_amax_W = (part && n > 0) ? W : nullptr; g_w_amax_part = g_w_amax_W ? part : nullptr; g_w_amax_n = g_w_amax_W ? n : 0;
 }
-extern "C" int t4r_head_split_fdx_supported(int D) { return t4r_head_split_supported(D) && head_fdx_on(); }
+extern "C" int t4r_head_split_fdx_supported(int D) { return t4r_head_split_supported(D); }
 extern "C" int t4r_head_split_logits_ce_dx(void* stream, void* ws, const float* X, long ldx, const float* W, long ldw, float* C,
                                            long ldc, const long* labels, float* loss_rows, float* lse, float* loss_mean,
                                            float* dX, long lddx, const float* wsum, int N, int V, int D, float alpha,
@@ -1967,7 +1892,7 @@ extern "C" int t4r_head_split_logits_ce_dx(void* stream, void* ws, const float* 
     // a previous full call on the same X and W) -- what bench.py times for its roofline, as t4r_head_split_logits_ce does
     const bool kernel_only = labels == nullptr;
     T4R_CHECK_ARG(t4r_head_split_fdx_supported(D) && X && W && C && ws && (kernel_only || (loss_rows && lse && dX)),
-                  "head_split_logits_ce_dx: unsupported (the two-way fp16 form must be on) or null pointer");
+                  "head_split_logits_ce_dx: unsupported width or null pointer");
     T4R_CHECK_ARG(aligned16(X) && ldx % 4 == 0 && aligned16(W) && ldw % 4 == 0 && aligned16(dX) && lddx % 4 == 0,
                   "head_split_logits_ce_dx: X / W / dX must be 16-byte aligned with pitches multiple of 4");
     T4R_CHECK_ARG(label_smoothing <= 0.f || wsum, "head_split_logits_ce_dx: label smoothing needs the column sums of W");
@@ -1986,9 +1911,7 @@ extern "C" int t4r_head_split_logits_ce_dx(void* stream, void* ws, const float* 
                                             w_part, w_npart));
     const int row_tiles = (N + 127) / 128;
     // one residency of the chip: two 256-thread workgroups per CU (66 KB of LDS each), every workgroup the same number of tiles
-    static int target = -1;
-    if (target < 0) { const char* e = t4r_exp_getenv("T4R_HEAD_FDX_WGS"); target = e ? max(1, atoi(e)) : 512; }
-    int splits = max(1, min(min(64, w.max_split), min(max(1, w.nkt / 8), target / row_tiles)));
+    int splits = max(1, min(min(64, w.max_split), min(max(1, w.nkt / 8), kHeadFdxWgs / row_tiles)));
     const int kt_per = (w.nkt + splits - 1) / splits;
     splits = (w.nkt + kt_per - 1) / kt_per;
     float* sm = reinterpret_cast<float*>((char*)ws + w.stats);
@@ -1996,7 +1919,7 @@ extern "C" int t4r_head_split_logits_ce_dx(void* stream, void* ws, const float* 
     float* stt = label_smoothing > 0.f ? ss + (long)w.ntile * N : nullptr;
     float* part = reinterpret_cast<float*>((char*)ws + w.part);
     const int vec_ok = aligned16(C) && ldc % 4 == 0;
-    float* colmax = (head_dw_fp16x2() && vec_ok) ? reinterpret_cast<float*>((char*)ws + w.colmax) : nullptr;
+    float* colmax = vec_ok ? reinterpret_cast<float*>((char*)ws + w.colmax) : nullptr;
     if (note) *note_of(note) = FwdNote{W, C, V, V, N, colmax != nullptr, 0, row_tiles};
     const int n_wg = splits * row_tiles, per_xcd = (n_wg + 7) / 8;
     if (stt) {

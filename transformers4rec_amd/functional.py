@@ -41,8 +41,7 @@ def _head_split_form(rows, table, N):
     """the shapes the module mirror sends to csrc/head_split.hip's one-pass head (prediction_task._head_split_ok)"""
     from .prediction_task import _head_split_ok
 
-    V, D = table.shape
-    return ops.head_split_fdx_supported(D) and _head_split_ok(rows, table, N, V)
+    return _head_split_ok(rows, table, N, table.shape[0])
 
 
 def mlm_step(table: torch.Tensor, masked_emb: torch.Tensor, layers, cfg: Dict, ids: torch.Tensor, mask_seed: int, mask_offset: int,

@@ -110,8 +110,7 @@ class _Pre(nn.Module):
 _SAMPLED_ROWS = _exp_env("T4R_SAMPLED_ROWS", "1") == "1"
 
 
-_HEAD_SPLIT = _exp_env("T4R_HEAD_SPLIT", "1") != "0"
-_HEAD_RECOMPUTE = _exp_env("T4R_HEAD_RECOMPUTE", "1") != "0"
+_HEAD_SPLIT = True       # module attribute (no switch): a test flips it for the general-GEMM reference, tools/ab_step.py for an A/B
 
 # the functions behind the registered inference / evaluation operators, under the operators' argument order (torch_ops.py)
 _EAGER_HEAD_OPS = types.SimpleNamespace(
@@ -149,10 +148,9 @@ class _NextItemHeadFn(torch.autograd.Function):
         V = W.shape[0]
         smooth = float(getattr(task.loss, "label_smoothing", 0.0) or 0.0)
         mode = task.resolve_head_mode(N, V) if neg is None else "materialize"
-        ctx.recompute = (mode == "recompute" and any(ctx.needs_input_grad) and _head_split_ok(xp, W, N, V)
-                         and ops.head_split_recompute_supported(W.shape[1]))
+        ctx.recompute = mode == "recompute" and any(ctx.needs_input_grad) and _head_split_ok(xp, W, N, V)
         if mode == "recompute" and not ctx.recompute:
-            # the recomputing kernels cannot take this call (precision mode, T4R_HEAD_SPLIT=0, a misaligned table, a
+            # the recomputing kernels cannot take this call (precision mode, a width above 128, a misaligned table, a
             # training=True call under no_grad): fall back by SIZE -- the chunked head when the [N, V] scores do not
             # fit, never a silent multi-GB allocation
             mode = task.size_head_mode(N, V)
@@ -182,8 +180,8 @@ class _NextItemHeadFn(torch.autograd.Function):
                 # d_model <= 128: operands cut once, W-stationary logits (csrc/head_split.hip)
                 # (and the softmax statistics reduced inside the product: no second pass over [N, V])
                 hws = ops.head_split_prepare(xp, V)
-                if ctx.needs_input_grad[0] and ops.head_split_fdx_supported(W.shape[1]) and W.stride(0) % 4 == 0:
-                    # one pass (round 5): the scores come off the matrix cores once, are stored, and feed the d X product
+                if ctx.needs_input_grad[0]:
+                    # one pass: the scores come off the matrix cores once, are stored, and feed the d X product
                     # from registers -- the backward keeps only d W's read of the logits
                     logits, loss, _rows, lse, dx_unit = ops.head_split_logits_ce_dx(hws, xp, W.detach(), labels, alpha=1.0 / T,
                                                                                     label_smoothing=smooth, ldc=ops.pad_ld(V),
@@ -534,7 +532,7 @@ class NextItemPredictionTask(nn.Module):
             # Where the scores do fit it is NOT the default: measured at BASELINE configs[1] (d_model 128) the two extra
             # products cost more than the 3.3 GB of logits traffic they save (step 3.13 vs 2.89 ms: docs/DESIGN_rounds_1_to_4.md, round 4);
             # head_mode="recompute" / T4R_HEAD_MODE=recompute selects it anyway (training calls only: metrics read the scores)
-            if mode == "fused" and getattr(self, "_training_call", False) and _HEAD_RECOMPUTE:
+            if mode == "fused" and getattr(self, "_training_call", False):
                 D = self.pre.module.output_weights.shape[1]
                 # its workspace (per-tile statistics + two table images) is not cache-sized like the chunked head's one
                 # chunk: ~30 GB at V = 10 M, N = 15 k, D = 128 -- above T4R_HEAD_WS_GB (default 16) the chunked head stays
