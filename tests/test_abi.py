@@ -71,8 +71,6 @@ _ALLOWED_FILE_SCOPE_STATE = {
     "g_side_all": "registry of those side streams for t4r_xlnet_layer_bwd_join",
     "g_side_mu": "mutex of that registry",
     "g_sink": "thread-local, set and cleared INSIDE one t4r_xlnet_layer_bwd call (split-K partial sink)",
-    "g_sg": "thread-local, set and cleared inside one t4r_gemm_softmax_grad_f32 call",
-    "g_rank": "thread-local, set and cleared inside one t4r_rank_of_target_f32 call",
     "g_amax_a": "thread-local, set and cleared inside one layer call (operand maxima of a GEMM launch)",
     "g_amax_b": "same", "g_amax_n": "same", "g_amax_nb": "same",
     "g_cu_budget": "CUs the backward's token-tile kernels may count on, set only through t4r_xlnet_set_cu_budget (documented in "
@@ -150,5 +148,8 @@ def test_product_build_reads_no_experiment_switch(monkeypatch):
     named = [os.path.basename(f) for f in glob.glob(os.path.join(root, "transformers4rec_amd", "csrc", "*")) if "T4R_HEAD_" in open(f).read()]
     assert not named, named
     assert "t4r_exp_getenv" not in open(os.path.join(root, "transformers4rec_amd", "csrc", "head_split.hip")).read()
+    # nor has the general GEMM: its tile / split-K / precision selection is written out in launch_layout
+    for name in ("gemm_f32.hip", "gemm_half.hip", "gemm_kernel.h"):
+        assert "t4r_exp_getenv" not in open(os.path.join(root, "transformers4rec_amd", "csrc", name)).read(), name
     head_py = open(os.path.join(root, "transformers4rec_amd", "prediction_task.py")).read()
     assert not re.findall(r'_exp_env\("(T4R_HEAD_[A-Z0-9_]+)"', head_py)

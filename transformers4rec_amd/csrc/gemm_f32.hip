@@ -4,41 +4,48 @@
 #include "gemm_kernel.h"
 #include <atomic>
 
-template <int BM, int BN, int BK, bool TA, bool TB, int FEAT>
+// k-tile depth of the fp32 form: 16.  BK = 32 (16 MFMAs per barrier) won isolated long-K launches (square 111 ->
+// 115 TF, wgrads 72 -> 80, head dX 91 -> 96; tools/gemm_bench.py) but lost on the K = 128
+// contractions (logits 85 -> 76 TF) and, selected per launch by K, made the whole training step
+// slower (6.31 vs 6.23 ms, same box): the softmax-gradient variants paid for the doubled staging
+// registers.  It was instantiated behind a switch until the forms were counted.  The depth itself is
+// kBkF32 (gemm_kernel.h, beside kBkHalf = 32 of the half forms).
+
+template <int BM, int BN, bool TA, bool TB, int FEAT>
 static int launch_feat(const GemmParams& p, int batch, hipStream_t stream) {
-    if (p.vecA && p.vecB) return launch_vec<BM, BN, BK, TA, TB, FEAT, true>(p, batch, stream);
-    return launch_vec<BM, BN, BK, TA, TB, FEAT, false>(p, batch, stream);
+    if (p.vecA && p.vecB) return launch_vec<BM, BN, kBkF32, TA, TB, FEAT, true>(p, batch, stream);
+    return launch_vec<BM, BN, kBkF32, TA, TB, FEAT, false>(p, batch, stream);
 }
 
-template <int BM, int BN, int BK, bool TA, bool TB>
+// the 64 x 64 fp32 forms: the A-operand transform or epilogue of the launch picks FEAT.  The three layout errors are guards kept
+// on purpose: today's callers pass transB = 0 with the softmax-gradient operand and NT, splitk 1 with the rank and collect
+// epilogues, so none of them fires, but the other layouts of this template need some branch, and a plain product in its place
+// would be a silent wrong answer.
+template <bool TA, bool TB>
 static int launch_cfg(const GemmParams& p, int batch, hipStream_t stream) {
     if (p.sg_lse) {
-        // softmax-gradient operand: only the tile the head uses is instantiated
-        if (BM == 64 && BN == 64 && !TB) return launch_feat<64, 64, BK, TA, false, 1>(p, batch, stream);
-        t4r_set_error("gemm: softmax-grad operand needs the 64x64 tile and transB = 0");
+        if (!TB) return launch_feat<64, 64, TA, false, 1>(p, batch, stream);
+        t4r_set_error("gemm: softmax-grad operand needs transB = 0");
         return -1;
     }
     if (p.rk_thr) {
-        if (BM == 64 && BN == 64 && !TA && TB && p.splitk == 1) return launch_feat<64, 64, BK, false, true, 4>(p, batch, stream);
-        t4r_set_error("gemm: the rank epilogue needs the 64x64 NT tile without split-K");
+        if (!TA && TB && p.splitk == 1) return launch_feat<64, 64, false, true, 4>(p, batch, stream);
+        t4r_set_error("gemm: the rank epilogue needs the NT layout without split-K");
         return -1;
     }
     if (p.tk_thr) {
-        if (BM == 64 && BN == 64 && !TA && TB && p.splitk == 1 && p.tk_filtered)
-            return p.tk_noisy ? launch_feat<64, 64, BK, false, true, 56>(p, batch, stream)
-                              : launch_feat<64, 64, BK, false, true, 40>(p, batch, stream);
-        if (BM == 64 && BN == 64 && !TA && TB && p.splitk == 1)
-            return p.tk_noisy ? launch_feat<64, 64, BK, false, true, 24>(p, batch, stream)
-                              : launch_feat<64, 64, BK, false, true, 8>(p, batch, stream);
-        t4r_set_error("gemm: the top-k collect epilogue needs the 64x64 NT tile without split-K");
+        if (!TA && TB && p.splitk == 1 && p.tk_filtered)
+            return p.tk_noisy ? launch_feat<64, 64, false, true, 56>(p, batch, stream)
+                              : launch_feat<64, 64, false, true, 40>(p, batch, stream);
+        if (!TA && TB && p.splitk == 1)
+            return p.tk_noisy ? launch_feat<64, 64, false, true, 24>(p, batch, stream)
+                              : launch_feat<64, 64, false, true, 8>(p, batch, stream);
+        t4r_set_error("gemm: the top-k collect epilogue needs the NT layout without split-K");
         return -1;
     }
-    if (p.drop.p > 0.f && (p.epilogue == EPI_BIAS_GELU || p.epilogue == EPI_BIAS_RESID)) {
-        if (BM == 64 && BN == 64) return launch_feat<64, 64, BK, TA, TB, 2>(p, batch, stream);
-        t4r_set_error("gemm: epilogue dropout needs the 64x64 tile");
-        return -1;
-    }
-    return launch_feat<BM, BN, BK, TA, TB, 0>(p, batch, stream);
+    if (p.drop.p > 0.f && (p.epilogue == EPI_BIAS_GELU || p.epilogue == EPI_BIAS_RESID))
+        return launch_feat<64, 64, TA, TB, 2>(p, batch, stream);
+    return launch_feat<64, 64, TA, TB, 0>(p, batch, stream);
 }
 
 // ---- precision of the contraction (process-wide; the backward runs on autograd's thread, so not thread-local)
@@ -66,15 +73,13 @@ extern "C" int t4r_get_precision(void) {
     }
     return m;
 }
-int t4r_gemm_half_dispatch(const GemmParams& p, int batch, int ta, int tb, int big, int prec, hipStream_t stream);
+int t4r_gemm_half_dispatch(const GemmParams& p, int batch, int ta, int tb, int bm, int bn, int prec, hipStream_t stream);   // gemm_half.hip
 int t4r_tok_gemm_try(const GemmParams& p, int batch, int ta, int tb, hipStream_t stream);     // tok_gemm.hip
 
 // shapes on which the split form beat the fp32 matrix cores (tools/gemm_bench.py --prec, profiles/r02_*)
-static bool auto_split(const GemmParams& p, bool ta, bool tb) {
-    static long min_flops = -1;
-    if (min_flops < 0) { const char* e = t4r_exp_getenv("T4R_GEMM_AUTO_MIN_GFLOP"); min_flops = (e ? atol(e) : 2) * 1000000000L; }
-    return 2.0 * p.M * p.N * (double)p.K >= (double)min_flops;
-}
+constexpr double kAutoSplitMinFlop = 2e9;
+static double gemm_flop(const GemmParams& p) { return 2.0 * p.M * p.N * (double)p.K; }
+static bool auto_split(const GemmParams& p) { return gemm_flop(p) >= kAutoSplitMinFlop; }
 
 // ---------------------------------------------------------------- deterministic split-K (two stages)
 // Split-K launches normally add their partial tiles into C with fp32 atomics: run-to-run non-deterministic, and every
@@ -129,8 +134,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(SplitKJobs jobs) {
 }
 
 void t4r_splitk_sink_begin(float* ws, long cap_floats) {
-    static const int enabled = [] { const char* e = t4r_exp_getenv("T4R_SPLITK_SINK"); return e ? atoi(e) : 1; }();
-    g_sink.ws = ws; g_sink.cap = cap_floats; g_sink.used = 0; g_sink.jobs.n = 0; g_sink.on = enabled && ws && cap_floats > 0;
+    g_sink.ws = ws; g_sink.cap = cap_floats; g_sink.used = 0; g_sink.jobs.n = 0; g_sink.on = ws && cap_floats > 0;
     g_sink.bypassed = 0;
 }
 int t4r_splitk_sink_flush(hipStream_t st) {
@@ -254,92 +258,54 @@ static int launch_layout(GemmParams& p, int batch, int splitk_req, hipStream_t s
             if (rc) return rc < 0 ? rc : 0;
         }
     }
-    // tile choice: prefer 128x128; drop to 64-wide tiles when the grid would not fill 256 CUs
-    auto nblk = [&](int bm, int bn) { return (long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn) * batch; };
-    // Measured on MI355X (tools/gemm_bench.py, profiles/r01_b_gemm_tile_sweep.txt): on the layer shapes
+    // Tile.  Measured on MI355X (tools/gemm_bench.py, profiles/r01_b_gemm_tile_sweep.txt): on the layer shapes
     // and the head's backward products the 64x64x16 tile (7-8 waves/SIMD resident) beats the 128-wide
-    // tiles -- latency- not LDS-bound, more workgroups in flight win (head dW 47 -> 79 TF/s).  The one
-    // exception is chosen by shape below.
+    // tiles -- latency- not LDS-bound, more workgroups in flight win (head dW 47 -> 79 TF/s).  Three forms
+    // take a larger one, each chosen by shape below (DESIGN.md 4.1.2 lists every form and what selects it).
     int bm = 64, bn = 64;
-    static int tile_sel = -1;
-    if (tile_sel < 0) { const char* e = t4r_exp_getenv("T4R_GEMM_TILE"); tile_sel = e ? atoi(e) : 0; }
-    if (tile_sel == 1) { bm = 64; bn = 128; } else if (tile_sel == 2) { bm = 128; bn = 64; }
-    else if (tile_sel == 3) { bm = 64; bn = 64; } else if (tile_sel == 4) { bm = 128; bn = 128; }
-    else if (!TA && TB && p.M >= 1024 && p.N >= 32768 && !p.sg_lse && !p.rk_thr && !p.tk_thr && p.epilogue == EPI_NONE) {
-        // the vocabulary-wide logits product (end-of-round pipeline): per output the workgroup pulls half
-        // as much of X and W through L2 with a 128 x 128 tile, 759 vs 797 us stand-alone at C2
-        bm = 128; bn = 128;
-    }
-    static int bk_sel = -1;
-    if (bk_sel < 0) { const char* e = t4r_exp_getenv("T4R_GEMM_BK"); bk_sel = e ? atoi(e) : 0; }
+    const bool feat = p.sg_lse || (p.drop.p > 0.f && (p.epilogue == EPI_BIAS_GELU || p.epilogue == EPI_BIAS_RESID));
+    // the vocabulary-wide logits product (end-of-round pipeline): per output the workgroup pulls half
+    // as much of X and W through L2 with a 128 x 128 tile, 759 vs 797 us stand-alone at C2
+    const bool logits_shape = !TA && TB && p.M >= 1024 && p.N >= 32768 && !p.sg_lse && !p.rk_thr && !p.tk_thr && p.epilogue == EPI_NONE;
     // precision of this launch: the half-precision variants need 16-byte loadable operands; the rank epilogue
     // (exact ranks of the evaluation head) always stays on the fp32 matrix cores
-    int half_big = 0;
     int prec = launch_precision();
-    if (prec == 4) prec = auto_split(p, TA, TB) ? 1 : 0;
+    if (prec == 4) prec = auto_split(p) ? 1 : 0;
     if (prec && (!(p.vecA && p.vecB) || p.rk_thr || p.tk_thr)) prec = 0;
     if (prec && p.sg_lse && TB) prec = 0;
-    if (prec) {
-        static int half_tile = -1;
-        if (half_tile < 0) { const char* e = t4r_exp_getenv("T4R_GEMM_HALF_TILE"); half_tile = e ? atoi(e) : 0; }
-        // 128 x 128 only with one operand plane (the three-plane images of a 128 x 128 tile take 101 KB of LDS)
-        const bool feat = p.sg_lse || (p.drop.p > 0.f && (p.epilogue == EPI_BIAS_GELU || p.epilogue == EPI_BIAS_RESID));
-        int big = (!feat && prec >= 2 && (half_tile == 4 || (half_tile == 0 && bm == 128 && bn == 128))) ? 1 : 0;
-        // experiment knobs for the three-plane form: T4R_GEMM_SPLIT_TILE = 4 (128 x 128, one workgroup per CU) | 2 (128 x 64)
-        static int split_tile = -1;
-        if (split_tile < 0) { const char* e = t4r_exp_getenv("T4R_GEMM_SPLIT_TILE"); split_tile = e ? atoi(e) : 0; }
-        if (!feat && prec == 1 && (split_tile == 4 || split_tile == 2) && p.M >= 256 && p.N >= 128) big = split_tile == 4 ? 1 : 2;
+    if (prec == 1 && amax_a && amax_b && !feat && p.epilogue == EPI_NONE) {
+        prec = 4; p.amaxA = amax_a; p.amaxB = amax_b; p.n_amax = amax_n; p.n_amax_b = amax_nb;       // always 64 x 64
+    } else if (prec == 1) {
         // measured (profiles/r02_b_gemm_prec_bench.txt): the 128 x 64 tile (half the A-operand LDS reads per MFMA)
         // wins the large plain products (C5 body 2459 -> 2233 us, square 4096 1051 -> 944 us, logits 700 -> 693 us)
-        // and loses or ties below ~20 GFLOP
-        if (!feat && prec == 1 && split_tile == 0 && p.M >= 1024 && p.N >= 512 && 2.0 * p.M * p.N * (double)p.K >= 2e10) big = 2;
-        // experiment: the softmax-gradient products of the head on the 128 x 64 tile (T4R_GEMM_SG_TILE=2)
-        static int sg_tile = -1;
-        if (sg_tile < 0) { const char* e = t4r_exp_getenv("T4R_GEMM_SG_TILE"); sg_tile = e ? atoi(e) : 0; }
-        if (p.sg_lse && prec == 1 && sg_tile == 2 && p.M >= 1024) big = 2;
-        bm = big ? 128 : 64;
-        bn = big == 1 ? 128 : 64;
-        half_big = big;
-        if (prec == 1 && amax_a && amax_b && !feat && p.epilogue == EPI_NONE) {
-            prec = 4; p.amaxA = amax_a; p.amaxB = amax_b; p.n_amax = amax_n; p.n_amax_b = amax_nb;
-            bm = bn = 64; half_big = 0;
-        }
+        // and loses or ties below ~20 GFLOP.  Never 128 x 128: the three-plane images of such a tile take 101 KB of LDS
+        if (!feat && p.M >= 1024 && p.N >= 512 && gemm_flop(p) >= 2e10) bm = 128;
+    } else if (logits_shape) {          // fp32 and the one-plane precisions
+        bm = bn = 128;
     }
+    // Split-K.  Enough workgroups to fill 256 CUs x 8 (the k-loop of one workgroup hides latency only
+    // through other resident workgroups), but at least ~20 k-tiles each so that the atomics of
+    // the epilogue stay a small part.  Measured (tools/gemm_bench.py): head dX 2765x128x100001
+    // 1076 us at 1024 workgroups, 786 us at 4096; wgrad 128x512x20480 best at 64 splits.
+    constexpr long kSplitTargetBlocks = 4096, kSplitMinTiles = 20;
+    const int kt = (p.K + (prec ? kBkHalf : kBkF32) - 1) / (prec ? kBkHalf : kBkF32);
     int splitk = splitk_req;
     if (splitk_req == 0) {  // auto: only when the caller allows atomics (accumulating outputs)
         splitk = 1;
     } else if (splitk_req < 0) {
-        const long blocks = nblk(bm, bn);
-        const int bk0 = prec ? 32 : (bk_sel ? bk_sel : 16);
-        const int kt = (p.K + bk0 - 1) / bk0;
-        // enough workgroups to fill 256 CUs x 8 (the k-loop of one workgroup hides latency only
-        // through other resident workgroups), but at least ~20 k-tiles each so that the atomics of
-        // the epilogue stay a small part.  Measured (tools/gemm_bench.py): head dX 2765x128x100001
-        // 1076 us at 1024 workgroups, 786 us at 4096; wgrad 128x512x20480 best at 64 splits.
-        static long target = -1, min_tiles = -1;
-        if (target < 0) { const char* e = t4r_exp_getenv("T4R_GEMM_SPLIT_TARGET"); target = e ? atol(e) : 4096; }
-        if (min_tiles < 0) { const char* e = t4r_exp_getenv("T4R_GEMM_SPLIT_MIN_TILES"); min_tiles = e ? atol(e) : 20; }
-        splitk = (int)max(1L, min((long)kt / min_tiles, target / max(1L, blocks)));
+        const long blocks = (long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn) * batch;
+        splitk = (int)max(1L, min((long)kt / kSplitMinTiles, kSplitTargetBlocks / max(1L, blocks)));
         splitk = min(splitk, 256);
     }
     p.splitk = max(1, splitk);
     p.part = nullptr;
     if (p.splitk > 1) {
         // every split owns at least one k-tile (a partial tile must be written by its split)
-        const int bk0 = prec ? 32 : (bk_sel ? bk_sel : 16);
-        const int kt = (p.K + bk0 - 1) / bk0, kt_per = (kt + p.splitk - 1) / p.splitk;
+        const int kt_per = (kt + p.splitk - 1) / p.splitk;
         p.splitk = (kt + kt_per - 1) / kt_per;
         if (p.splitk > 1) p.part = splitk_sink_take(p, batch);
     }
-    // k-tile depth 16.  BK = 32 (16 MFMAs per barrier) wins isolated long-K launches (square 111 ->
-    // 115 TF, wgrads 72 -> 80, head dX 91 -> 96; tools/gemm_bench.py) but loses on the K = 128
-    // contractions (logits 85 -> 76 TF) and, selected per launch by K, made the whole training step
-    // slower (6.31 vs 6.23 ms, same box): the softmax-gradient variants pay for the doubled staging
-    // registers.  T4R_GEMM_BK=32 keeps it available for experiments.
-    const int BK = bk_sel ? bk_sel : 16;
-    static int xcd_sel = -1;
-    if (xcd_sel < 0) { const char* e = t4r_exp_getenv("T4R_GEMM_XCD"); xcd_sel = e ? atoi(e) : 1; }
-    p.xcd_order = xcd_sel;
+    p.xcd_order = 1;        // XCD-aware tile order (gemm_kernel.h); the kernel keeps the test of it
     if (p.splitk > 1) {
         if (p.epilogue != EPI_NONE) { t4r_set_error("gemm: split-K needs epilogue NONE"); return -1; }
         if (!p.accumulate && !p.part) {  // atomics accumulate: start from zero unless the caller accumulates
@@ -347,31 +313,24 @@ static int launch_layout(GemmParams& p, int batch, int splitk_req, hipStream_t s
                 (void)hipMemset2DAsync(p.C + b * p.sC, p.ldc * sizeof(float), 0, p.N * sizeof(float), p.M, stream);
         }
     }
-    if (prec) return t4r_gemm_half_dispatch(p, batch, TA, TB, half_big, prec, stream);
-    if (BK == 16) {
-        if (bm == 128 && bn == 128) return launch_cfg<128, 128, 16, TA, TB>(p, batch, stream);
-        if (bm == 64 && bn == 128) return launch_cfg<64, 128, 16, TA, TB>(p, batch, stream);
-        if (bm == 128 && bn == 64) return launch_cfg<128, 64, 16, TA, TB>(p, batch, stream);
-        return launch_cfg<64, 64, 16, TA, TB>(p, batch, stream);
+    if (prec) return t4r_gemm_half_dispatch(p, batch, TA, TB, bm, bn, prec, stream);
+    if constexpr (!TA && TB) {
+        if (bm == 128) return launch_feat<128, 128, false, true, 0>(p, batch, stream);
     }
-    if (bm == 128 && bn == 128) return launch_cfg<128, 128, 32, TA, TB>(p, batch, stream);
-    if (bm == 64 && bn == 128) return launch_cfg<64, 128, 32, TA, TB>(p, batch, stream);
-    if (bm == 128 && bn == 64) return launch_cfg<128, 64, 32, TA, TB>(p, batch, stream);
-    return launch_cfg<64, 64, 32, TA, TB>(p, batch, stream);
+    return launch_cfg<TA, TB>(p, batch, stream);
 }
 
 struct SoftmaxGradA { const float* lse; const long* labels; const float* gout; int rows, V; float smooth; int yoff; };
-static thread_local const SoftmaxGradA* g_sg = nullptr;   // set only by t4r_gemm_softmax_grad_f32
 struct RankEpi { const float* thr; const long* label; int* count; };
-static thread_local const RankEpi* g_rank = nullptr;      // set only by t4r_rank_of_target_f32
 struct TopkEpi { const float* thr; long thr_ld; int* count; float* val; int* idx; int cap; const GumbelCfg* noise; const ItkFilter* filt; };
 
+// sg: the softmax-gradient A operand (t4r_gemm_softmax_grad_launch); rank: the rank epilogue (t4r_rank_of_target_f32);
 // topk / force_fp32: the two products of the fused top-k head (end of this file); null / false everywhere else
 static int gemm_launch_impl(hipStream_t stream, int transA, int transB, int M, int N, int K, float alpha,
                             const float* A, long lda, const float* B, long ldb, float* C, long ldc,
                             const float* bias, int epilogue, float* aux, long ldaux, int splitk,
                             int accumulate, int batch, long sA, long sB, long sC, const DropCfg* drop,
-                            const TopkEpi* topk, bool force_fp32) {
+                            const SoftmaxGradA* sg, const RankEpi* rank, const TopkEpi* topk, bool force_fp32) {
     if (M <= 0 || N <= 0) { g_amax_a = g_amax_b = nullptr; return 0; }     // operand maxima announced for THIS launch die with it
     T4R_CHECK_ARG(K > 0 && A && B && C && batch >= 1, "gemm: bad arguments");
     GemmParams p;
@@ -386,7 +345,7 @@ static int gemm_launch_impl(hipStream_t stream, int transA, int transB, int M, i
     p.drop = drop ? *drop : make_drop(0.f, 0, 0);
     p.sg_lse = nullptr; p.sg_labels = nullptr; p.sg_gout = nullptr; p.sg_rows = 1; p.sg_V = 1; p.sg_smooth = 0.f; p.sg_yoff = 0;
     p.rk_thr = nullptr; p.rk_label = nullptr; p.rk_count = nullptr;
-    if (g_rank) { p.rk_thr = g_rank->thr; p.rk_label = g_rank->label; p.rk_count = g_rank->count; }
+    if (rank) { p.rk_thr = rank->thr; p.rk_label = rank->label; p.rk_count = rank->count; }
     p.tk_thr = nullptr; p.tk_thr_ld = 0; p.tk_count = nullptr; p.tk_val = nullptr; p.tk_idx = nullptr; p.tk_cap = 0;
     p.tk_noisy = 0; p.tk_noise = GumbelCfg{0, 0, 0};
     p.tk_filtered = 0; p.tk_filt = ItkFilter{nullptr, nullptr, 0, 0};
@@ -396,9 +355,9 @@ static int gemm_launch_impl(hipStream_t stream, int transA, int transB, int M, i
         if (topk->noise) { p.tk_noisy = 1; p.tk_noise = *topk->noise; }
         if (topk->filt) { p.tk_filtered = 1; p.tk_filt = *topk->filt; }
     }
-    if (g_sg) {
-        p.sg_lse = g_sg->lse; p.sg_labels = g_sg->labels; p.sg_gout = g_sg->gout;
-        p.sg_rows = g_sg->rows; p.sg_V = g_sg->V; p.sg_smooth = g_sg->smooth; p.sg_yoff = g_sg->yoff;
+    if (sg) {
+        p.sg_lse = sg->lse; p.sg_labels = sg->labels; p.sg_gout = sg->gout;
+        p.sg_rows = sg->rows; p.sg_V = sg->V; p.sg_smooth = sg->smooth; p.sg_yoff = sg->yoff;
     }
     if (transA) {
         if (transB) return launch_layout<true, true>(p, batch, splitk, stream, force_fp32);
@@ -414,7 +373,7 @@ int t4r_gemm_launch(hipStream_t stream, int transA, int transB, int M, int N, in
                     const float* bias, int epilogue, float* aux, long ldaux, int splitk,
                     int accumulate, int batch, long sA, long sB, long sC, const DropCfg* drop) {
     return gemm_launch_impl(stream, transA, transB, M, N, K, alpha, A, lda, B, ldb, C, ldc, bias, epilogue, aux, ldaux, splitk,
-                            accumulate, batch, sA, sB, sC, drop, nullptr, false);
+                            accumulate, batch, sA, sB, sC, drop, nullptr, nullptr, nullptr, false);
 }
 
 extern "C" int t4r_gemm_f32(void* stream, int transA, int transB, int M, int N, int K, float alpha,
@@ -442,14 +401,10 @@ int t4r_gemm_softmax_grad_launch(hipStream_t stream, int transA, int n_rows, int
                                  const long* labels, const float* grad_out, float label_smoothing, const float* B,
                                  long ldb, float* C, long ldc, int splitk, int accumulate) {
     T4R_CHECK_ARG(lse && labels && logits, "gemm_softmax_grad: null operand");
-    SoftmaxGradA sg{lse, labels, grad_out, n_rows, V, label_smoothing, yoff};
-    g_sg = &sg;
+    const SoftmaxGradA sg{lse, labels, grad_out, n_rows, V, label_smoothing, yoff};
     const int M = transA ? Vc : n_rows, K = transA ? n_rows : Vc;
-    const int rc = t4r_gemm_launch(stream, transA, 0, M, N, K, alpha, logits, ld_logits, B, ldb,
-                                   C, ldc, nullptr, EPI_NONE, nullptr, 0, splitk, accumulate, 1, 0, 0, 0,
-                                   nullptr);
-    g_sg = nullptr;
-    return rc;
+    return gemm_launch_impl(stream, transA, 0, M, N, K, alpha, logits, ld_logits, B, ldb, C, ldc, nullptr, EPI_NONE, nullptr, 0,
+                            splitk, accumulate, 1, 0, 0, 0, nullptr, &sg, nullptr, nullptr, false);
 }
 
 extern "C" int t4r_gemm_softmax_grad_f32(void* stream, int transA, int n_rows, int V, int N, float alpha,
@@ -476,14 +431,10 @@ extern "C" int t4r_rank_of_target_f32(void* stream, int n_rows, int V, int D, fl
         t4r_set_error("rank_of_target: memset failed");
         return -1;
     }
-    RankEpi re{target_score, labels, rank};
-    g_rank = &re;
+    const RankEpi re{target_score, labels, rank};
     // C is never written by the rank epilogue; a non-null dummy keeps the argument check happy
-    const int rc = t4r_gemm_launch((hipStream_t)stream, 0, 1, n_rows, V, D, alpha, X, ldx, W, ldw,
-                                   reinterpret_cast<float*>(rank), V, nullptr, EPI_NONE, nullptr, 0, 1, 0, 1, 0, 0,
-                                   0, nullptr);
-    g_rank = nullptr;
-    return rc;
+    return gemm_launch_impl((hipStream_t)stream, 0, 1, n_rows, V, D, alpha, X, ldx, W, ldw, reinterpret_cast<float*>(rank), V,
+                            nullptr, EPI_NONE, nullptr, 0, 1, 0, 1, 0, 0, 0, nullptr, nullptr, &re, nullptr, false);
 }
 
 // ---- the two products of the fused top-k inference head (csrc/item_topk.hip), both form 0 whatever the process-wide mode:
@@ -491,7 +442,7 @@ extern "C" int t4r_rank_of_target_f32(void* stream, int n_rows, int V, int D, fl
 int t4r_gemm_fp32_nt_launch(hipStream_t stream, int M, int N, int K, float alpha, const float* A, long lda,
                             const float* B, long ldb, float* C, long ldc) {
     return gemm_launch_impl(stream, 0, 1, M, N, K, alpha, A, lda, B, ldb, C, ldc, nullptr, EPI_NONE, nullptr, 0, 1, 0, 1, 0, 0,
-                            0, nullptr, nullptr, true);
+                            0, nullptr, nullptr, nullptr, nullptr, true);
 }
 // ... and the same product with the collect epilogue: no C; (score, item) of every score >= thr[row * thr_ld] goes to the
 // row's candidate list (GemmParams::tk_*).  count[n_rows] must be zero on entry.
@@ -502,7 +453,7 @@ int t4r_gemm_topk_collect_launch(hipStream_t stream, int n_rows, int V, int D, f
     const TopkEpi te{thr, thr_ld, count, cand_val, cand_idx, cap, noise, nullptr};
     // C is never written by the collect epilogue; a non-null dummy keeps the argument check happy
     return gemm_launch_impl(stream, 0, 1, n_rows, V, D, alpha, X, ldx, W, ldw, cand_val, V, nullptr, EPI_NONE, nullptr, 0, 1, 0,
-                            1, 0, 0, 0, nullptr, &te, true);
+                            1, 0, 0, 0, nullptr, nullptr, nullptr, &te, true);
 }
 // ... and under an item filter (item_filter.h): only allowed items are appended
 int t4r_gemm_topk_collect_filtered_launch(hipStream_t stream, int n_rows, int V, int D, float alpha, const float* X, long ldx,
@@ -510,5 +461,5 @@ int t4r_gemm_topk_collect_filtered_launch(hipStream_t stream, int n_rows, int V,
                                           int* cand_idx, int cap, const GumbelCfg* noise, const ItkFilter* filt) {
     const TopkEpi te{thr, thr_ld, count, cand_val, cand_idx, cap, noise, filt};
     return gemm_launch_impl(stream, 0, 1, n_rows, V, D, alpha, X, ldx, W, ldw, cand_val, V, nullptr, EPI_NONE, nullptr, 0, 1, 0,
-                            1, 0, 0, 0, nullptr, &te, true);
+                            1, 0, 0, 0, nullptr, nullptr, nullptr, &te, true);
 }
