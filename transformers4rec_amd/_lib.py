@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("T4R_HIP_LIB") or os.path.join(_HERE, "lib", "libt4r_h
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip.h")
 SAMPLING_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_sampling.h")
 FILTER_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_filter.h")
+OPTIM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_optim.h")
 
 _P, _I, _L, _F, _Q = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_ulonglong
 _C = {"p": _P, "i": _I, "l": _L, "f": _F, "Q": _Q}
@@ -174,6 +175,14 @@ _SIGS_FILTER = {
     "t4r_item_sample_filtered_h16": ("i", _SIGS_SAMPLING["t4r_item_sample_h16"][1] + _FILT),
 }
 
+# the fourth header, include/t4r_hip_optim.h (tests/test_optim_clip_cpu.py checks this table against it)
+_SIGS_OPTIM = {
+    "t4r_grad_sumsq_parts": ("l", "l"),
+    "t4r_grad_sumsq": ("i", "pplp"),
+    "t4r_grad_clip_coef": ("i", "ppiffp"),
+    "t4r_adamw_step": ("i", "ppppp" + "li" + "fffff" + "if" + "i" + "p" + "llp"),
+}
+
 _lib = None
 
 
@@ -202,6 +211,11 @@ def filter_header_symbols():
     return _declared(FILTER_HEADER_PATH)
 
 
+def optim_header_symbols():
+    """Function names declared in include/t4r_hip_optim.h."""
+    return _declared(OPTIM_HEADER_PATH)
+
+
 def load():
     """Loads the library and sets ctypes prototypes.  Raises if it is not built."""
     global _lib
@@ -212,7 +226,7 @@ def load():
             f"{LIB_PATH} not found: the HIP extension is not built "
             "(run `python -m transformers4rec_amd.build`). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (ret, args) in list(_SIGS.items()) + list(_SIGS_SAMPLING.items()) + list(_SIGS_FILTER.items()):
+    for name, (ret, args) in list(_SIGS.items()) + list(_SIGS_SAMPLING.items()) + list(_SIGS_FILTER.items()) + list(_SIGS_OPTIM.items()):
         fn = getattr(lib, name)
         fn.restype = ctypes.c_char_p if ret == "s" else (None if ret == "v" else _C[ret])
         fn.argtypes = [_C[a] for a in args]

@@ -7,7 +7,7 @@
 //   fused Adam                    : torch.optim.Adam semantics (reference Model.fit, torch/model/base.py:669-718)
 // All are one pass over their operands with 16-byte accesses where the row width allows.
 #include "t4r_common.h"
-
+#include "adam_kernel.h"
 // ---------------------------------------------------------------- residual + LayerNorm fwd
 template <int VEC>
 struct alignas(4 * VEC) FV {
@@ -579,71 +579,7 @@ extern "C" int t4r_add_pos_bwd(void* stream, const float* dy, float* d_pos, int 
 }
 
 // ---------------------------------------------------------------- fused Adam over a flat buffer
-// torch.optim.Adam (amsgrad=False, maximize=False): with step t (1-based)
-//   g = grad (+ wd * p) ; m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2
-//   p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
-// grad_scale multiplies grad first (1/world_size for the DP mean).  Optionally zeroes the grad.
-// The two bias corrections 1 - b1^t and sqrt(1 - b2^t) are computed in DOUBLE on the host (from the float betas the ABI
-// takes) and passed to the kernel rounded once to float: in fp32 `1.f - powf(b2, t)` is a cancellation of a rounded power --
-// 6.7e-6 relative at t = 2, which put p tens of fp32 roundings away from an exact Adam step during the first steps
-// (tests/test_adam_gpu.py counts them).
-// One element's step.  Every multiply-add is written out as the fmaf it is meant to be: left to the compiler's contraction, the
-// two instantiations of the kernel (and its float4 body and scalar tail) fused different pairs and rounded m, v and p differently
-// -- the two entry points disagreed in the last bit from the second step on (tests/test_adam_gpu.py holds them to one arithmetic).
-__device__ __forceinline__ void adam_element(float& p, float g, float& m, float& v, float step_size, float b1, float b2,
-                                             float eps, float wd, float bc2_sqrt, float grad_scale) {
-    const float gr = fmaf(wd, p, g * grad_scale);
-    m = fmaf(b1, m, (1.f - b1) * gr);
-    v = fmaf(b2, v, ((1.f - b2) * gr) * gr);
-    const float denom = sqrtf(v) / bc2_sqrt + eps;
-    p = fmaf(-step_size, m / denom, p);
-}
-// AMAX (round 6): the launch also leaves, per workgroup, the largest |p| AFTER the update among the elements [amax_lo, amax_hi)
-// in amax_part[blockIdx.x] -- the tied item table's maximum, which the next step's head needs to position its fp16 images
-// (csrc/head_split.hip: split_w_images_kernel reduces the <= 1024 partials) and used to get from a memset + a 21 us pass over
-// the 51 MB the optimizer has just streamed.  Plain stores, one slot per workgroup (same-address atomics serialise).
-template <bool AMAX>
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float* __restrict__ g,
-                                                    float* __restrict__ m, float* __restrict__ v,
-                                                    long n, float lr, float b1, float b2, float eps,
-                                                    float wd, float bc1, float bc2_sqrt,
-                                                    float grad_scale, int zero_grad, long amax_lo, long amax_hi,
-                                                    float* __restrict__ amax_part) {
-    float mx = 0.f;
-    const float step_size = lr / bc1;
-    const long stride = (long)gridDim.x * blockDim.x * 4;
-    for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
-        if (i + 4 <= n) {
-            float4 pp = *reinterpret_cast<float4*>(p + i);
-            float4 gg = *reinterpret_cast<float4*>(g + i);
-            float4 mm = *reinterpret_cast<float4*>(m + i);
-            float4 vv = *reinterpret_cast<float4*>(v + i);
-            float* P = &pp.x; float* G = &gg.x; float* M = &mm.x; float* V = &vv.x;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                adam_element(P[e], G[e], M[e], V[e], step_size, b1, b2, eps, wd, bc2_sqrt, grad_scale);
-                if (AMAX && i + e >= amax_lo && i + e < amax_hi) mx = fmaxf(mx, fabsf(P[e]));
-            }
-            *reinterpret_cast<float4*>(p + i) = pp;
-            *reinterpret_cast<float4*>(m + i) = mm;
-            *reinterpret_cast<float4*>(v + i) = vv;
-            if (zero_grad) *reinterpret_cast<float4*>(g + i) = make_float4(0.f, 0.f, 0.f, 0.f);
-        } else {
-            for (long j = i; j < n; ++j) {
-                adam_element(p[j], g[j], m[j], v[j], step_size, b1, b2, eps, wd, bc2_sqrt, grad_scale);
-                if (AMAX && j >= amax_lo && j < amax_hi) mx = fmaxf(mx, fabsf(p[j]));
-                if (zero_grad) g[j] = 0.f;
-            }
-        }
-    }
-    if (AMAX) {
-        __shared__ float sh[4];
-        mx = wave_max(mx);
-        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = mx;
-        __syncthreads();
-        if (threadIdx.x == 0) amax_part[blockIdx.x] = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-    }
-}
+// adam_kernel.h: the arithmetic (adam_element) and the kernel body, shared with csrc/optim.hip (t4r_adamw_step)
 
 extern "C" int t4r_adam_step(void* stream, float* param, float* grad, float* exp_avg,
                              float* exp_avg_sq, long n, int step, float lr, float beta1, float beta2,
@@ -657,9 +593,9 @@ extern "C" int t4r_adam_step(void* stream, float* param, float* grad, float* exp
     long blocks = (n / 4 + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(adam_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param,
+    hipLaunchKernelGGL((adam_kernel<false, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param,
                        grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s,
-                       grad_scale, zero_grad, 0L, 0L, nullptr);
+                       grad_scale, zero_grad, 0L, 0L, nullptr, nullptr, 0, 1.f);
     T4R_LAUNCH_CHECK();
     return 0;
 }
@@ -680,9 +616,9 @@ extern "C" int t4r_adam_step_amax(void* stream, float* param, float* grad, float
     long blocks = (n / 4 + 255) / 256;
     if (blocks > 512) blocks = 512;      // (the consumer reduces the partials in every workgroup: 512 x 4 bytes)
     if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(adam_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
+    hipLaunchKernelGGL((adam_kernel<true, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
                        exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale, zero_grad, amax_lo, amax_hi,
-                       amax_part);
+                       amax_part, nullptr, 0, 1.f);
     if (hipGetLastError() != hipSuccess) { t4r_set_error("adam_step_amax: launch failed"); return -1; }
     return (int)blocks;
 }

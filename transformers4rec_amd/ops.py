@@ -1476,3 +1476,48 @@ def adam_step_(param, grad, exp_avg, exp_avg_sq, step, lr=1e-3, betas=(0.9, 0.99
     call("t4r_adam_step", _stream(), _chk(param, torch.float32), _chk(grad, torch.float32),
          _chk(exp_avg), _chk(exp_avg_sq), param.numel(), int(step), float(lr), float(betas[0]),
          float(betas[1]), float(eps), float(weight_decay), float(grad_scale), int(zero_grad))
+
+
+# ---- include/t4r_hip_optim.h: global-norm clipping and AdamW over flat buckets (optim.FusedAdam drives them)
+def grad_sumsq_parts(n):
+    """how many partials grad_sumsq_ over n elements writes (a pure function of n, <= 2048)"""
+    return _lib.load().t4r_grad_sumsq_parts(int(n))
+
+
+def grad_sumsq_(grad, part):
+    """part[:count] (float64) = per-workgroup sums of grad^2, squared and added in double; -> count"""
+    _chk(grad, torch.float32, "grad"), _chk(part, torch.float64, "part")
+    lib = _lib.load()
+    need = lib.t4r_grad_sumsq_parts(grad.numel())
+    if part.numel() < need:
+        raise ValueError(f"part holds {part.numel()} partials, {need} are written")
+    n = lib.t4r_grad_sumsq(_stream(), grad.data_ptr(), grad.numel(), part.data_ptr())
+    if n < 0:
+        raise _lib.T4RHipError(lib.t4r_last_error().decode())
+    return n
+
+
+def grad_clip_coef_(part, n_part, grad_scale, max_norm, out):
+    """out[0] = fp32(|grad_scale| * sqrt(sum part[:n_part])), out[1] = min(max_norm / (out[0] + 1e-6), 1): no host read"""
+    _chk(part, torch.float64, "part"), _chk(out, torch.float32, "out")
+    if not 1 <= n_part <= part.numel() or out.numel() < 2:
+        raise ValueError("grad_clip_coef_: 1 <= n_part <= part.numel() and out of at least 2 floats")
+    call("t4r_grad_clip_coef", _stream(), part.data_ptr(), int(n_part), float(grad_scale), float(max_norm), out.data_ptr())
+
+
+def adamw_step_(param, grad, exp_avg, exp_avg_sq, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                decoupled=False, grad_scale=1.0, zero_grad=True, clip_coef=None, amax=None):
+    """adam_step_ with the gradient multiplied by the device scalar clip_coef (a 1-element fp32 tensor, or None) after
+    grad_scale, and with torch.optim.AdamW's decoupled weight decay when `decoupled`.  amax = (lo, hi, part) as
+    adam_step_amax_.  -> the number of workgroups (= partial maxima written when amax is given)"""
+    lo, hi, part = amax if amax is not None else (0, 0, None)
+    if clip_coef is not None and clip_coef.numel() != 1:
+        raise ValueError("clip_coef is one float")
+    lib = _lib.load()
+    n = lib.t4r_adamw_step(_stream(), _chk(param, torch.float32), _chk(grad, torch.float32), _chk(exp_avg), _chk(exp_avg_sq),
+                           param.numel(), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                           float(weight_decay), int(bool(decoupled)), float(grad_scale), int(zero_grad),
+                           _p(clip_coef, torch.float32, "clip_coef"), int(lo), int(hi), _p(part, torch.float32, "amax part"))
+    if n < 0:
+        raise _lib.T4RHipError(lib.t4r_last_error().decode())
+    return n

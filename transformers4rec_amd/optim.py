@@ -1,4 +1,4 @@
-"""Flat parameter / gradient buffers and the fused Adam step.
+"""Flat parameter / gradient buffers and the fused Adam / AdamW step with global-norm clipping.
 
 The reference trains with torch.optim.Adam (Model.fit, transformers4rec/torch/model/base.py:
 669-718) and lets torch DDP bucket the gradients.  On MI355X every parameter lives in one of
@@ -61,14 +61,55 @@ def flatten_model(model):
     return FlatParams(dense), (FlatParams(tables) if tables else None)
 
 
-class FusedAdam:
-    """torch.optim.Adam semantics over FlatParams buffers; zeroes the gradients in the same pass."""
+def warmup_schedule(name, num_warmup_steps, num_training_steps=None, num_cycles=0.5):
+    """-> f(step) -> learning-rate multiplier: the lambdas of transformers.optimization.get_constant_schedule_with_warmup /
+    get_linear_schedule_with_warmup / get_cosine_schedule_with_warmup, which the reference's Trainer.get_scheduler
+    (transformers4rec/torch/trainer.py:259-313) hands to LambdaLR.  `step` counts the optimizer steps already taken."""
+    import math
 
-    def __init__(self, flats, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    if name not in ("constant_with_warmup", "linear", "cosine"):
+        raise ValueError(f"unknown schedule '{name}': constant_with_warmup, linear or cosine")
+    if num_warmup_steps is None:
+        raise ValueError(f"{name} requires num_warmup_steps")
+    if name != "constant_with_warmup" and num_training_steps is None:
+        raise ValueError(f"{name} requires num_training_steps")
+    w, T = num_warmup_steps, num_training_steps
+
+    def f(step):
+        if name == "constant_with_warmup":
+            return float(step) / float(max(1.0, w)) if step < w else 1.0
+        if step < w:
+            return float(step) / float(max(1, w))
+        if name == "linear":
+            return max(0.0, float(T - step) / float(max(1, T - w)))
+        progress = float(step - w) / float(max(1, T - w))
+        return max(0.0, 0.5 * (1.0 + math.cos(math.pi * float(num_cycles) * 2.0 * progress)))
+
+    return f
+
+
+class FusedAdam:
+    """torch.optim.Adam semantics over FlatParams buffers; zeroes the gradients in the same pass.
+
+    decoupled_weight_decay=True makes it torch.optim.AdamW; max_grad_norm clips the global norm of the (grad_scale-d) gradient
+    over all buckets as torch.nn.utils.clip_grad_norm_ does, with the norm and the coefficient left on the device.  The
+    reference's Trainer recipe (AdamW, max_grad_norm 1.0, warm-up) is
+        FusedAdam(flats, lr, weight_decay=0.01, decoupled_weight_decay=True, max_grad_norm=1.0) + set_schedule(warmup_schedule(...)).
+    With both new arguments at their defaults step() launches exactly what it always has."""
+
+    def __init__(self, flats, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None,
+                 decoupled_weight_decay=False):
+        if max_grad_norm is not None and not max_grad_norm > 0:
+            raise ValueError(f"max_grad_norm must be greater than 0 (or None: no clipping), got {max_grad_norm}")
         self.flats = [f for f in flats if f is not None]
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
+        self.max_grad_norm, self.decoupled_weight_decay = max_grad_norm, bool(decoupled_weight_decay)
+        self.base_lr, self._schedule = lr, None
         self.state = [(torch.zeros_like(f.data), torch.zeros_like(f.data)) for f in self.flats]
         self.step_count = 0
+        # clipping: the partial sums of squares of every bucket side by side, and (norm, coefficient); allocated at the first
+        # clipped step (the partial counts come from the library)
+        self._clip_part = self._clip_out = None
         # per bucket: (parameter, offset, partial-maxima buffer) of its largest 2-D table on the GPU, or None
         self._amax_targets = []
         for f in self.flats:
@@ -85,9 +126,25 @@ class FusedAdam:
         from .transformer import _join_weight_gradient_streams
         _join_weight_gradient_streams()
 
+    def set_schedule(self, f):
+        """f(step) -> multiplier of the constructor's lr (warmup_schedule); None: constant.  The step that makes step_count == t
+        runs at base_lr * f(t - 1): a torch scheduler is stepped AFTER the optimizer, so its first step runs at f(0)."""
+        self._schedule = f
+        return self
+
+    @property
+    def last_grad_norm(self):
+        """0-d device tensor: the norm of the scaled gradient over all buckets BEFORE the clip of the last step; None when
+        clipping is off or no step was taken.  Reading it synchronises the caller, not step()."""
+        return None if self._clip_out is None else self._clip_out[0]
+
     def step(self, grad_scale=1.0):
         self._join()
         self.step_count += 1
+        if self._schedule is not None:
+            self.lr = self.base_lr * self._schedule(self.step_count - 1)
+        if self.max_grad_norm is not None or self.decoupled_weight_decay:
+            return self._step_ext(grad_scale)
         for k, (f, (m, v)) in enumerate(zip(self.flats, self.state)):
             f.ensure_grads()
             tgt = self._amax_targets[k]
@@ -101,6 +158,54 @@ class FusedAdam:
             n = ops.adam_step_amax_(f.data, f.grad, m, v, self.step_count, lo, lo + p.numel(), part, self.lr, self.betas, self.eps,
                                     self.weight_decay, grad_scale, zero_grad=True)
             p._t4r_w_amax = (part, n, p.data_ptr(), p._version, f.data, f.data._version)
+
+    def _step_ext(self, grad_scale):
+        """sum of squares per bucket -> one coefficient launch -> one t4r_adamw_step per bucket"""
+        for f in self.flats:
+            f.ensure_grads()
+        coef = None
+        if self.max_grad_norm is not None:
+            if self._clip_part is None:
+                dev = self.flats[0].data.device
+                self._clip_part = torch.zeros(sum(ops.grad_sumsq_parts(f.numel) for f in self.flats), device=dev, dtype=torch.float64)
+                self._clip_out = torch.zeros(2, device=dev, dtype=torch.float32)
+            n_part = 0
+            for f in self.flats:
+                n_part += ops.grad_sumsq_(f.grad, self._clip_part[n_part:])
+            ops.grad_clip_coef_(self._clip_part, n_part, grad_scale, self.max_grad_norm, self._clip_out)
+            coef = self._clip_out[1:]
+        for k, (f, (m, v)) in enumerate(zip(self.flats, self.state)):
+            tgt = self._amax_targets[k]
+            amax = None if tgt is None else (tgt[1], tgt[1] + tgt[0].numel(), tgt[2])
+            n = ops.adamw_step_(f.data, f.grad, m, v, self.step_count, self.lr, self.betas, self.eps, self.weight_decay,
+                                self.decoupled_weight_decay, grad_scale, zero_grad=True, clip_coef=coef, amax=amax)
+            if tgt is not None:       # as step(): the table's maximum after the update, for the head of the next step
+                p = tgt[0]
+                p._t4r_w_amax = (tgt[2], n, p.data_ptr(), p._version, f.data, f.data._version)
+
+    def state_dict(self):
+        """moments per bucket (copies), step count and hyper-parameters; a schedule is code and is set again by the caller"""
+        return {"step_count": self.step_count,
+                "state": [{"exp_avg": m.detach().clone(), "exp_avg_sq": v.detach().clone()} for m, v in self.state],
+                "hyper": {"lr": self.base_lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay,
+                          "max_grad_norm": self.max_grad_norm, "decoupled_weight_decay": self.decoupled_weight_decay}}
+
+    def load_state_dict(self, sd):
+        if len(sd["state"]) != len(self.state):
+            raise ValueError(f"state_dict has {len(sd['state'])} buckets, the optimizer {len(self.state)}")
+        for (m, v), s in zip(self.state, sd["state"]):
+            if s["exp_avg"].shape != m.shape or s["exp_avg_sq"].shape != v.shape:
+                raise ValueError("state_dict bucket sizes do not match the optimizer's")
+        h = sd["hyper"]
+        if h["max_grad_norm"] is not None and not h["max_grad_norm"] > 0:
+            raise ValueError("max_grad_norm must be greater than 0")
+        for (m, v), s in zip(self.state, sd["state"]):
+            m.copy_(s["exp_avg"])
+            v.copy_(s["exp_avg_sq"])
+        self.step_count = int(sd["step_count"])
+        self.base_lr = self.lr = h["lr"]
+        self.betas, self.eps, self.weight_decay = tuple(h["betas"]), h["eps"], h["weight_decay"]
+        self.max_grad_norm, self.decoupled_weight_decay = h["max_grad_norm"], bool(h["decoupled_weight_decay"])
 
     def zero_grad(self):
         self._join()
