@@ -10,7 +10,7 @@ from .schema import ColumnSchema, IntDomain, Schema, Tags, ValueCount, random_da
 from .masking import (CausalLanguageModeling, MaskedLanguageModeling, MaskSequence, GradCarrier,  # noqa: E402,F401
                       ReplacementLanguageModeling, enable_autograd_gradients, hip_parameters)
 from .features import (  # noqa: E402,F401
-    ContinuousFeatures, EmbeddingFeatures, FeatureConfig, SequenceEmbeddingFeatures, SoftEmbedding,
+    ContinuousFeatures, EmbeddingFeatures, FeatureConfig, PretrainedEmbeddingFeatures, SequenceEmbeddingFeatures, SoftEmbedding,
     SoftEmbeddingFeatures, TableConfig, TabularSequenceFeatures)
 from . import ranking_metric  # noqa: E402,F401
 from .ranking_metric import AvgPrecisionAt, DCGAt, NDCGAt, PrecisionAt, RecallAt  # noqa: E402,F401

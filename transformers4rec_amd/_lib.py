@@ -14,6 +14,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip.h")
 SAMPLING_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_sampling.h")
 FILTER_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_filter.h")
 OPTIM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_optim.h")
+PRETRAINED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_pretrained.h")
 
 _P, _I, _L, _F, _Q = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_ulonglong
 _C = {"p": _P, "i": _I, "l": _L, "f": _F, "Q": _Q}
@@ -183,6 +184,16 @@ _SIGS_OPTIM = {
     "t4r_adamw_step": ("i", "ppppp" + "li" + "fffff" + "if" + "i" + "p" + "llp"),
 }
 
+# the fifth header, include/t4r_hip_pretrained.h (tests/test_pretrained_cpu.py checks this table against it); the common head is
+# stream, dtype, image, ldp, rows, ids, T, ids_div
+_PP = "pipllpli"
+_SIGS_PRETRAINED = {
+    "t4r_pretrained_proj_ws_bytes": ("l", "ii"),
+    "t4r_pretrained_proj_fwd": ("i", _PP + "ppppfii" + "pli" + "pppp"),
+    "t4r_pretrained_proj_bwd_ws_floats": ("l", "lii"),
+    "t4r_pretrained_proj_bwd": ("i", _PP + "pli" + "ppp" + "ii" + "ppppp"),
+}
+
 _lib = None
 
 
@@ -216,6 +227,11 @@ def optim_header_symbols():
     return _declared(OPTIM_HEADER_PATH)
 
 
+def pretrained_header_symbols():
+    """Function names declared in include/t4r_hip_pretrained.h."""
+    return _declared(PRETRAINED_HEADER_PATH)
+
+
 def load():
     """Loads the library and sets ctypes prototypes.  Raises if it is not built."""
     global _lib
@@ -226,7 +242,8 @@ def load():
             f"{LIB_PATH} not found: the HIP extension is not built "
             "(run `python -m transformers4rec_amd.build`). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (ret, args) in list(_SIGS.items()) + list(_SIGS_SAMPLING.items()) + list(_SIGS_FILTER.items()) + list(_SIGS_OPTIM.items()):
+    for name, (ret, args) in (list(_SIGS.items()) + list(_SIGS_SAMPLING.items()) + list(_SIGS_FILTER.items()) + list(_SIGS_OPTIM.items())
+                              + list(_SIGS_PRETRAINED.items())):
         fn = getattr(lib, name)
         fn.restype = ctypes.c_char_p if ret == "s" else (None if ret == "v" else _C[ret])
         fn.argtypes = [_C[a] for a in args]

@@ -29,8 +29,8 @@ said -- BEFORE that forward -- that it exchanges `.grad` itself after backward:
 `backward()` and `optimizer.step()`, or `distributed.GradReducer` / `SparseRowExchange`.
 
 There is no CPU fallback: a CPU tensor raises _lib.T4RHipError like the rest of the package.
-Configurations off the hot path (PLM/RTD masking, custom projection blocks, pretrained-embedding
-modules, transformer bodies other than XLNet / GPT-2 / BERT) raise NotImplementedError when the
+Configurations off the hot path (PLM/RTD masking, custom projection blocks, transformer bodies
+other than XLNet / GPT-2 / BERT) raise NotImplementedError when the
 shadow is built; nothing silently routes through the reference's torch code.
 """
 import torch
@@ -179,6 +179,37 @@ def _dense_relu_dim(proj):
     return int(lin.weight.shape[0])
 
 
+def shadow_pretrained(rp):
+    """HIP-side PretrainedEmbeddingFeatures of the (built) reference module `rp`; parameters are tied by name by the caller"""
+    if _cls(rp) != "PretrainedEmbeddingFeatures":
+        raise NotImplementedError(f"dropin: pretrained module {_cls(rp)} is off the HIP hot path")
+    if getattr(rp, "sequence_combiner", None) is not None:
+        raise NotImplementedError("dropin: sequence_combiner on pretrained embeddings is off the HIP hot path")
+    if _transformations(getattr(rp, "pre", None)):
+        raise NotImplementedError("dropin: pre transformations on pretrained embeddings are off the HIP hot path")
+    post = _transformations(getattr(rp, "post", None))
+    if any(_cls(t) != "TabularLayerNorm" for t in post) or len(post) > 1:
+        raise NotImplementedError("dropin: post transformations on pretrained embeddings other than the layer-norm normalizer "
+                                  "are off the HIP hot path")
+    names = list(rp.features)
+    proj = getattr(rp, "projection", None)
+    if rp.pretrained_output_dims and proj is None:
+        raise NotImplementedError("dropin: the reference pretrained module is not built yet (no projection layers)")
+    in_dims, out_dims = {}, {}
+    for n in names:
+        if proj is not None and n in proj:
+            out_dims[n], in_dims[n] = int(proj[n].weight.shape[0]), int(proj[n].weight.shape[1])
+        elif post and n in post[0].feature_layer_norm:
+            in_dims[n] = int(post[0].feature_layer_norm[n].weight.shape[0])
+        else:
+            sizes = getattr(rp, "input_size", None) or {}
+            if n not in sizes:
+                raise NotImplementedError(f"dropin: the width of pretrained feature {n!r} is unknown (module not built)")
+            in_dims[n] = int(sizes[n][-1])
+    return F.PretrainedEmbeddingFeatures(names, in_dims, pretrained_output_dims=out_dims or None,
+                                         normalizer="layer-norm" if post else None)
+
+
 def shadow_features(ref):
     """HIP-side TabularSequenceFeatures sharing every parameter with the reference module `ref`."""
     merge = ref.to_merge
@@ -186,7 +217,8 @@ def shadow_features(ref):
         inc = getattr(getattr(m, "filter_features", None), "to_include", None)
         return inc is not None and len(inc) == 0 and not list(m.parameters())
 
-    extra = [k for k in merge.keys() if k not in ("categorical_module", "continuous_module") and not _empty(merge[k])]
+    extra = [k for k in merge.keys() if k not in ("categorical_module", "continuous_module", "pretrained_embedding_module")
+             and not _empty(merge[k])]
     if extra or "categorical_module" not in merge:
         raise NotImplementedError(f"dropin: feature modules {extra or 'without categorical_module'} are off the "
                                   "HIP hot path")
@@ -214,9 +246,12 @@ def shadow_features(ref):
             else:
                 raise NotImplementedError(f"dropin: continuous module {kind} (e.g. continuous_projection) is off "
                                           "the HIP hot path")
+        pt = None
+        if "pretrained_embedding_module" in merge and not _empty(merge["pretrained_embedding_module"]):
+            pt = shadow_pretrained(merge["pretrained_embedding_module"])
         sh = F.TabularSequenceFeatures(cat, cont, _aggregation_name(ref.aggregation),
                                        _dense_relu_dim(ref.projection_module), None, getattr(ref, "schema", None),
-                                       getattr(ref, "max_sequence_length", None))
+                                       getattr(ref, "max_sequence_length", None), pretrained_embedding_module=pt)
         sh.set_masking(shadow_masking(ref.masking))
     tie_by_name(sh, ref, "TabularSequenceFeatures")
     return sh

@@ -350,6 +350,136 @@ class ContinuousFeatures(nn.Module):
         self.post = None
 
 
+class PretrainedEmbeddingFeatures(nn.Module):
+    """Drop-in for tr.PretrainedEmbeddingFeatures (features/embedding.py:599-740): frozen text / image vectors of the items
+    (or of the session), optionally projected (`projection.<feature>`, torch.nn.Linear with its default init) and normalised
+    (`post.feature_layer_norm.<feature>`).
+
+      features                names of the pretrained features
+      input_dims              {name: E}, the width of each feature's vectors (the reference learns it at build time from the
+                              schema's shapes; here it is a constructor argument, an int serving every feature)
+      pretrained_output_dims  None, an int (every feature is projected to it) or a dict (only the named ones are)
+      normalizer              None, "layer-norm" or a TabularLayerNorm
+
+    Every feature has two forms.  DENSE, the reference's wire form: inputs[name] is a float [B, L, E] (or [B, E]) tensor, projected
+    by the general GEMM and the LayerNorm kernels.  DEVICE-RESIDENT: `attach_table(name, weight [V, E], key=None)` packs the frozen
+    table once into an fp16 image (ops.pack_item_table) kept as a non-persistent buffer -- it follows .to(device) and is not in the
+    state_dict --, and the feature is computed from the ids inputs[key] (default: the item-id column) by the fused gather +
+    projection kernel (csrc/pretrained_proj.hip); inputs[name] need not exist.  The table's values are then its fp16 roundings,
+    as under the reference's autocast; there is no gradient for the table in either form."""
+
+    def __init__(self, features, input_dims, pretrained_output_dims=None, sequence_combiner=None, pre=None, post=None,
+                 aggregation=None, normalizer=None, schema=None):
+        super().__init__()
+        if sequence_combiner is not None:
+            raise NotImplementedError("sequence_combiner on pretrained embeddings is off the hot path")
+        if pre is not None or post is not None or aggregation is not None:
+            raise NotImplementedError("pre / post / aggregation on PretrainedEmbeddingFeatures other than `normalizer` are off "
+                                      "the hot path")
+        self.features = list(features)
+        self.schema = schema
+        self.pretrained_output_dims = pretrained_output_dims
+        self.sequence_combiner = None
+        if isinstance(input_dims, int):
+            input_dims = {n: input_dims for n in self.features}
+        missing = [n for n in self.features if n not in input_dims]
+        if missing:
+            raise ValueError(f"PretrainedEmbeddingFeatures: no input width for {missing}")
+        self.input_dims = {n: int(input_dims[n]) for n in self.features}
+        if isinstance(pretrained_output_dims, dict):
+            unknown = [n for n in pretrained_output_dims if n not in self.features]
+            if unknown:
+                raise ValueError(f"pretrained_output_dims names unknown features: {unknown}")
+            out = {n: int(d) for n, d in pretrained_output_dims.items()}
+        elif pretrained_output_dims:
+            out = {n: int(pretrained_output_dims) for n in self.features}
+        else:
+            out = {}
+        if out:
+            self.projection = nn.ModuleDict({n: _Linear(self.input_dims[n], out[n]) for n in self.features if n in out})
+        self._out_dims = {n: out.get(n, self.input_dims[n]) for n in self.features}
+        if isinstance(normalizer, str):
+            if normalizer != "layer-norm":
+                raise NotImplementedError(f"normalizer {normalizer!r}: only 'layer-norm' is on the hot path")
+            self.post = TabularLayerNorm(self._out_dims)        # width-1 features are skipped, as in the reference
+        elif isinstance(normalizer, TabularLayerNorm):
+            self.post = normalizer.build(self._out_dims)
+        elif normalizer is None:
+            self.post = None
+        else:
+            raise NotImplementedError("normalizer must be None, 'layer-norm' or a TabularLayerNorm")
+        self.embedding_tables = nn.ModuleDict()     # no trainable tables (TabularSequenceFeatures._apply_pre walks this name)
+        self._keys = {}
+
+    @classmethod
+    def from_schema(cls, schema, tags=None, pretrained_output_dims=None, sequence_combiner=None, normalizer=None, pre=None,
+                    post=None, aggregation=None, input_dims=None, **kwargs):
+        """features/embedding.py:670-695; the width of a column is input_dims[name], else the column's `embedding_dim`"""
+        if tags:
+            schema = schema.select_by_tag(tags)
+        names = schema.column_names
+        if not names:
+            return None
+        dims = dict(input_dims or {}) if not isinstance(input_dims, int) else {n: input_dims for n in names}
+        for c in schema.feature:
+            if c.name not in dims and getattr(c, "embedding_dim", None):
+                dims[c.name] = int(c.embedding_dim)
+        return cls(names, dims, pretrained_output_dims=pretrained_output_dims, sequence_combiner=sequence_combiner, pre=pre,
+                   post=post, aggregation=aggregation, normalizer=normalizer, schema=schema)
+
+    # ------------------------------------------------------------------ device-resident tables
+    @staticmethod
+    def _image_name(name):
+        return "_image_" + name
+
+    def attach_table(self, name, weight, key=None):
+        """keeps the frozen table weight [V, E] of feature `name` on the device as an fp16 image; the feature is then looked up
+        by inputs[key] (None: the item-id column of the block this module is merged into)"""
+        if name not in self.features:
+            raise KeyError(f"attach_table: {name!r} is not one of {self.features}")
+        if not hasattr(self, "projection") or name not in self.projection:
+            raise ValueError(f"attach_table: the device-resident form of {name!r} is gather + projection in one kernel and needs "
+                             f"a projection for it: name it in pretrained_output_dims")
+        if weight.dim() != 2 or weight.shape[1] != self.input_dims[name]:
+            raise ValueError(f"attach_table: {name!r} takes a [V, {self.input_dims[name]}] table, got {tuple(weight.shape)}")
+        image = ops.pack_item_table(weight.detach().float().contiguous(), "fp16")
+        self.detach_table(name)
+        # the buffer is the whole padded image [V, ld]: a copy to another device keeps the aligned row pitch
+        ld = image.stride(0) if image.shape[0] > 1 else ops.image_ld(image.shape[1])
+        self.register_buffer(self._image_name(name), torch.as_strided(image, (image.shape[0], ld), (ld, 1)), persistent=False)
+        self._keys[name] = key
+        return self
+
+    def detach_table(self, name):
+        if self._image_name(name) in self._buffers:
+            del self._buffers[self._image_name(name)]
+        self._keys.pop(name, None)
+        return self
+
+    def table_image(self, name):
+        """the attached fp16 image of `name` as its [V, E] view, or None"""
+        buf = self._buffers.get(self._image_name(name))
+        return None if buf is None else buf[:, :self.input_dims[name]]
+
+    def table_key(self, name):
+        return self._keys.get(name)
+
+    def output_dim(self, name):
+        return self._out_dims[name]
+
+    def layer_norm(self, name):
+        if self.post is None or name not in self.post.feature_layer_norm:
+            return None
+        return self.post.feature_layer_norm[name]
+
+    def forward_output_size(self, input_sizes=None):
+        out = {}
+        for n in self.features:
+            lead = list(input_sizes[n][:-1]) if input_sizes and n in input_sizes else [-1]
+            out[n] = torch.Size(lead + [self._out_dims[n]])
+        return out
+
+
 _POST_SALT = 4
 _post_seed_value = None
 
@@ -415,6 +545,69 @@ def _post_bwd(saved, dy):
     return dy
 
 
+def _pretrained_fwd(mod, pt, name, inputs, B, L, col, dim, err, save):
+    """one pretrained feature's rows -> (feature dict for ops.seq_features_fwd, record for _pretrained_bwd)"""
+    lin = pt.projection[name] if hasattr(pt, "projection") and name in pt.projection else None
+    ln = pt.layer_norm(name)
+    image = pt.table_image(name)
+    if image is not None:
+        key = pt.table_key(name) or mod.categorical_module.item_id
+        ids = inputs[key].contiguous()
+        per_session = ids.ndim == 1
+        rows, xhat, rstd = ops.pretrained_proj_fwd(
+            image, ids, lin.weight.detach(), lin.bias.detach(), None if ln is None else ln.weight.detach(),
+            None if ln is None else ln.bias.detach(), 1e-5 if ln is None else ln.eps, err_flag=err,
+            save=save)
+        rec = dict(form="image", image=image, ids=ids, xhat=xhat, rstd=rstd, lin=lin, ln=ln, per_session=per_session)
+    else:
+        if name not in inputs:
+            raise KeyError(f"pretrained feature {name!r}: no inputs[{name!r}] and no attached table (attach_table)")
+        x = inputs[name]
+        if x.ndim not in (2, 3) or x.shape[-1] != pt.input_dims[name]:
+            raise ValueError(f"pretrained feature {name!r}: expected [B, L, {pt.input_dims[name]}] or [B, {pt.input_dims[name]}], "
+                             f"got {tuple(x.shape)}")
+        per_session = x.ndim == 2
+        x2 = x.contiguous().float().view(-1, x.shape[-1])
+        rows = z = x2
+        mean = rstd = None
+        if lin is not None:
+            rows = z = ops.gemm(x2, lin.weight.detach(), False, True, bias=lin.bias.detach(), epilogue=ops.EPI_BIAS)
+        if ln is not None:
+            rows, mean, rstd = ops.add_layernorm_fwd(z, None, ln.weight.detach(), ln.bias.detach(), ln.eps)
+        rec = dict(form="dense", x=x2, z=z, mean=mean, rstd=rstd, lin=lin, ln=ln, per_session=per_session)
+    rec["feat"] = dict(kind=3 if per_session else 1, input=rows, table=None, dim=dim, col=col)
+    return rec["feat"], rec
+
+
+def _pretrained_bwd(rec, d2, col, dim, B, L):
+    """parameter gradients of one pretrained feature from its columns of the aggregate's gradient d2 [B * L, W]"""
+    lin, ln = rec["lin"], rec["ln"]
+    if lin is None and ln is None:
+        return      # a pass-through column block
+    if rec["per_session"]:      # broadcast over L: the gradient is the sum over the sequence
+        g, gcol = ops.seq_sum_cols(d2, col, dim, B, L), 0
+    else:
+        g, gcol = d2, col
+    if rec["form"] == "image":
+        ops.pretrained_proj_bwd(g, rec["image"], rec["ids"], None if ln is None else ln.weight.detach(), rec["xhat"], rec["rstd"],
+                                _grad_buf(lin.weight), _grad_buf(lin.bias), None if ln is None else _grad_buf(ln.weight),
+                                None if ln is None else _grad_buf(ln.bias), col=gcol)
+        return
+    if g.shape[1] != dim:
+        g = ops.copy_cols_out(g, col, dim)
+    if ln is not None:
+        g = ops.add_layernorm_bwd(rec["z"], None, ln.weight.detach(), rec["mean"], rec["rstd"], g, _grad_buf(ln.weight),
+                                  _grad_buf(ln.bias))
+    if lin is not None:
+        db = _grad_buf(lin.bias)
+        if dim % 4 == 0:
+            ops.colsum_(g, db)
+        else:
+            ones = torch.ones((g.shape[0], 1), device=g.device, dtype=torch.float32)
+            ops.gemm(g, ones, True, False, accumulate=True, out=db.view(dim, 1))
+        ops.gemm_wgrad(g, rec["x"], _grad_buf(lin.weight))
+
+
 class _SeqFeaturesFn(torch.autograd.Function):
     """gather (+soft embeddings) -> aggregate -> [ReLU projection] -> masking, one autograd node.
     Parameter gradients are accumulated straight into `.grad` (flat-buffer friendly)."""
@@ -422,7 +615,7 @@ class _SeqFeaturesFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, mod, inputs, training, testing):
         ctx.carrier = bool(mod.__dict__.get("_t4r_carrier_on", False))      # anchor = the GradCarrier's one-float output
-        cat, cont = mod.categorical_module, mod.continuous_module
+        cat, cont, pt = mod.categorical_module, mod.continuous_module, mod.pretrained_module
         names = mod._feature_order
         item_ids = inputs[cat.item_id].contiguous()
         B, L = item_ids.shape
@@ -433,7 +626,7 @@ class _SeqFeaturesFn(torch.autograd.Function):
             mask = masking.mask_schema
             mask_mode = masking.apply_mode(training, testing)
             L_out = mask.shape[1]
-        feats, soft_saved, post_saved = [], {}, {}
+        feats, soft_saved, post_saved, pt_saved = [], {}, {}, {}
         step = mod._post_step
         for fidx, name in enumerate(names):
             col, dim = mod._cols[name], mod._dims[name]
@@ -453,6 +646,11 @@ class _SeqFeaturesFn(torch.autograd.Function):
                                              err_flag=mod._err_flag(item_ids.device)).view(B * Lf, dim)
                     e, post_saved[name] = _post_fwd(cat, cat._post, name, fidx, e, step)
                     f = dict(kind=3 if per_session else 1, input=e, table=None, dim=dim, col=col)
+                feats.append(f)
+            elif pt is not None and name in pt.features:
+                # (grad mode is off inside forward: whether a backward can follow is the anchor's needs_input_grad)
+                f, pt_saved[name] = _pretrained_fwd(mod, pt, name, inputs, B, L, col, dim, mod._err_flag(item_ids.device),
+                                                    save=ctx.needs_input_grad[0])
                 feats.append(f)
             elif isinstance(cont, ContinuousFeatures):
                 x = inputs[name].contiguous().float().view(B * L, 1)
@@ -485,7 +683,10 @@ class _SeqFeaturesFn(torch.autograd.Function):
                            bias=lin.bias.detach(), epilogue=ops.EPI_BIAS_RELU).view(B, L_out, -1)
             if masking is not None:
                 ops.apply_mask_fwd_(out, mask, memb.detach(), mask_mode)
-        ctx.mod, ctx.inputs, ctx.soft_saved, ctx.post_saved = mod, inputs, soft_saved, post_saved
+        ctx.mod, ctx.inputs, ctx.soft_saved, ctx.post_saved, ctx.pt_saved = mod, inputs, soft_saved, post_saved, pt_saved
+        if mod._aggregation != "element-wise-sum-item-multi":
+            for rec in pt_saved.values():
+                del rec["feat"]     # only that aggregation's backward aggregates the features again
         # the sort behind the deterministic table gradient depends on the ids only: done here, in the forward
         ctx.sorted_ids = {}
         if training:
@@ -534,6 +735,8 @@ class _SeqFeaturesFn(torch.autograd.Function):
         if agg == "element-wise-sum-item-multi":
             item = cat.item_id
             def again(n):   # the feature as the forward aggregated it (post-transformed rows are recomputed)
+                if n in ctx.pt_saved:
+                    return dict(ctx.pt_saved[n]["feat"], dim=W, col=0)
                 ids_n = ctx.inputs[n].contiguous()
                 tabn = cat.embedding_tables[n].weight.detach()
                 f = dict(kind=2 if ids_n.ndim == 1 else 0, input=ids_n, table=tabn, dim=W, col=0, rows=tabn.shape[0])
@@ -569,6 +772,9 @@ class _SeqFeaturesFn(torch.autograd.Function):
                     _table_scatter(ctx, name, g, ids_f, tab, 0, dim, cat.padding_idx)
                 else:
                     _table_scatter(ctx, name, src.view(-1, src.shape[-1]), ids_f, tab, col, dim, cat.padding_idx)
+            elif name in ctx.pt_saved:
+                src = d_other if agg == "element-wise-sum-item-multi" else d
+                _pretrained_bwd(ctx.pt_saved[name], src.view(B * L, -1), col, dim, B, L)
             elif isinstance(cont, ContinuousFeatures):
                 continue    # no parameters behind a pass-through column
             else:
@@ -595,7 +801,8 @@ class TabularSequenceFeatures(nn.Module):
     def __init__(self, categorical_module: SequenceEmbeddingFeatures,
                  continuous_module: Optional[SoftEmbeddingFeatures] = None, aggregation: str = "concat",
                  projection_dim: Optional[int] = None, masking: Optional[MaskSequence] = None,
-                 schema=None, max_sequence_length: Optional[int] = None):
+                 schema=None, max_sequence_length: Optional[int] = None,
+                 pretrained_embedding_module: Optional[PretrainedEmbeddingFeatures] = None):
         super().__init__()
         if aggregation not in ops.AGG:
             raise ValueError(f"aggregation must be one of {sorted(ops.AGG)}")
@@ -605,6 +812,8 @@ class TabularSequenceFeatures(nn.Module):
         if continuous_module is not None:
             mods["continuous_module"] = continuous_module
         mods["categorical_module"] = categorical_module
+        if pretrained_embedding_module is not None:
+            mods["pretrained_embedding_module"] = pretrained_embedding_module
         self.to_merge = nn.ModuleDict(mods)
         self._aggregation = aggregation
         dims = {n: t.embedding_dim for n, t in categorical_module.embedding_tables.items()}
@@ -612,6 +821,11 @@ class TabularSequenceFeatures(nn.Module):
             dims.update({n: 1 for n in continuous_module.names})
         elif continuous_module is not None:
             dims.update({n: s.embedding_table.embedding_dim for n, s in continuous_module.embedding_tables.items()})
+        if pretrained_embedding_module is not None:
+            clash = [n for n in pretrained_embedding_module.features if n in dims]
+            if clash:
+                raise ValueError(f"pretrained features share names with other features: {clash}")
+            dims.update({n: pretrained_embedding_module.output_dim(n) for n in pretrained_embedding_module.features})
         # ConcatFeatures order = sorted(feature names) (tabular/aggregation.py:43)
         self._feature_order = sorted(dims)
         self._dims = dims
@@ -642,6 +856,10 @@ class TabularSequenceFeatures(nn.Module):
     @property
     def continuous_module(self):
         return self.to_merge["continuous_module"] if "continuous_module" in self.to_merge else None
+
+    @property
+    def pretrained_module(self):
+        return self.to_merge["pretrained_embedding_module"] if "pretrained_embedding_module" in self.to_merge else None
 
     @property
     def masking(self):
@@ -682,11 +900,12 @@ class TabularSequenceFeatures(nn.Module):
     # ------------------------------------------------------------------ construction
     @classmethod
     def from_schema(cls, schema, continuous_tags=(Tags.CONTINUOUS,), categorical_tags=(Tags.CATEGORICAL,),
-                    aggregation=None, max_sequence_length=None, continuous_soft_embeddings=False,
+                    pretrained_embeddings_tags=(Tags.EMBEDDING,), aggregation=None, max_sequence_length=None, continuous_soft_embeddings=False,
                     d_output=None, masking=None, embedding_dims=None, embedding_dim_default=64,
                     soft_embedding_cardinalities=None, soft_embedding_cardinality_default=10,
                     soft_embedding_dims=None, soft_embedding_dim_default=8, layer_norm=True,
-                    projection=None, continuous_projection=None, pre=None, post=None, **kwargs):
+                    projection=None, continuous_projection=None, pre=None, post=None, pretrained_output_dims=None,
+                    normalizer=None, pretrained_input_dims=None, **kwargs):
         """Same keyword surface as the reference (features/sequence.py:140-229,
         features/embedding.py:103-221, :313-410) for the arguments the hot path uses."""
         if projection is not None or continuous_projection is not None:
@@ -703,7 +922,18 @@ class TabularSequenceFeatures(nn.Module):
         # (features/tabular.py:150-185); soft embeddings replace `post` by their LayerNorm
         cat = SequenceEmbeddingFeatures(tables, item_id=item_id, pre=pre, post=post)
         cont = None
-        cont_names = [c for c in schema.select_by_tag(list(continuous_tags)).column_names if c not in cards]
+        pt = None
+        if pretrained_embeddings_tags:
+            tags = pretrained_embeddings_tags
+            pt = PretrainedEmbeddingFeatures.from_schema(
+                schema, tags=list(tags) if isinstance(tags, (list, tuple, set)) else [tags],
+                pretrained_output_dims=pretrained_output_dims, normalizer=normalizer, input_dims=pretrained_input_dims)
+        if pt is not None and (pre is not None or post is not None):
+            raise NotImplementedError("pre / post transformations on pretrained embeddings other than `normalizer` are off the "
+                                      "hot path")
+        pt_names = set(pt.features) if pt is not None else set()
+        cont_names = [c for c in schema.select_by_tag(list(continuous_tags)).column_names
+                      if c not in cards and c not in pt_names]
         if cont_names and not continuous_soft_embeddings:
             cont = ContinuousFeatures(cont_names, pre=pre, post=post)     # features/continuous.py:60-63
         elif cont_names:
@@ -713,7 +943,7 @@ class TabularSequenceFeatures(nn.Module):
                  for n in cont_names}, layer_norm=layer_norm, pre=pre, post=None if layer_norm else post)
         if (masking or d_output) and not aggregation:
             aggregation = "concat"
-        out = cls(cat, cont, aggregation or "concat", d_output, None, schema, max_sequence_length)
+        out = cls(cat, cont, aggregation or "concat", d_output, None, schema, max_sequence_length, pretrained_embedding_module=pt)
         hidden = out.output_size()[-1]
         if masking is not None and item_id is None:
             raise ValueError("For masking a categorical_module is required including an item_id.")

@@ -123,6 +123,8 @@ def input_block_of(model):
 
     f = model.input_features
     cat, cont = f.categorical_module, f.continuous_module
+    if getattr(f, "pretrained_module", None) is not None:
+        raise NotImplementedError("functional path: pretrained-embedding features run through the module path only")
     if f._aggregation != "concat" and len(f._feature_order) > 1:
         raise NotImplementedError("functional path: concat aggregation only")
     if cat._post is not None or getattr(cat, "_pre", None) is not None:

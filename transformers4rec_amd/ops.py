@@ -1521,3 +1521,58 @@ def adamw_step_(param, grad, exp_avg, exp_avg_sq, step, lr=1e-3, betas=(0.9, 0.9
     if n < 0:
         raise _lib.T4RHipError(lib.t4r_last_error().decode())
     return n
+
+
+# ------------------------------------------------------------------------------------ pretrained-embedding features
+# (include/t4r_hip_pretrained.h, csrc/pretrained_proj.hip)
+def _pretrained_image(what, image, ids, E):
+    for t, name in ((image, "image"), (ids, "ids")):
+        if not t.is_cuda:
+            raise _lib.T4RHipError(f"{what}: {name} must be a HIP device tensor (got {t.device}); there is no CPU path")
+    if image.dtype not in _H16:
+        raise TypeError(f"{what}: image: expected a 16-bit serving image (ops.pack_item_table), got {image.dtype}")
+    if image.dim() != 2 or image.stride(1) != 1 or image.shape[1] != E:
+        raise ValueError(f"{what}: image must be a row-major [rows, {E}] view of a packed table")
+    return _row_pitch(image, image_ld(E))
+
+
+def pretrained_proj_ws_bytes(E, P):
+    return int(_lib.load().t4r_pretrained_proj_ws_bytes(int(E), int(P)))
+
+
+def pretrained_proj_fwd(image, ids, W, b, ln_w=None, ln_b=None, eps=1e-5, T=None, out=None, col=0, err_flag=None, save=True):
+    """rows of the packed fp16 table `image` [V, E] gathered by ids (int64, T tokens or T / L per-session ids) and projected by
+    W [P, E], b [P] (+ LayerNorm ln_w, ln_b) in one kernel -> (out, xhat, rstd): out [T, P] fp32, or columns [col, col + P) of the
+    given 2-D `out`; xhat [T, P], rstd [T] what pretrained_proj_bwd needs (None without LayerNorm or with save=False)."""
+    P, E = W.shape
+    ldp = _pretrained_image("pretrained_proj_fwd", image, ids, E)
+    T = ids.numel() if T is None else int(T)
+    if ids.numel() == 0 or T % ids.numel():
+        raise ValueError(f"pretrained_proj_fwd: {ids.numel()} ids do not divide {T} tokens")
+    if out is None:
+        out = torch.empty((T, P), device=image.device, dtype=torch.float32)
+    ln = ln_w is not None
+    xhat = torch.empty((T, P), device=image.device, dtype=torch.float32) if ln and save else None
+    rstd = torch.empty(T, device=image.device, dtype=torch.float32) if ln and save else None
+    ws = torch.empty(max(16, pretrained_proj_ws_bytes(E, P)), device=image.device, dtype=torch.uint8)
+    call("t4r_pretrained_proj_fwd", _stream(), _H16[image.dtype], image.data_ptr(), ldp, image.shape[0],
+         _chk(ids, torch.int64, "ids"), T, T // ids.numel(), _chk(W, torch.float32, "W"), _p(b, torch.float32, "b"),
+         _p(ln_w, torch.float32, "ln_w"), _p(ln_b, torch.float32, "ln_b"), float(eps), E, P,
+         out.data_ptr(), _row_pitch(out, out.shape[1]), int(col), _p(xhat), _p(rstd), ws.data_ptr(), _p(err_flag, torch.int32, "err_flag"))
+    return out, xhat, rstd
+
+
+def pretrained_proj_bwd(dout, image, ids, ln_w, xhat, rstd, d_W, d_b, d_ln_w=None, d_ln_b=None, col=0):
+    """the parameter gradients of pretrained_proj_fwd, ACCUMULATED into d_W [P, E], d_b [P] (and d_ln_w, d_ln_b [P]), from
+    columns [col, col + P) of dout [..., ld]; the table has no gradient.  Bit-reproducible (no float atomics)."""
+    P, E = d_W.shape
+    ldp = _pretrained_image("pretrained_proj_bwd", image, ids, E)
+    ld = dout.shape[-1]
+    T = dout.numel() // ld
+    if ids.numel() == 0 or T % ids.numel():
+        raise ValueError(f"pretrained_proj_bwd: {ids.numel()} ids do not divide {T} tokens")
+    ws = torch.empty(max(4, _lib.load().t4r_pretrained_proj_bwd_ws_floats(T, E, P)), device=dout.device, dtype=torch.float32)
+    call("t4r_pretrained_proj_bwd", _stream(), _H16[image.dtype], image.data_ptr(), ldp, image.shape[0],
+         _chk(ids, torch.int64, "ids"), T, T // ids.numel(), _chk(dout, torch.float32, "dout"), ld, int(col),
+         _p(ln_w, torch.float32, "ln_w"), _p(xhat), _p(rstd), E, P, _chk(d_W, torch.float32, "d_W"), _p(d_b, torch.float32, "d_b"),
+         _p(d_ln_w), _p(d_ln_b), ws.data_ptr())

@@ -45,6 +45,7 @@ class ColumnSchema:
     tags: List[Tags] = field(default_factory=list)
     int_domain: Optional[IntDomain] = None
     value_count: Optional[ValueCount] = None
+    embedding_dim: Optional[int] = None      # width of a pretrained-embedding column (Tags.EMBEDDING)
 
 
 def _tag_values(tags):
