@@ -15,6 +15,7 @@ SAMPLING_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_
 FILTER_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_filter.h")
 OPTIM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_optim.h")
 PRETRAINED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_pretrained.h")
+ATTN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_attn.h")
 
 _P, _I, _L, _F, _Q = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_ulonglong
 _C = {"p": _P, "i": _I, "l": _L, "f": _F, "Q": _Q}
@@ -194,6 +195,13 @@ _SIGS_PRETRAINED = {
     "t4r_pretrained_proj_bwd": ("i", _PP + "pli" + "ppp" + "ii" + "ppppp"),
 }
 
+# the sixth header, include/t4r_hip_attn.h (tests/test_attn_prob_cpu.py checks this table against it): the one-kernel attention
+# forward and the attention core's backward with the `prob` pointer
+_SIGS_ATTN = {
+    "t4r_xlnet_attn_block_fwd_prob": ("i", "ppppp" + "l" + "pppp" + "pppppppp" + "iiii" + "ffQQQ" + "p"),
+    "t4r_xlnet_attn_bwd_prob": ("i", "p" * 16 + "iiii" + "ifQQ"),
+}
+
 _lib = None
 
 
@@ -232,6 +240,11 @@ def pretrained_header_symbols():
     return _declared(PRETRAINED_HEADER_PATH)
 
 
+def attn_header_symbols():
+    """Function names declared in include/t4r_hip_attn.h."""
+    return _declared(ATTN_HEADER_PATH)
+
+
 def load():
     """Loads the library and sets ctypes prototypes.  Raises if it is not built."""
     global _lib
@@ -243,7 +256,7 @@ def load():
             "(run `python -m transformers4rec_amd.build`). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (ret, args) in (list(_SIGS.items()) + list(_SIGS_SAMPLING.items()) + list(_SIGS_FILTER.items()) + list(_SIGS_OPTIM.items())
-                              + list(_SIGS_PRETRAINED.items())):
+                              + list(_SIGS_PRETRAINED.items()) + list(_SIGS_ATTN.items())):
         fn = getattr(lib, name)
         fn.restype = ctypes.c_char_p if ret == "s" else (None if ret == "v" else _C[ret])
         fn.argtypes = [_C[a] for a in args]

@@ -543,9 +543,9 @@ int t4r_xlnet_attn_mfma_fwd(hipStream_t st, const float* q, const float* k, cons
                             const float* rw, const float* rr, float* out, float* lse, int B, int L, int n_head,
                             int d_head, float scale, long kr_bstride, DropCfg drop, const int* key_len);
 int t4r_xlnet_attn_mfma_bwd(hipStream_t st, const float* q, const float* k, const float* v, const float* kr,
-                            const float* rw, const float* rr, const float* lse, const float* dout, float* dq,
-                            float* dk, float* dv, float* part, float* dkr, float* d_rw, float* d_rr, int B, int L,
-                            int n_head, int d_head, float scale, long kr_bstride, DropCfg drop, const int* key_len);
+                            const float* rw, const float* rr, const float* lse, const float* prob, const float* dout,
+                            float* dq, float* dk, float* dv, float* part, float* dkr, float* d_rw, float* d_rr, int B,
+                            int L, int n_head, int d_head, float scale, long kr_bstride, DropCfg drop, const int* key_len);
 #ifdef T4R_EXPERIMENTAL
 // the fp32-MFMA core with the permuted k-slots (tools/experimental: phase 3 of the one-kernel backward as its own launch;
 // measured slower than xlnet_attn_mfma_bwd_kernel, not in the product library)
@@ -644,14 +644,19 @@ static int attn_bwd_launch(hipStream_t st, const float* q, const float* k, const
 }
 
 // d_rw / d_rr are ACCUMULATED into (parameter gradients); dq/dk/dv/dk_r are overwritten.
-extern "C" int t4r_xlnet_attn_bwd(void* stream, const float* q, const float* k, const float* v,
-                                  const float* k_r, const float* r_w_bias, const float* r_r_bias,
-                                  const float* out, const float* lse, const float* dout, float* dq,
-                                  float* dk, float* dv, float* dk_r, float* d_r_w_bias,
-                                  float* d_r_r_bias, float* workspace, int B, int L, int n_head,
-                                  int d_head, int kr_per_batch, float drop_p, unsigned long long seed,
-                                  unsigned long long ctr_hi, const int* key_len) {
+// prob: null, or the probabilities before dropout [B][n_head][L][L] that t4r_xlnet_attn_block_fwd_prob left (the one-wave
+// matrix-core kernel then reads them instead of recomputing the scores; lse is not read and may be null).  An internal entry:
+// the layer (xlnet_layer.hip) and the two public ones below call it.
+int t4r_xlnet_attn_bwd_impl(void* stream, const float* q, const float* k, const float* v, const float* k_r,
+                            const float* r_w_bias, const float* r_r_bias, const float* out, const float* lse,
+                            const float* prob, const float* dout, float* dq, float* dk, float* dv, float* dk_r,
+                            float* d_r_w_bias, float* d_r_r_bias, float* workspace, int B, int L, int n_head, int d_head,
+                            int kr_per_batch, float drop_p, unsigned long long seed, unsigned long long ctr_hi,
+                            const int* key_len) {
     if (B == 0) return 0;
+    T4R_CHECK_ARG(!prob || (n_head > 0 && t4r_xlnet_attn_mfma_ok(L, d_head)),
+                  "xlnet_attn_bwd: stored probabilities are read by the one-wave kernels only (L <= 32, d_head 16 / 32)");
+    T4R_CHECK_ARG(!prob || (reinterpret_cast<uintptr_t>(prob) & 15) == 0, "xlnet_attn_bwd: prob must be 16-byte aligned");
     T4R_CHECK_ARG(L >= 1, "xlnet_attn: L must be at least 1");
     const int D = n_head * d_head;
     const float scale = 1.0f / sqrtf((float)d_head);
@@ -674,8 +679,9 @@ extern "C" int t4r_xlnet_attn_bwd(void* stream, const float* q, const float* k, 
     }
 #endif
     if (use_mfma(L, d_head))
-        return t4r_xlnet_attn_mfma_bwd(st, q, k, v, k_r, r_w_bias, r_r_bias, lse, dout, dq, dk, dv, workspace, dk_r,
+        return t4r_xlnet_attn_mfma_bwd(st, q, k, v, k_r, r_w_bias, r_r_bias, lse, prob, dout, dq, dk, dv, workspace, dk_r,
                                        d_r_w_bias, d_r_r_bias, B, L, n_head, d_head, scale, bs, dc, key_len);
+    T4R_CHECK_ARG(!prob, "xlnet_attn_bwd: stored probabilities are read by the one-wave matrix-core kernels only");
     T4R_CHECK_ARG(attn_bwd_smem(L, D, n_head) <= 160 * 1024, "xlnet_attn_bwd: L*d_model too large for LDS");
     switch (d_head) {
         case 8: return attn_bwd_launch<8>(st, q, k, v, k_r, r_w_bias, r_r_bias, out, lse, dout, dq, dk, dv, workspace, dk_r, d_r_w_bias, d_r_r_bias, B, L, n_head, scale, bs, dc, key_len);
@@ -684,4 +690,27 @@ extern "C" int t4r_xlnet_attn_bwd(void* stream, const float* q, const float* k, 
     }
     t4r_set_error("xlnet_attn_bwd: d_head must be 8, 16 or 32");
     return -1;
+}
+
+extern "C" int t4r_xlnet_attn_bwd(void* stream, const float* q, const float* k, const float* v,
+                                  const float* k_r, const float* r_w_bias, const float* r_r_bias,
+                                  const float* out, const float* lse, const float* dout, float* dq,
+                                  float* dk, float* dv, float* dk_r, float* d_r_w_bias,
+                                  float* d_r_r_bias, float* workspace, int B, int L, int n_head,
+                                  int d_head, int kr_per_batch, float drop_p, unsigned long long seed,
+                                  unsigned long long ctr_hi, const int* key_len) {
+    return t4r_xlnet_attn_bwd_impl(stream, q, k, v, k_r, r_w_bias, r_r_bias, out, lse, nullptr, dout, dq, dk, dv, dk_r,
+                                   d_r_w_bias, d_r_r_bias, workspace, B, L, n_head, d_head, kr_per_batch, drop_p, seed, ctr_hi,
+                                   key_len);
+}
+// include/t4r_hip_attn.h
+extern "C" int t4r_xlnet_attn_bwd_prob(void* stream, const float* q, const float* k, const float* v, const float* k_r,
+                                       const float* r_w_bias, const float* r_r_bias, const float* prob, const float* dout,
+                                       float* dq, float* dk, float* dv, float* dk_r, float* d_r_w_bias, float* d_r_r_bias,
+                                       float* workspace, int B, int L, int n_head, int d_head, int kr_per_batch, float drop_p,
+                                       unsigned long long seed, unsigned long long ctr_hi) {
+    T4R_CHECK_ARG(prob != nullptr, "xlnet_attn_bwd_prob: null pointer");
+    return t4r_xlnet_attn_bwd_impl(stream, q, k, v, k_r, r_w_bias, r_r_bias, nullptr, nullptr, prob, dout, dq, dk, dv, dk_r,
+                                   d_r_w_bias, d_r_r_bias, workspace, B, L, n_head, d_head, kr_per_batch, drop_p, seed, ctr_hi,
+                                   nullptr);
 }

@@ -122,6 +122,7 @@ struct AttnBlockFwd {
     const float *rw, *rr;    // r_w_bias, r_r_bias [D]
     const float *gamma, *beta;
     float *qkv, *av, *lse;   // saved for the backward: [3][T][D], [T][D], [B][n_head][L]
+    float* prob;             // NULL, or [B][n_head][L][L] (16-byte aligned): the probabilities BEFORE dropout, for the core's backward
     float *ao, *mean, *rstd; // o-projection output before dropout [T][D], LayerNorm statistics [T] (all NULL: inference)
     float* h1;               // [T, D]
     const int* key_len;      // optional [B]
@@ -497,8 +498,21 @@ __global__ __launch_bounds__(D * 4) void xlnet_attn_block_fwd_kernel(AttnBlockFw
                                 if (j0 + r < L) m[r] = drop_scale(p.drop_p, mbase + j0 + r);
                         }
                     }
+                    f32x4 pn;                                                                // the probabilities before dropout
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) pv[jt][r] = pv[jt][r] * inv * m[r];          // 0 for j >= L (exp(-inf))
+                    for (int r = 0; r < 4; ++r) pn[r] = pv[jt][r] * inv;                    // 0 for j >= L (exp(-inf))
+                    if (p.prob && i < L && j0 < L) {       // kept for the core's backward: columns j < L only
+                        float* dst = p.prob + mbase + j0;
+                        if (aligned) {                     // L % 4 == 0: the lane's four columns are inside the row, 16-byte aligned
+                            st4_stream(dst, pn);
+                        } else {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r)
+                                if (j0 + r < L) dst[r] = pn[r];
+                        }
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) pv[jt][r] = pn[r] * m[r];
                 }
                 // attn_vec^T[d][i] = sum_j v[j][d] P~[i][j]:  A = a value column (k = j), B = the probabilities in place
                 f32x4 o[HC];
@@ -663,13 +677,17 @@ static thread_local int g_ab_in_on = 0;
 static thread_local unsigned long long g_ab_in_ctr = 0;
 static thread_local float* g_ab_hin = nullptr;
 void t4r_xlnet_attn_block_input_dropout(int on, unsigned long long ctr, float* hin) { g_ab_in_on = on; g_ab_in_ctr = ctr; g_ab_hin = hin; }
-extern "C" int t4r_xlnet_attn_block_fwd(void* stream, const float* h, const float* planes, const float* o, const float* kr,
-                                        long kr_bstride, const float* r_w_bias, const float* r_r_bias, const float* gamma,
-                                        const float* beta, float* qkv, float* av, float* lse, float* ao, float* mean,
-                                        float* rstd, float* h1, int B, int L, int D, int n_head, float eps, float drop_p,
-                                        unsigned long long seed, unsigned long long ctr_prob, unsigned long long ctr_out,
-                                        const int* key_len) {
+// prob: null, or [B][n_head][L][L] fp32, 16-byte aligned: the attention probabilities before dropout (exact zeros at masked
+// columns) are stored there for the core's backward.  An internal entry: the layer (xlnet_layer.hip) and the two public ones
+// below call it.
+int t4r_xlnet_attn_block_fwd_impl(void* stream, const float* h, const float* planes, const float* o, const float* kr,
+                                  long kr_bstride, const float* r_w_bias, const float* r_r_bias, const float* gamma,
+                                  const float* beta, float* qkv, float* av, float* lse, float* prob, float* ao, float* mean,
+                                  float* rstd, float* h1, int B, int L, int D, int n_head, float eps, float drop_p,
+                                  unsigned long long seed, unsigned long long ctr_prob, unsigned long long ctr_out,
+                                  const int* key_len) {
     if (B <= 0) return 0;
+    T4R_CHECK_ARG((reinterpret_cast<uintptr_t>(prob) & 15) == 0, "xlnet_attn_block_fwd: prob must be 16-byte aligned");
     T4R_CHECK_ARG(t4r_xlnet_attn_block_supported(L, D, n_head), "xlnet_attn_block_fwd: unsupported shape (L <= 32, d_head 16 / 32, d_model 32 / 64 / 128)");
     T4R_CHECK_ARG(h && planes && o && kr && r_w_bias && r_r_bias && gamma && beta && qkv && av && lse && h1, "xlnet_attn_block_fwd: null pointer");
     const bool train = ao != nullptr;
@@ -684,7 +702,7 @@ extern "C" int t4r_xlnet_attn_block_fwd(void* stream, const float* h, const floa
         p.wqkv_h = PH_.QKVT; p.wpl_h = 3L * D * D; p.wscale = PH_.scale + HS_Q;
     }
     p.rw = r_w_bias; p.rr = r_r_bias; p.gamma = gamma; p.beta = beta;
-    p.qkv = qkv; p.av = av; p.lse = lse; p.ao = ao; p.mean = mean; p.rstd = rstd; p.h1 = h1; p.key_len = key_len;
+    p.qkv = qkv; p.av = av; p.lse = lse; p.prob = prob; p.ao = ao; p.mean = mean; p.rstd = rstd; p.h1 = h1; p.key_len = key_len;
     p.B = B; p.L = L; p.S = S; p.T = (long)B * L;
     p.scale = 1.0f / sqrtf((float)dh); p.eps = eps;
     p.drop_p = make_drop(drop_p, seed, ctr_prob);
@@ -697,7 +715,8 @@ extern "C" int t4r_xlnet_attn_block_fwd(void* stream, const float* h, const floa
 #endif
     hipStream_t st = (hipStream_t)stream;
 #ifdef T4R_EXPERIMENTAL
-    { int rc2 = 0; if (attn_block2_try_launch(p, st, B, L, D, dh, &rc2)) return rc2; }     // tools/experimental (T4R_XLNET_ATTN_BLOCK2=1)
+    // tools/experimental (T4R_XLNET_ATTN_BLOCK2=1); that layout does not store the probabilities
+    if (!p.prob) { int rc2 = 0; if (attn_block2_try_launch(p, st, B, L, D, dh, &rc2)) return rc2; }
 #endif
     const dim3 grid((unsigned)((B + S - 1) / S)), block((unsigned)(D * 4));
     const size_t smem = attn_block_smem(D);
@@ -723,6 +742,25 @@ extern "C" int t4r_xlnet_attn_block_fwd(void* stream, const float* h, const floa
 #undef T4R_AB_FWD
     T4R_LAUNCH_CHECK();
     return 0;
+}
+extern "C" int t4r_xlnet_attn_block_fwd(void* stream, const float* h, const float* planes, const float* o, const float* kr,
+                                        long kr_bstride, const float* r_w_bias, const float* r_r_bias, const float* gamma,
+                                        const float* beta, float* qkv, float* av, float* lse, float* ao, float* mean,
+                                        float* rstd, float* h1, int B, int L, int D, int n_head, float eps, float drop_p,
+                                        unsigned long long seed, unsigned long long ctr_prob, unsigned long long ctr_out,
+                                        const int* key_len) {
+    return t4r_xlnet_attn_block_fwd_impl(stream, h, planes, o, kr, kr_bstride, r_w_bias, r_r_bias, gamma, beta, qkv, av, lse, nullptr,
+                                         ao, mean, rstd, h1, B, L, D, n_head, eps, drop_p, seed, ctr_prob, ctr_out, key_len);
+}
+// include/t4r_hip_attn.h
+extern "C" int t4r_xlnet_attn_block_fwd_prob(void* stream, const float* h, const float* planes, const float* o, const float* kr,
+                                             long kr_bstride, const float* r_w_bias, const float* r_r_bias, const float* gamma,
+                                             const float* beta, float* qkv, float* av, float* lse, float* prob, float* ao,
+                                             float* mean, float* rstd, float* h1, int B, int L, int D, int n_head, float eps,
+                                             float drop_p, unsigned long long seed, unsigned long long ctr_prob,
+                                             unsigned long long ctr_out, const int* key_len) {
+    return t4r_xlnet_attn_block_fwd_impl(stream, h, planes, o, kr, kr_bstride, r_w_bias, r_r_bias, gamma, beta, qkv, av, lse, prob,
+                                         ao, mean, rstd, h1, B, L, D, n_head, eps, drop_p, seed, ctr_prob, ctr_out, key_len);
 }
 
 #ifdef T4R_EXPERIMENTAL

@@ -35,6 +35,16 @@
 #ifndef T4R_ATTN_BWD_BOUNDS
 #define T4R_ATTN_BWD_BOUNDS 512
 #endif
+// The backward that READS the probabilities (HAVE_P) holds no score fragments and no Pm: 12.7 KB of LDS per wave, twelve
+// waves per CU.  At C2 (d_head 32, KH 10) per-session / shared k_r take 149 / 181 VGPRs at 512: 42.4 / 43.3 us.  768
+// (<= 168 VGPRs) compiles the per-session form to the same code and spills 12 registers of the shared one: 42.7 / 50.5 us;
+// 256 gives 44.1 / 43.4 us.  (The recomputing form at the same shape: 63 / 65 us; reading P with KH 16: 51.5 / 49.8 us.)
+#ifndef T4R_ATTN_BWD_P_BOUNDS
+#define T4R_ATTN_BWD_P_BOUNDS 512
+#endif
+#ifndef T4R_ATTN_BWD_KH_FOLLOWS_L
+#define T4R_ATTN_BWD_KH_FOLLOWS_L 1
+#endif
 #ifndef T4R_ATTN_FWD_BOUNDS
 #define T4R_ATTN_FWD_BOUNDS 512
 #endif
@@ -184,15 +194,50 @@ __global__ __launch_bounds__(T4R_ATTN_FWD_BOUNDS) void xlnet_attn_mfma_fwd_kerne
 // ------------------------------------------------------------------------------------------ backward
 // part: row blockIdx.x of [gridDim.x][2L*D + 2D]: d k_r (shared k_r only) | d r_w_bias | d r_r_bias,
 // this head's columns (same layout the VALU kernels use; reduced by t4r_reduce_partials_launch).
-template <int DH, bool SHARED_KR>
-__global__ __launch_bounds__(T4R_ATTN_BWD_BOUNDS) void xlnet_attn_mfma_bwd_kernel(
+//
+// HAVE_P: `prob` [B][n_head][L][L] holds the probabilities BEFORE dropout as the one-kernel forward left them
+// (xlnet_attn_block.hip; exact zeros at masked columns), so the scores are not recomputed: no q / k / k_r row
+// fragments, no score products, no lse, no key-length mask.  The dropout mask is regenerated either way.
+// KH: half-length of the contractions over sequence positions (2 KH >= L; the relative-position contraction of
+// d q runs 2 KH per lane half, 4 KH >= 2 L).  The row layout is "lane (i, kh) owns columns kh*KH .. kh*KH+KH-1".
+// The recomputing form keeps KH = 16 (its scores come in that layout).
+template <int KH>
+__device__ __forceinline__ void drop_scale_run(const DropCfg& d, unsigned long long row0, int j0, int L, bool aligned,
+                                               float (&m)[KH]) {
+    // masks of the KH elements row0 + j0 .. of which those with j < L are needed (the rest get 1).  aligned (wave
+    // uniform): row0 % 4 == 0 and L % 4 == 0, so one Philox block serves four columns; j0 = kh*KH is then 0 or KH
+    // past a block border, and the run starts (j0 & 3) elements into its first block
+    if (aligned) {
+        constexpr int NB = (KH + (KH & 3) + 3) / 4;
+        float f[4 * NB];
+        const int a0 = j0 & ~3;
+#pragma unroll
+        for (int blk = 0; blk < NB; ++blk) {
+            float4 x = make_float4(1.f, 1.f, 1.f, 1.f);
+            if (a0 + 4 * blk < L) x = drop_scale4(d, row0 + a0 + 4 * blk);
+            f[4 * blk] = x.x; f[4 * blk + 1] = x.y; f[4 * blk + 2] = x.z; f[4 * blk + 3] = x.w;
+        }
+        const bool shifted = (j0 & 3) != 0;
+#pragma unroll
+        for (int t = 0; t < KH; ++t) m[t] = (KH & 3) ? (shifted ? f[t + (KH & 3)] : f[t]) : f[t];
+    } else {
+#pragma unroll
+        for (int t = 0; t < KH; ++t) m[t] = j0 + t < L ? drop_scale(d, row0 + j0 + t) : 1.f;
+    }
+}
+
+template <int DH, bool SHARED_KR, bool HAVE_P, int KH>
+__global__ __launch_bounds__(HAVE_P ? T4R_ATTN_BWD_P_BOUNDS : T4R_ATTN_BWD_BOUNDS) void xlnet_attn_mfma_bwd_kernel(
     const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
     const float* __restrict__ kr, const float* __restrict__ r_w_bias, const float* __restrict__ r_r_bias,
-    const float* __restrict__ lse, const float* __restrict__ dout, float* __restrict__ dq,
+    const float* __restrict__ lse, const float* __restrict__ prob, const float* __restrict__ dout, float* __restrict__ dq,
     float* __restrict__ dk, float* __restrict__ dv, float* __restrict__ part, float* __restrict__ dkr_b, int B,
     int L, int n_head, float scale, long kr_bstride, DropCfg drop, const int* key_len) {
+    static_assert(HAVE_P || KH == 16, "the recomputed scores arrive 16 columns per lane");
+    static_assert(KH % 2 == 0 && KH >= 2 && KH <= 16, "row layout: an even number of columns per lane, two lanes per row of 32");
     __shared__ __attribute__((aligned(16))) float Sm[32 * XM_SP];
-    __shared__ __attribute__((aligned(16))) float Pm[32 * XM_SP];   // dropped probabilities, parked for d v
+    // dropped probabilities, parked for d v (HAVE_P: they stay in registers and go through Sm once d k has read it)
+    __shared__ __attribute__((aligned(16))) float Pm[HAVE_P ? 4 : 32 * XM_SP];
     __shared__ __attribute__((aligned(16))) float Rm[32 * XM_RP];
     const int lane = threadIdx.x;
     const int h = blockIdx.y, hc = h * DH, D = n_head * DH;
@@ -206,12 +251,6 @@ __global__ __launch_bounds__(T4R_ATTN_BWD_BOUNDS) void xlnet_attn_mfma_bwd_kerne
         int c = lane & 31, kh = lane >> 5;
         asm volatile("" : "+v"(c), "+v"(kh));
         const int dc = min(c, DH - 1);
-        Frag<DH / 2> rw, del;
-#pragma unroll
-        for (int t = 0; t < DH / 2; ++t) {
-            rw.v[t] = r_w_bias[hc + kh * (DH / 2) + t];
-            del.v[t] = r_r_bias[hc + kh * (DH / 2) + t] - rw.v[t];
-        }
         const float rw_c = r_w_bias[hc + dc], rr_c = r_r_bias[hc + dc];
         const long tok0 = (long)b * L;
         const float* qb = q + tok0 * D;
@@ -222,26 +261,58 @@ __global__ __launch_bounds__(T4R_ATTN_BWD_BOUNDS) void xlnet_attn_mfma_bwd_kerne
         const int ic = min(c, L - 1);
         const int roff = ic * D + hc + kh * (DH / 2);
         const bool row_ok = c < L;
-        const ScoreFrags<DH> sf = load_score_frags<DH>(qb, kb, krb, D, hc, L, c, kh);
+        Frag<KH> P;               // probabilities before dropout, row layout; 0 outside the L x L block
+        if constexpr (HAVE_P) {
+            // the lane's run of its row, straight from memory.  L even: the run starts on an even element of an even-length
+            // row and a pair of columns is inside the row or outside it as a whole -> 8-byte loads
+            const float* pb = prob + (long)(b * n_head + h) * L * L + ic * L;
+            if ((L & 1) == 0) {
+#pragma unroll
+                for (int t = 0; t < KH; t += 2) {
+                    const int j = kh * KH + t;
+                    const float2 x = *reinterpret_cast<const float2*>(pb + min(j, L - 2));
+                    P.v[t] = (row_ok && j < L) ? x.x : 0.f;
+                    P.v[t + 1] = (row_ok && j < L) ? x.y : 0.f;
+                }
+            } else {
+#pragma unroll
+                for (int t = 0; t < KH; ++t) {
+                    const int j = kh * KH + t;
+                    const float x = pb[min(j, L - 1)];
+                    P.v[t] = (row_ok && j < L) ? x : 0.f;
+                }
+            }
+        }
+        Frag<DH / 2> rw, del;     // recomputing form only
+        ScoreFrags<DH> sf;
+        if constexpr (!HAVE_P) {
+#pragma unroll
+            for (int t = 0; t < DH / 2; ++t) {
+                rw.v[t] = r_w_bias[hc + kh * (DH / 2) + t];
+                del.v[t] = r_r_bias[hc + kh * (DH / 2) + t] - rw.v[t];
+            }
+            sf = load_score_frags<DH>(qb, kb, krb, D, hc, L, c, kh);
+        }
         const Frag<DH / 2> dof = row_frag<DH>(gb, roff);                 // operands of dP = dO V^T, in flight early
         const Frag<DH / 2> vf = row_frag<DH>(vb, roff);                  // lane column j = c
-        const Frag<16> kcol = col_frag<16>(kb, hc + dc, D, L, kh, 0.f);  // for d q = dS K
+        const Frag<KH> kcol = col_frag<KH>(kb, hc + dc, D, L, kh, 0.f);  // for d q = dS K
         __builtin_amdgcn_sched_barrier(0);    // the loads are issued here; the waits sit at the uses
-        float s[16];
-        scores_row_layout<DH>(sf, L, rw, del, scale, Sm, Rm, c, kh, s);
-        const float lrow = lse[((long)b * n_head + h) * L + ic];
-        Frag<16> P;
-        const int klen = key_len ? key_len[b] : L;
+        if constexpr (!HAVE_P) {
+            float s[16];
+            scores_row_layout<DH>(sf, L, rw, del, scale, Sm, Rm, c, kh, s);
+            const float lrow = lse[((long)b * n_head + h) * L + ic];
+            const int klen = key_len ? key_len[b] : L;
 #pragma unroll
-        for (int t = 0; t < 16; ++t)
-            P.v[t] = (row_ok && kh * 16 + t < L && !(kh * 16 + t >= klen && kh * 16 + t != c)) ? __expf(s[t] - lrow) : 0.f;
+            for (int t = 0; t < KH; ++t)
+                P.v[t] = (row_ok && kh * 16 + t < L && !(kh * 16 + t >= klen && kh * 16 + t != c)) ? __expf(s[t] - lrow) : 0.f;
+        }
         ATTN_PHASE_FENCE();   // keeps later phases' operand loads out of this one
         // (operands of the NEXT phase are requested at the start of each phase: the fences keep them here)
-        Frag<16> krc[2];          // k_r column fragments for d q += d raw K_r : k = m = kh*32 + 16u + t
+        Frag<KH> krc[2];          // k_r column fragments for d q += d raw K_r : k = m = kh*2KH + KH u + t
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
-            for (int t = 0; t < 16; ++t) krc[u].v[t] = krb[min(kh * 32 + 16 * u + t, 2 * L - 1) * D + hc + dc];
+            for (int t = 0; t < KH; ++t) krc[u].v[t] = krb[min(kh * 2 * KH + KH * u + t, 2 * L - 1) * D + hc + dc];
         // dP = dO V^T (accumulator layout) -> row layout through Sm
         {
             f32x16 dp = zero16();
@@ -251,27 +322,28 @@ __global__ __launch_bounds__(T4R_ATTN_BWD_BOUNDS) void xlnet_attn_mfma_bwd_kerne
         }
         __builtin_amdgcn_s_waitcnt(0xc07f);
         __builtin_amdgcn_wave_barrier();
-        Frag<16> dS;
+        Frag<KH> dS, Pd;          // Pd: the dropped probabilities (HAVE_P: kept for d v)
         {
             const unsigned long long mbase = ((unsigned long long)(b * n_head + h) * L + ic) * L;
             float drow = 0.f;
-            float dpm[16], msk[16];
+            float dpm[KH], msk[KH];
             if (drop.p > 0.f) {
-                drop_scale_run16(drop, mbase + kh * 16, L - kh * 16, (L & 3) == 0, msk);
+                drop_scale_run<KH>(drop, mbase, kh * KH, L, (L & 3) == 0, msk);
             } else {
 #pragma unroll
-                for (int t = 0; t < 16; ++t) msk[t] = 1.f;
+                for (int t = 0; t < KH; ++t) msk[t] = 1.f;
             }
 #pragma unroll
-            for (int t = 0; t < 16; ++t) {
-                const int j = kh * 16 + t;
+            for (int t = 0; t < KH; ++t) {
+                const int j = kh * KH + t;
                 dpm[t] = Sm[c * XM_SP + j] * msk[t];
-                Pm[c * XM_SP + j] = P.v[t] * msk[t];
+                Pd.v[t] = P.v[t] * msk[t];
+                if constexpr (!HAVE_P) Pm[c * XM_SP + j] = Pd.v[t];
                 drow += P.v[t] * dpm[t];
             }
             drow += __shfl_xor(drow, 32, 64);
 #pragma unroll
-            for (int t = 0; t < 16; ++t) dS.v[t] = P.v[t] * (dpm[t] - drow) * scale;
+            for (int t = 0; t < KH; ++t) dS.v[t] = P.v[t] * (dpm[t] - drow) * scale;
         }
         __builtin_amdgcn_wave_barrier();
         ATTN_PHASE_FENCE();   // keeps later phases' operand loads out of this one
@@ -282,27 +354,27 @@ __global__ __launch_bounds__(T4R_ATTN_BWD_BOUNDS) void xlnet_attn_mfma_bwd_kerne
         __builtin_amdgcn_wave_barrier();
         if (row_ok) {
 #pragma unroll
-            for (int t = 0; t < 16; ++t) {
-                const int j = kh * 16 + t;
+            for (int t = 0; t < KH; ++t) {
+                const int j = kh * KH + t;
                 if (j < L) Rm[c * XM_RP + j + L - c] = dS.v[t];
             }
         }
-        // dS and Pd by rows into Sm / (after use) for the transposed reads
+        // dS by rows into Sm for the transposed reads (rows L .. 31 are zeros: P is)
 #pragma unroll
-        for (int t = 0; t < 16; ++t) Sm[c * XM_SP + kh * 16 + t] = dS.v[t];
+        for (int t = 0; t < KH; ++t) Sm[c * XM_SP + kh * KH + t] = dS.v[t];
         __builtin_amdgcn_s_waitcnt(0xc07f);
         __builtin_amdgcn_wave_barrier();
         ATTN_PHASE_FENCE();   // keeps later phases' operand loads out of this one
         // d q = dS K + d raw K_r
-        const Frag<16> qcol = col_frag<16>(qb, hc + dc, D, L, kh, 0.f);     // for d k, d k_r (next phases)
+        const Frag<KH> qcol = col_frag<KH>(qb, hc + dc, D, L, kh, 0.f);     // for d k, d k_r (next phases)
         f32x16 dqa = zero16(), dqb = zero16();
         {
             mfma_chain(dqa, dS, kcol);
 #pragma unroll
-            for (int u = 0; u < 2; ++u) {       // contraction over m (64): k = kh*32 + 16u + t
-                Frag<16> dr;
+            for (int u = 0; u < 2; ++u) {       // contraction over m (4 KH >= 2 L): k = kh*2KH + KH u + t
+                Frag<KH> dr;
 #pragma unroll
-                for (int t = 0; t < 16; ++t) dr.v[t] = Rm[c * XM_RP + kh * 32 + 16 * u + t];
+                for (int t = 0; t < KH; ++t) dr.v[t] = Rm[c * XM_RP + kh * 2 * KH + KH * u + t];
                 mfma_chain(dqb, dr, krc[u]);
             }
         }
@@ -319,14 +391,14 @@ __global__ __launch_bounds__(T4R_ATTN_BWD_BOUNDS) void xlnet_attn_mfma_bwd_kerne
         }
         ATTN_PHASE_FENCE();   // keeps later phases' operand loads out of this one
         // d k = dS^T (q + r_w_bias) : A = dS^T read by columns from Sm, B = column fragment of q
-        const Frag<16> gcol = col_frag<16>(gb, hc + dc, D, L, kh, 0.f);     // for d v (last phase)
+        const Frag<KH> gcol = col_frag<KH>(gb, hc + dc, D, L, kh, 0.f);     // for d v (last phase)
         {
-            Frag<16> at;
+            Frag<KH> at;
 #pragma unroll
-            for (int t = 0; t < 16; ++t) at.v[t] = Sm[(kh * 16 + t) * XM_SP + c];
-            Frag<16> qf;
+            for (int t = 0; t < KH; ++t) at.v[t] = Sm[(kh * KH + t) * XM_SP + c];
+            Frag<KH> qf;
 #pragma unroll
-            for (int t = 0; t < 16; ++t) qf.v[t] = qcol.v[t] + rw_c;
+            for (int t = 0; t < KH; ++t) qf.v[t] = qcol.v[t] + rw_c;
             f32x16 g = zero16();
             mfma_chain(g, at, qf);
             if (c < DH) {
@@ -340,14 +412,14 @@ __global__ __launch_bounds__(T4R_ATTN_BWD_BOUNDS) void xlnet_attn_mfma_bwd_kerne
         ATTN_PHASE_FENCE();   // keeps later phases' operand loads out of this one
         // d k_r = d raw^T (q + r_r_bias) : two 32-row tiles (m = c, c + 32)
         {
-            Frag<16> qf;
+            Frag<KH> qf;
 #pragma unroll
-            for (int t = 0; t < 16; ++t) qf.v[t] = qcol.v[t] + rr_c;
+            for (int t = 0; t < KH; ++t) qf.v[t] = qcol.v[t] + rr_c;
 #pragma unroll
             for (int half = 0; half < 2; ++half) {
-                Frag<16> at;
+                Frag<KH> at;
 #pragma unroll
-                for (int t = 0; t < 16; ++t) at.v[t] = Rm[(kh * 16 + t) * XM_RP + c + 32 * half];
+                for (int t = 0; t < KH; ++t) at.v[t] = Rm[(kh * KH + t) * XM_RP + c + 32 * half];
                 if (!SHARED_KR) {
                     f32x16 g = zero16();
                     mfma_chain(g, at, qf);
@@ -366,11 +438,18 @@ __global__ __launch_bounds__(T4R_ATTN_BWD_BOUNDS) void xlnet_attn_mfma_bwd_kerne
             }
         }
         ATTN_PHASE_FENCE();   // keeps later phases' operand loads out of this one
-        // d v = P~^T dO : P~ was parked by rows in Pm, read by columns
+        // d v = P~^T dO : P~ was parked by rows in Pm (HAVE_P: goes by rows into Sm now that d k has read dS), read by columns
         {
-            Frag<16> at;
+            if constexpr (HAVE_P) {
 #pragma unroll
-            for (int t = 0; t < 16; ++t) at.v[t] = Pm[(kh * 16 + t) * XM_SP + c];
+                for (int t = 0; t < KH; ++t) Sm[c * XM_SP + kh * KH + t] = Pd.v[t];
+                __builtin_amdgcn_s_waitcnt(0xc07f);
+                __builtin_amdgcn_wave_barrier();
+            }
+            const float* Pt = HAVE_P ? Sm : Pm;
+            Frag<KH> at;
+#pragma unroll
+            for (int t = 0; t < KH; ++t) at.v[t] = Pt[(kh * KH + t) * XM_SP + c];
             f32x16 g = zero16();
             mfma_chain(g, at, gcol);
             if (c < DH) {
@@ -422,10 +501,11 @@ int t4r_xlnet_attn_mfma_fwd(hipStream_t st, const float* q, const float* k, cons
     return 0;
 }
 
+// prob: the probabilities before dropout [B][n_head][L][L] as the one-kernel forward stored them, or null (recompute)
 int t4r_xlnet_attn_mfma_bwd(hipStream_t st, const float* q, const float* k, const float* v, const float* kr,
-                            const float* rw, const float* rr, const float* lse, const float* dout, float* dq,
-                            float* dk, float* dv, float* part, float* dkr, float* d_rw, float* d_rr, int B, int L,
-                            int n_head, int d_head, float scale, long kr_bstride, DropCfg drop, const int* key_len) {
+                            const float* rw, const float* rr, const float* lse, const float* prob, const float* dout,
+                            float* dq, float* dk, float* dv, float* part, float* dkr, float* d_rw, float* d_rr, int B,
+                            int L, int n_head, int d_head, float scale, long kr_bstride, DropCfg drop, const int* key_len) {
     const int D = n_head * d_head;
     // (one (session, head) unit per wave and 1024 x n_head waves: at four heads exactly one residency of 256 CUs.  Shrinking the
     //  grid to the CU budget was tried (round 5) and is worse: the unit is a whole session, so 1024 sessions on 960 workgroups
@@ -433,11 +513,21 @@ int t4r_xlnet_attn_mfma_bwd(hipStream_t st, const float* q, const float* k, cons
     const int gx = t4r_xlnet_attn_mfma_blocks(B);
     const dim3 grid(gx, n_head), block(64);
     float* dkr_b = kr_bstride > 0 ? dkr : nullptr;
-#define T4R_BWD(DHV, SH)                                                                                      \
-    hipLaunchKernelGGL((xlnet_attn_mfma_bwd_kernel<DHV, SH>), grid, block, 0, st, q, k, v, kr, rw, rr, lse, dout, dq, \
-                       dk, dv, part, dkr_b, B, L, n_head, scale, kr_bstride, drop, key_len)
-    if (d_head == 32) { if (dkr_b) T4R_BWD(32, false); else T4R_BWD(32, true); }
-    else { if (dkr_b) T4R_BWD(16, false); else T4R_BWD(16, true); }
+#define T4R_BWD(DHV, SH, HP, KHV)                                                                                      \
+    hipLaunchKernelGGL((xlnet_attn_mfma_bwd_kernel<DHV, SH, HP, KHV>), grid, block, 0, st, q, k, v, kr, rw, rr, lse, prob, \
+                       dout, dq, dk, dv, part, dkr_b, B, L, n_head, scale, kr_bstride, drop, key_len)
+#define T4R_BWD_SH(DHV, HP, KHV) do { if (dkr_b) T4R_BWD(DHV, false, HP, KHV); else T4R_BWD(DHV, true, HP, KHV); } while (0)
+#define T4R_BWD_DH(HP, KHV) do { if (d_head == 32) T4R_BWD_SH(32, HP, KHV); else T4R_BWD_SH(16, HP, KHV); } while (0)
+    if (!prob) T4R_BWD_DH(false, 16);
+#if !T4R_ATTN_BWD_KH_FOLLOWS_L      /* A/B builds only: every contraction padded to 32 as in the recomputing form */
+    else if (L <= 32) T4R_BWD_DH(true, 16);
+#endif
+    else if (L <= 16) T4R_BWD_DH(true, 8);       // contraction half-lengths follow L: 2 KH >= L
+    else if (L <= 20) T4R_BWD_DH(true, 10);
+    else if (L <= 24) T4R_BWD_DH(true, 12);
+    else T4R_BWD_DH(true, 16);
+#undef T4R_BWD_DH
+#undef T4R_BWD_SH
 #undef T4R_BWD
     T4R_LAUNCH_CHECK();
     return t4r_reduce_partials_launch(st, part, gx, kr_bstride > 0 ? nullptr : dkr, 2 * L * D, 0, d_rw, D, 1, d_rr,

@@ -54,6 +54,15 @@ int t4r_xlnet_ff_amax_count_bwd(long T);
 void t4r_gemm_operand_amax2(const float* a, int na, const float* b, int nb);   // gemm_f32.hip: the two producers ran different grids
 long t4r_xlnet_ff_amax_slots(long T);
 bool t4r_xlnet_body_fp16x2();
+// xlnet_attn.hip / xlnet_attn_block.hip: the public entries plus the `prob` pointer (the attention probabilities before dropout
+// [B][n_head][L][L]: the one-kernel forward stores them, the core's backward reads them instead of recomputing the scores)
+int t4r_xlnet_attn_bwd_impl(void*, const float*, const float*, const float*, const float*, const float*, const float*, const float*,
+                            const float*, const float*, const float*, float*, float*, float*, float*, float*, float*, float*, int,
+                            int, int, int, int, float, unsigned long long, unsigned long long, const int*);
+int t4r_xlnet_attn_block_fwd_impl(void*, const float*, const float*, const float*, const float*, long, const float*, const float*,
+                                  const float*, const float*, float*, float*, float*, float*, float*, float*, float*, float*, int,
+                                  int, int, int, float, float, unsigned long long, unsigned long long, unsigned long long,
+                                  const int*);
 void t4r_splitk_sink_begin(float* ws, long cap_floats);                          // gemm_f32.hip: deterministic split-K
 int t4r_splitk_sink_flush(hipStream_t st);
 void t4r_splitk_sink_end();
@@ -143,7 +152,7 @@ enum { P_Q = 0, P_K, P_V, P_O, P_R, P_RWB, P_RRB, P_LN1W, P_LN1B, P_W1, P_B1, P_
        P_LN2B, P_COUNT };
 
 struct LayerWs {
-    float *qkv, *kr, *av, *lse, *ao, *mean1, *rstd1, *h1, *ffpre, *ffact, *ffout, *mean2, *rstd2, *pe_b, *planes, *amax, *hin;
+    float *qkv, *kr, *av, *lse, *ao, *mean1, *rstd1, *h1, *ffpre, *ffact, *ffout, *mean2, *rstd2, *pe_b, *planes, *amax, *hin, *prob;
     long total;
 };
 
@@ -177,6 +186,9 @@ static LayerWs carve(float* base, int B, int L, int D, int n, int per_batch_kr) 
     // the dropped input rows of a FIRST layer that applies the model's input dropout itself (T4R_LAYER_FUSE_INPUT); last, so
     // that every other offset is what it was
     w.hin = (per_batch_kr && t4r_xlnet_fused_supported(D)) ? take(T * D) : nullptr;
+    // the attention probabilities before dropout [B][n][L][L] of a layer whose attention half runs as the one-kernel forward:
+    // the core's backward reads them instead of recomputing the scores (same size with and without dropout)
+    w.prob = (t4r_xlnet_fused_supported(D) && t4r_xlnet_attn_block_supported(L, D, n)) ? take((long)B * n * L * L) : nullptr;
     w.total = o;
     return w;
 }
@@ -265,10 +277,10 @@ extern "C" int t4r_xlnet_layer_fwd(void* stream, const float* h, const float* po
         if (block) {
             // q | k | v projection, attention core, o-projection + dropout + residual + LayerNorm: ONE launch
             t4r_xlnet_attn_block_input_dropout(fuse_in, ctr_hi(offset, 255, SITE_INPUT), w.hin);
-            const int rc_ab = t4r_xlnet_attn_block_fwd(stream, h, w.planes, params[P_O], w.kr, drop ? 2L * L * D : 0L, params[P_RWB],
-                                                       params[P_RRB], params[P_LN1W], params[P_LN1B], w.qkv, w.av, w.lse, w.ao, w.mean1,
-                                                       w.rstd1, w.h1, B, L, D, n_head, ln_eps, drop_p, seed, C(SITE_PROB),
-                                                       C(SITE_ATTN_OUT), key_len);
+            const int rc_ab = t4r_xlnet_attn_block_fwd_impl(stream, h, w.planes, params[P_O], w.kr, drop ? 2L * L * D : 0L, params[P_RWB],
+                                                            params[P_RRB], params[P_LN1W], params[P_LN1B], w.qkv, w.av, w.lse, w.prob,
+                                                            w.ao, w.mean1, w.rstd1, w.h1, B, L, D, n_head, ln_eps, drop_p, seed,
+                                                            C(SITE_PROB), C(SITE_ATTN_OUT), key_len);
             t4r_xlnet_attn_block_input_dropout(0, 0, nullptr);
             if (rc_ab) return rc_ab;
         } else {
@@ -565,10 +577,11 @@ extern "C" int t4r_xlnet_layer_bwd(void* stream, const float* h, const float* po
         // LayerNorm-1 backward + d attn_vec in one launch; the attention core; d h from d q, d k, d v in one launch
         RUN(t4r_xlnet_ln1_bwd(stream, dx, w.ao, h, w.mean1, w.rstd1, params[P_LN1W], w.planes, dh_in, dao_buf, dav,
                               grads[P_LN1W], grads[P_LN1B], ln1_part, T, D, drop_p, seed, C(SITE_ATTN_OUT)));
-        RUN(t4r_xlnet_attn_bwd(stream, w.qkv, w.qkv + TD, w.qkv + 2 * TD, w.kr, params[P_RWB],
-                               params[P_RRB], w.av, w.lse, dav, dqkv, dqkv + TD, dqkv + 2 * TD, dkr,
-                               grads[P_RWB], grads[P_RRB], attn_ws, B, L, n_head, dh, drop, drop_p, seed,
-                               C(SITE_PROB), key_len));
+        // (the one-kernel forward left the probabilities in the workspace: the core reads them instead of recomputing the scores)
+        RUN(t4r_xlnet_attn_bwd_impl(stream, w.qkv, w.qkv + TD, w.qkv + 2 * TD, w.kr, params[P_RWB],
+                                    params[P_RRB], w.av, w.lse, use_attn_block(L, D, n_head) ? w.prob : nullptr, dav, dqkv,
+                                    dqkv + TD, dqkv + 2 * TD, dkr, grads[P_RWB], grads[P_RRB], attn_ws, B, L, n_head, dh, drop,
+                                    drop_p, seed, C(SITE_PROB), key_len));
         }
         // ONE event for the o, r and q|k|v products (their operands are all complete here; with the join deferred nothing
         // is gained by starting the o product before the attention core)

@@ -704,6 +704,22 @@ def xlnet_attn_bwd(q, k, v, k_r, r_w_bias, r_r_bias, out, lse, dout, d_rw, d_rr,
     return dq, dk, dv, dkr
 
 
+def xlnet_attn_bwd_prob(q, k, v, k_r, r_w_bias, r_r_bias, prob, dout, d_rw, d_rr, B, L, n_head, drop=NO_DROP):
+    """xlnet_attn_bwd reading the probabilities before dropout [B, n_head, L, L] that xlnet_attn_block_fwd(prob=...) left
+    (include/t4r_hip_attn.h; L <= 32, d_head 16 / 32)"""
+    D = q.shape[-1]
+    dev = q.device
+    per_b = int(k_r.shape[0] == B * 2 * L and B > 1)
+    dq, dk, dv = torch.empty((3, B * L, D), device=dev, dtype=torch.float32).unbind(0)
+    dkr = torch.empty_like(k_r)
+    nws = _lib.load().t4r_xlnet_attn_bwd_ws_floats(B, L, D, n_head)
+    ws = torch.empty(nws, device=dev, dtype=torch.float32)
+    call("t4r_xlnet_attn_bwd_prob", _stream(), _chk(q), _chk(k), _chk(v), _chk(k_r), _chk(r_w_bias), _chk(r_r_bias),
+         _chk(prob), _chk(dout), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), dkr.data_ptr(), _chk(d_rw), _chk(d_rr),
+         ws.data_ptr(), B, L, n_head, D // n_head, per_b, float(drop[0]), int(drop[1]), int(drop[2]))
+    return dq, dk, dv, dkr
+
+
 def mha_fwd(q, k, v, B, L, n_head, causal, drop=NO_DROP, key_len=None):
     """q,k,v: [B*L, D] views that may be column slices of one [B*L, 3D] buffer (row stride = ld)."""
     D = q.shape[1]
@@ -935,8 +951,10 @@ def xlnet_attn_block_supported(L, D, n_head):
 
 
 def xlnet_attn_block_fwd(h, planes, o, kr, r_w_bias, r_r_bias, gamma, beta, B, L, n_head, eps, drop_p=0.0, seed=0, ctr_prob=0,
-                         ctr_out=0, key_len=None, train=True):
-    """the attention half of a layer in one launch (csrc/xlnet_attn_block.hip): h [B L, D] -> h1, and what the backward needs"""
+                         ctr_out=0, key_len=None, train=True, prob=None):
+    """the attention half of a layer in one launch (csrc/xlnet_attn_block.hip): h [B L, D] -> h1, and what the backward needs.
+    prob: a contiguous fp32 buffer of B n_head L L elements (16-byte aligned) that receives the probabilities before dropout
+    (include/t4r_hip_attn.h)"""
     T, D = h.shape
     dev = h.device
     qkv = torch.empty((3, T, D), device=dev)
@@ -946,10 +964,15 @@ def xlnet_attn_block_fwd(h, planes, o, kr, r_w_bias, r_r_bias, gamma, beta, B, L
     mean = torch.empty(T, device=dev) if train else None
     rstd = torch.empty(T, device=dev) if train else None
     per_session = kr.shape[0] == B * 2 * L and B > 1
-    call("t4r_xlnet_attn_block_fwd", _stream(), _chk(h, torch.float32), planes.data_ptr(), _chk(o, torch.float32), _chk(kr, torch.float32),
-         2 * L * D if per_session else 0, _chk(r_w_bias), _chk(r_r_bias), _chk(gamma), _chk(beta), qkv.data_ptr(), av.data_ptr(),
-         lse.data_ptr(), _p(ao), _p(mean), _p(rstd), h1.data_ptr(), B, L, D, n_head, float(eps), float(drop_p), int(seed),
-         int(ctr_prob), int(ctr_out), _p(key_len, torch.int32))
+    head = (_stream(), _chk(h, torch.float32), planes.data_ptr(), _chk(o, torch.float32), _chk(kr, torch.float32),
+            2 * L * D if per_session else 0, _chk(r_w_bias), _chk(r_r_bias), _chk(gamma), _chk(beta), qkv.data_ptr(), av.data_ptr(),
+            lse.data_ptr())
+    tail = (_p(ao), _p(mean), _p(rstd), h1.data_ptr(), B, L, D, n_head, float(eps), float(drop_p), int(seed),
+            int(ctr_prob), int(ctr_out), _p(key_len, torch.int32))
+    if prob is None:
+        call("t4r_xlnet_attn_block_fwd", *head, *tail)
+    else:
+        call("t4r_xlnet_attn_block_fwd_prob", *head, _chk(prob, torch.float32), *tail)
     return h1, dict(qkv=qkv, av=av, lse=lse, ao=ao, mean=mean, rstd=rstd)
 
 
