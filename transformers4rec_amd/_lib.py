@@ -16,6 +16,7 @@ FILTER_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_fi
 OPTIM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_optim.h")
 PRETRAINED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_pretrained.h")
 ATTN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_attn.h")
+ROWS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_rows.h")
 
 _P, _I, _L, _F, _Q = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_ulonglong
 _C = {"p": _P, "i": _I, "l": _L, "f": _F, "Q": _Q}
@@ -202,6 +203,16 @@ _SIGS_ATTN = {
     "t4r_xlnet_attn_bwd_prob": ("i", "p" * 16 + "iiii" + "ifQQ"),
 }
 
+# the seventh header, include/t4r_hip_rows.h (tests/test_last_rows_cpu.py checks this table against it): the row-mapped forms
+# of the layer's row-wise kernels; the tail of each is the map (rows, n)
+_SIGS_ROWS = {
+    "t4r_xlnet_ff_fwd_rows": ("i", _SIGS["t4r_xlnet_ff_fwd"][1] + "pi"),
+    "t4r_xlnet_ff_bwd_rows": ("i", _SIGS["t4r_xlnet_ff_bwd"][1] + "pip"),
+    "t4r_xlnet_ln1_bwd_rows": ("i", "p" + "ppppppp" + "ppp" + "ppp" + "lif" + "QQ" + "pi"),
+    "t4r_xlnet_layer_fwd_rows": ("i", _SIGS["t4r_xlnet_layer_fwd"][1] + "pi"),
+    "t4r_xlnet_layer_bwd_rows": ("i", _SIGS["t4r_xlnet_layer_bwd"][1] + "pi"),
+}
+
 _lib = None
 
 
@@ -245,6 +256,11 @@ def attn_header_symbols():
     return _declared(ATTN_HEADER_PATH)
 
 
+def rows_header_symbols():
+    """Function names declared in include/t4r_hip_rows.h."""
+    return _declared(ROWS_HEADER_PATH)
+
+
 def load():
     """Loads the library and sets ctypes prototypes.  Raises if it is not built."""
     global _lib
@@ -256,7 +272,7 @@ def load():
             "(run `python -m transformers4rec_amd.build`). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (ret, args) in (list(_SIGS.items()) + list(_SIGS_SAMPLING.items()) + list(_SIGS_FILTER.items()) + list(_SIGS_OPTIM.items())
-                              + list(_SIGS_PRETRAINED.items()) + list(_SIGS_ATTN.items())):
+                              + list(_SIGS_PRETRAINED.items()) + list(_SIGS_ATTN.items()) + list(_SIGS_ROWS.items())):
         fn = getattr(lib, name)
         fn.restype = ctypes.c_char_p if ret == "s" else (None if ret == "v" else _C[ret])
         fn.argtypes = [_C[a] for a in args]

@@ -34,6 +34,7 @@
 // activation-chunk planes [3][16R][D + 16] (written by the
 // FF1 epilogue, B operand of FF2; d_inner = 4 D is walked in four chunks of D, two barriers per chunk).
 #include "xlnet_fused.h"
+#include <type_traits>
 
 struct FFFwdParams {
     const float *h1, *b1, *b2, *gamma, *beta;
@@ -46,6 +47,13 @@ struct FFFwdParams {
     DropCfg drop_act, drop_out;
     DropCfg drop_final;    // p > 0: the MODEL's output dropout (HF modeling_xlnet.py:1177) applied to hout in this launch (last layer)
 };
+// The row-mapped form (include/t4r_hip_rows.h): T counts the COMPACT rows, the tile works on compact rows [blockIdx.x 16 R, ...)
+// and everything that identifies a token -- the h1 loads, the hout / mean / rstd stores, every Philox counter -- uses
+// rows[compact]; ffpre / ffact / ffout and the operand maxima are in compact order.  Its own kernel (and parameter struct): the
+// plain form is compiled as it always was.
+struct FFFwdRowsParams : FFFwdParams {
+    const int* rows;       // [T] ascending, unique token rows
+};
 
 // FULL: every row of the tile is a token; TRAIN: the backward's activations are saved and the Philox masks evaluated
 // (p = 0 keeps everything); !TRAIN (inference: nothing saved, p = 0): neither.
@@ -54,8 +62,8 @@ struct FFFwdParams {
 // (|gelu(x)| <= |x|, |pre[t][f]| <= D max|W1| max|h1[t]| + max|b1|, the dropout factor on top): one scale for all four
 // chunks of a token, as their products share an accumulator.  The bound is loose by one to two orders of magnitude, which
 // costs nothing: fp16 keeps its 11 + 11 bits over 2^17 of range below the bound.
-template <int D, int R, bool FULL, bool TRAIN, bool HS>
-__device__ __forceinline__ void ff_fwd_body(const FFFwdParams& p, uint16_t* smem) {
+template <int D, int R, bool FULL, bool TRAIN, bool HS, bool MAP = false, class Params = FFFwdParams>
+__device__ __forceinline__ void ff_fwd_body(const Params& p, uint16_t* smem) {
     constexpr int NW = D / 16, NT = NW * 64, RT = 16 * R, PH = D + 16, PLN = RT * PH, DI = 4 * D;
     uint16_t* sh_h = smem;                                   // [3][RT][PH] token planes
     uint16_t* sh_a = sh_h + 3 * PLN;                         // [3][RT][PH] activation-chunk planes
@@ -64,6 +72,8 @@ __device__ __forceinline__ void ff_fwd_body(const FFFwdParams& p, uint16_t* smem
     float* sh_sa = reinterpret_cast<float*>(sh_a + 2 * PLN);       // HS: [RT] activation scales | [RT] their inverses
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, n = lane & 15, g = lane >> 4;
     const long t0 = (long)blockIdx.x * RT;
+    // the token of a (clamped) compact row
+    auto tok = [&](long c) -> long { if constexpr (MAP) return (long)p.rows[c]; else return c; };
     float h1max_keep = 0.f;
     if constexpr (HS) {
         const float w1max = 16384.f / p.wh.scale[HS_W1];    // >= max |W1| (the scale puts it into [2^13, 2^14))
@@ -74,7 +84,7 @@ __device__ __forceinline__ void ff_fwd_body(const FFFwdParams& p, uint16_t* smem
         for (int i = tid; i < ((RT * G + NT - 1) / NT) * NT; i += NT) {
             const bool live = i < RT * G;
             const int row = live ? i / G : RT - 1, c4 = live ? (i % G) * 4 : 0;
-            const long t = FULL ? t0 + row : min(t0 + row, (long)p.T - 1);
+            const long t = tok(FULL ? t0 + row : min(t0 + row, (long)p.T - 1));
             const float4 v = ld4(p.h1 + t * D + c4);
             float m = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
 #pragma unroll
@@ -100,7 +110,7 @@ __device__ __forceinline__ void ff_fwd_body(const FFFwdParams& p, uint16_t* smem
     } else
     for (int i = tid; i < RT * (D / 4); i += NT) {
         const int row = i / (D / 4), c4 = (i % (D / 4)) * 4;
-        const long t = FULL ? t0 + row : min(t0 + row, (long)p.T - 1);
+        const long t = tok(FULL ? t0 + row : min(t0 + row, (long)p.T - 1));
         const float4 v = ld4(p.h1 + t * D + c4);
         uint32_t w0[3], w1[3];
         cut3(v.x, v.y, w0);
@@ -121,6 +131,11 @@ __device__ __forceinline__ void ff_fwd_body(const FFFwdParams& p, uint16_t* smem
     AFragH<D> h1f, h2f;
     float actmax = 0.f;            // HS, training: running max |act| of this lane (operand maximum for the W2 weight gradient)
     float is1[R], is2[R];          // HS: what turns an accumulator of FF1 / FF2 back into values, per token block
+    long tk[R];                    // MAP: the tokens of this lane's R compact rows (rows past the end: the last one's, never stored)
+    if constexpr (MAP) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) tk[r] = tok(min(t0 + r * 16 + n, (long)p.T - 1));
+    }
     if constexpr (HS) {
         const float iw1 = 1.f / p.wh.scale[HS_W1], iw2 = 1.f / p.wh.scale[HS_W2];
 #pragma unroll
@@ -161,7 +176,7 @@ __device__ __forceinline__ void ff_fwd_body(const FFFwdParams& p, uint16_t* smem
             if (TRAIN && in) st4(p.ffpre + t * DI + d0, v);
             v = make_float4(gelu_erf(v.x), gelu_erf(v.y), gelu_erf(v.z), gelu_erf(v.w));
             if (TRAIN) {
-                const float4 m = drop_scale4(p.drop_act, (unsigned long long)t * DI + d0);
+                const float4 m = drop_scale4(p.drop_act, (unsigned long long)(MAP ? tk[r] : t) * DI + d0);
                 v.x *= m.x; v.y *= m.y; v.z *= m.z; v.w *= m.w;
             }
             if (TRAIN && in) st4(p.ffact + t * DI + d0, v);
@@ -206,11 +221,11 @@ __device__ __forceinline__ void ff_fwd_body(const FFFwdParams& p, uint16_t* smem
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const long t = t0 + r * 16 + n;
-        const long tc = FULL ? t : min(t, (long)p.T - 1);
+        const long tc = MAP ? tk[r] : (FULL ? t : min(t, (long)p.T - 1));       // the token (clamped)
         float4 v = make_float4(acc2[r][0] + bias2.x, acc2[r][1] + bias2.y, acc2[r][2] + bias2.z, acc2[r][3] + bias2.w);
         if (TRAIN && (FULL || t < p.T)) st4(p.ffout + t * D + f0, v);
         if (TRAIN) {
-            const float4 m = drop_scale4(p.drop_out, (unsigned long long)t * D + f0);
+            const float4 m = drop_scale4(p.drop_out, (unsigned long long)(MAP ? tc : t) * D + f0);
             v.x *= m.x; v.y *= m.y; v.z *= m.z; v.w *= m.w;
         }
         const float4 hres = ld4(p.h1 + tc * D + f0);          // the residual in fp32 (L2 hit: this tile was just read)
@@ -256,11 +271,12 @@ __device__ __forceinline__ void ff_fwd_body(const FFFwdParams& p, uint16_t* smem
             float4 o = make_float4((x[r].x - mu[r]) * rs * gam.x + bet.x, (x[r].y - mu[r]) * rs * gam.y + bet.y,
                                    (x[r].z - mu[r]) * rs * gam.z + bet.z, (x[r].w - mu[r]) * rs * gam.w + bet.w);
             if (TRAIN && p.drop_final.p > 0.f) {      // workgroup-uniform: the last layer of a stack in training mode
-                const float4 mf = drop_scale4(p.drop_final, (unsigned long long)t * D + f0);
+                const float4 mf = drop_scale4(p.drop_final, (unsigned long long)(MAP ? tk[r] : t) * D + f0);
                 o.x *= mf.x; o.y *= mf.y; o.z *= mf.z; o.w *= mf.w;
             }
-            st4(p.hout + t * D + f0, o);
-            if (TRAIN && w == 0 && g == 0) { p.mean[t] = mu[r]; p.rstd[t] = rs; }
+            const long ts = MAP ? tk[r] : t;
+            st4(p.hout + ts * D + f0, o);
+            if (TRAIN && w == 0 && g == 0) { p.mean[ts] = mu[r]; p.rstd[ts] = rs; }
         }
     }
     if constexpr (HS && TRAIN) {
@@ -285,6 +301,20 @@ __global__ __launch_bounds__(D * 4) void xlnet_ff_fwd_kernel(FFFwdParams p) {
     }
 }
 
+// the row-mapped form (HS only: the product library's arithmetic)
+template <int D, int R>
+__global__ __launch_bounds__(D * 4) void xlnet_ff_fwd_rows_kernel(FFFwdRowsParams p) {
+    extern __shared__ uint16_t smem16[];
+    const bool full = (long)(blockIdx.x + 1) * 16 * R <= p.T;
+    if (p.ffpre != nullptr) {
+        if (full) ff_fwd_body<D, R, true, true, true, true>(p, smem16);
+        else ff_fwd_body<D, R, false, true, true, true>(p, smem16);
+    } else {
+        if (full) ff_fwd_body<D, R, true, false, true, true>(p, smem16);
+        else ff_fwd_body<D, R, false, false, true, true>(p, smem16);
+    }
+}
+
 // -------------------------------------------------------------------------------------------------- backward
 struct FFBwdParams {
     const float *dy, *ffout, *h1, *mean, *rstd, *gamma, *ffpre;
@@ -297,12 +327,22 @@ struct FFBwdParams {
     DropCfg drop_act, drop_out;
     DropCfg drop_final;    // p > 0: dy is the gradient of the DROPPED output (model-level site): masked on load
 };
+// The row-mapped form (include/t4r_hip_rows.h): T counts the COMPACT rows; dy, h1, mean, rstd are read at rows[compact] and the
+// Philox counters are the token's; ffout, ffpre (read) and dh1, dffout, dpre, the partial sums and the operand maxima (written)
+// are in compact order.  h1c [T, D]: the mapped rows of h1 in compact order (this kernel holds them in registers anyway): the
+// operand of the W1 weight gradient, which then contracts over the compact rows.
+struct FFBwdRowsParams : FFBwdParams {
+    const int* rows;
+    float* h1c;
+};
 
 // HS: both products on the two-way fp16 split.  The d ffout rows carry their own power-of-two scale (gradient rows of one
 // tile differ by orders of magnitude); the d pre rows are positioned by a per-token bound known before the first chunk:
 // |gelu'| <= 1.13, the dropout factor, |d act[t][f]| <= D max|W2| max|d ffout[t]|.
-template <int D, int R, bool HS = false>
-__global__ __launch_bounds__(D * 4) void xlnet_ff_bwd_kernel(FFBwdParams p) {
+// Params = FFBwdRowsParams: the row-mapped form, its own instantiations (the plain ones compile to what they always were)
+template <int D, int R, bool HS = false, class Params = FFBwdParams>
+__global__ __launch_bounds__(D * 4) void xlnet_ff_bwd_kernel(Params p) {
+    constexpr bool MAP = std::is_same<Params, FFBwdRowsParams>::value;
     constexpr int NW = D / 16, RT = 16 * R, PH = D + 16, PLN = RT * PH, DI = 4 * D;
     extern __shared__ uint16_t smem16[];
     uint16_t* sh_dfo = smem16;                                  // [3][RT][PH]  d ffout planes (B operand of the FF2 dX product)
@@ -312,6 +352,7 @@ __global__ __launch_bounds__(D * 4) void xlnet_ff_bwd_kernel(FFBwdParams p) {
     float* sh_sp = reinterpret_cast<float*>(sh_dp + 2 * PLN);      // HS: [RT] d pre scales | [RT] their inverses
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, n = lane & 15, g = lane >> 4;
     const long t0 = (long)blockIdx.x * RT;
+    auto tok = [&](long c) -> long { if constexpr (MAP) return (long)p.rows[c]; else return c; };     // token of a clamped compact row
     float dfomax_keep = 0.f;
     // ---- phase A: LayerNorm backward, lane = two consecutive features of a token row; a wave owns RT / NW rows and walks
     // them RB at a time with every load of the batch in flight before the first reduction (round 5: one row at a time was a
@@ -327,14 +368,17 @@ __global__ __launch_bounds__(D * 4) void xlnet_ff_bwd_kernel(FFBwdParams p) {
         for (int row0 = w; row0 < RT; row0 += NW * RB) {
             float2 fo[RB], hh[RB], dd[RB];
             float mu_[RB], rs_[RB];
+            long tk_[RB];       // MAP: the rows' tokens
 #pragma unroll
             for (int b = 0; b < RB; ++b) {          // unconditional loads from clamped addresses
                 const long tc = min(t0 + min(row0 + b * NW, RT - 1), (long)p.T - 1);
-                mu_[b] = p.mean[tc]; rs_[b] = p.rstd[tc];
+                const long tt = tok(tc);
+                if constexpr (MAP) tk_[b] = tt;
+                mu_[b] = p.mean[tt]; rs_[b] = p.rstd[tt];
                 const int cc = act_lane ? c0 : 0;
                 fo[b] = *reinterpret_cast<const float2*>(p.ffout + tc * D + cc);
-                hh[b] = *reinterpret_cast<const float2*>(p.h1 + tc * D + cc);
-                dd[b] = *reinterpret_cast<const float2*>(p.dy + tc * D + cc);
+                hh[b] = *reinterpret_cast<const float2*>(p.h1 + tt * D + cc);
+                dd[b] = *reinterpret_cast<const float2*>(p.dy + tt * D + cc);
             }
 #pragma unroll
             for (int b = 0; b < RB; ++b) {
@@ -346,14 +390,15 @@ __global__ __launch_bounds__(D * 4) void xlnet_ff_bwd_kernel(FFBwdParams p) {
                 const float mu = mu_[b], rs = rs_[b];
                 float xh[2] = {0.f, 0.f}, gg[2] = {0.f, 0.f}, dyv[2] = {0.f, 0.f}, m[2] = {1.f, 1.f};
                 float s1 = 0.f, s2 = 0.f;
+                const long tq = MAP ? tk_[b] : t;      // the token: what the Philox counters are made of
                 if (act_lane) {
-                    drop_scale_vec<2>(p.drop_out, (unsigned long long)t * D + c0, true, m);
+                    drop_scale_vec<2>(p.drop_out, (unsigned long long)tq * D + c0, true, m);
                     const float2 fo_ = fo[b], hh_ = hh[b], dd_ = dd[b];
                     const float xv[2] = {fo_.x * m[0] + hh_.x, fo_.y * m[1] + hh_.y};
                     dyv[0] = dd_.x; dyv[1] = dd_.y;
                     if (p.drop_final.p > 0.f) {       // workgroup-uniform
                         float mf[2];
-                        drop_scale_vec<2>(p.drop_final, (unsigned long long)t * D + c0, true, mf);
+                        drop_scale_vec<2>(p.drop_final, (unsigned long long)tq * D + c0, true, mf);
                         dyv[0] *= mf[0]; dyv[1] *= mf[1];
                     }
 #pragma unroll
@@ -378,6 +423,7 @@ __global__ __launch_bounds__(D * 4) void xlnet_ff_bwd_kernel(FFBwdParams p) {
                     // residual part of d h1 (the FF1 dX product is added at the end) and the rows of the FF2 weight gradient
                     *reinterpret_cast<float2*>(p.dh1 + t * D + c0) = make_float2(dx[0], dx[1]);
                     *reinterpret_cast<float2*>(p.dffout + t * D + c0) = make_float2(dxa[0], dxa[1]);
+                    if constexpr (MAP) *reinterpret_cast<float2*>(p.h1c + t * D + c0) = hh[b];
                 }
             }
             if constexpr (HS) {      // wave-uniform: the whole row lives in this wave
@@ -436,6 +482,11 @@ __global__ __launch_bounds__(D * 4) void xlnet_ff_bwd_kernel(FFBwdParams p) {
     AFragH<D> h2f, h3f;
     float is2[R], is3[R], sps[R];      // HS: accumulator -> value factors of the two products, the d pre scales
     float dpremax = 0.f;               // HS: running max |d pre| of this lane (operand maximum for the W1 weight gradient)
+    long tk[R];                        // MAP: the tokens of this lane's R compact rows (rows past the end: the last one's, never stored)
+    if constexpr (MAP) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) tk[r] = tok(min(t0 + r * 16 + n, (long)p.T - 1));
+    }
     if constexpr (HS) {
         const float iw2 = 1.f / p.wh.scale[HS_W2], iw1 = 1.f / p.wh.scale[HS_W1];
 #pragma unroll
@@ -479,7 +530,7 @@ __global__ __launch_bounds__(D * 4) void xlnet_ff_bwd_kernel(FFBwdParams p) {
             const long t = t0 + r * 16 + n;
             float4 v = make_float4(acc[r][0] * gelu_erf_grad(pre[r].x), acc[r][1] * gelu_erf_grad(pre[r].y),
                                    acc[r][2] * gelu_erf_grad(pre[r].z), acc[r][3] * gelu_erf_grad(pre[r].w));
-            const float4 m = drop_scale4(p.drop_act, (unsigned long long)t * DI + d0);
+            const float4 m = drop_scale4(p.drop_act, (unsigned long long)(MAP ? tk[r] : t) * DI + d0);
             v.x *= m.x; v.y *= m.y; v.z *= m.z; v.w *= m.w;
             if (t < p.T) st4(p.dpre + t * DI + d0, v);           // rows beyond T are exact zeros (d ffout rows are)
             if constexpr (HS) {
@@ -643,6 +694,30 @@ static int ff_bwd_launch(hipStream_t st, const FFBwdParams& p) {
     return 0;
 }
 
+// the row-mapped launches (p.T = the number of mapped rows)
+template <int D, int R>
+static int ff_fwd_rows_launch(hipStream_t st, const FFFwdRowsParams& p) {
+    constexpr int RT = 16 * R, PH = D + 16, NW = D / 16;
+    const size_t smem = (size_t)(6 * RT * PH) * 2 + (size_t)(2 * NW * RT) * sizeof(float);
+    const dim3 grid((unsigned)((p.T + RT - 1) / RT));
+    static T4rLdsAttr attr;
+    t4r_ensure_dynamic_lds((const void*)xlnet_ff_fwd_rows_kernel<D, R>, smem, attr);
+    hipLaunchKernelGGL((xlnet_ff_fwd_rows_kernel<D, R>), grid, dim3(D * 4), smem, st, p);
+    T4R_LAUNCH_CHECK();
+    return 0;
+}
+template <int D, int R>
+static int ff_bwd_rows_launch(hipStream_t st, const FFBwdRowsParams& p) {
+    constexpr int RT = 16 * R, PH = D + 16, NW = D / 16;
+    const size_t smem = (size_t)(6 * RT * PH) * 2 + (size_t)(NW * 3 * D) * sizeof(float);
+    const dim3 grid((unsigned)((p.T + RT - 1) / RT));
+    static T4rLdsAttr attr;
+    t4r_ensure_dynamic_lds((const void*)xlnet_ff_bwd_kernel<D, R, true, FFBwdRowsParams>, smem, attr);
+    hipLaunchKernelGGL((xlnet_ff_bwd_kernel<D, R, true, FFBwdRowsParams>), grid, dim3(D * 4), smem, st, p);
+    T4R_LAUNCH_CHECK();
+    return 0;
+}
+
 #define FUSED_DISPATCH(FN, D, R, ...)                                                           \
     do {                                                                                        \
         switch ((D) * 8 + (R)) {                                                                \
@@ -658,10 +733,11 @@ static int ff_bwd_launch(hipStream_t st, const FFBwdParams& p) {
 // Fused feed-forward block, forward.  h1 [T, D] -> hout [T, D]; saves ffpre / ffact [T, 4D], ffout [T, D], mean / rstd [T]
 // for the backward when the pointers are given (all or none).  planes: the buffer t4r_xlnet_ff_prepare filled.
 // replaces: HF modeling_xlnet.py:297-305 (layer_1, activation, dropout, layer_2, dropout, layer_norm(output + inp))
-extern "C" int t4r_xlnet_ff_fwd(void* stream, const float* h1, const float* planes, const float* b1, const float* b2,
-                                const float* gamma, const float* beta, float* ffpre, float* ffact, float* ffout, float* mean,
-                                float* rstd, float* hout, int T, int D, float eps, float drop_p, unsigned long long seed,
-                                unsigned long long ctr_act, unsigned long long ctr_out) {
+// rows != null: the row-mapped form on n rows (include/t4r_hip_rows.h)
+static int ff_fwd_impl(void* stream, const float* h1, const float* planes, const float* b1, const float* b2,
+                       const float* gamma, const float* beta, float* ffpre, float* ffact, float* ffout, float* mean,
+                       float* rstd, float* hout, int T, int D, float eps, float drop_p, unsigned long long seed,
+                       unsigned long long ctr_act, unsigned long long ctr_out, const int* rows, int n) {
     if (T <= 0) return 0;
     T4R_CHECK_ARG(t4r_xlnet_fused_supported(D), "xlnet_ff_fwd: d_model must be 32, 64 or 128");
     T4R_CHECK_ARG(h1 && planes && b1 && b2 && gamma && beta && hout, "xlnet_ff_fwd: null pointer");
@@ -673,27 +749,64 @@ extern "C" int t4r_xlnet_ff_fwd(void* stream, const float* h1, const float* plan
                   mean, rstd, hout, T, eps,
                   make_drop(drop_p, seed, ctr_act), make_drop(drop_p, seed, ctr_out),
                   make_drop(g_ff_final_on ? drop_p : 0.f, seed, g_ff_final_ctr)};
+    if (rows) {
+        T4R_CHECK_ARG(n >= 1 && n <= T, "xlnet_ff_fwd_rows: the number of mapped rows must be in [1, T]");
+        T4R_CHECK_ARG(t4r_xlnet_body_fp16x2(), "xlnet_ff_fwd_rows: the row-mapped kernels exist in the two-way fp16 form only");
+        FFFwdRowsParams pr;
+        static_cast<FFFwdParams&>(pr) = p;
+        pr.T = n;
+        pr.rows = rows;
+        const int Rn = pick_r(n);
+        FUSED_DISPATCH(ff_fwd_rows_launch, D, Rn, (hipStream_t)stream, pr);
+        t4r_set_error("xlnet_ff_fwd_rows: no instantiation");
+        return -1;
+    }
     const int R = pick_r(T);
     FUSED_DISPATCH(ff_fwd_launch, D, R, (hipStream_t)stream, p);
     t4r_set_error("xlnet_ff_fwd: no instantiation");
     return -1;
+}
+extern "C" int t4r_xlnet_ff_fwd(void* stream, const float* h1, const float* planes, const float* b1, const float* b2,
+                                const float* gamma, const float* beta, float* ffpre, float* ffact, float* ffout, float* mean,
+                                float* rstd, float* hout, int T, int D, float eps, float drop_p, unsigned long long seed,
+                                unsigned long long ctr_act, unsigned long long ctr_out) {
+    return ff_fwd_impl(stream, h1, planes, b1, b2, gamma, beta, ffpre, ffact, ffout, mean, rstd, hout, T, D, eps, drop_p, seed,
+                       ctr_act, ctr_out, nullptr, 0);
+}
+// include/t4r_hip_rows.h
+extern "C" int t4r_xlnet_ff_fwd_rows(void* stream, const float* h1, const float* planes, const float* b1, const float* b2,
+                                     const float* gamma, const float* beta, float* ffpre, float* ffact, float* ffout,
+                                     float* mean, float* rstd, float* hout, int T, int D, float eps, float drop_p,
+                                     unsigned long long seed, unsigned long long ctr_act, unsigned long long ctr_out,
+                                     const int* rows, int n) {
+    T4R_CHECK_ARG(rows != nullptr, "xlnet_ff_fwd_rows: null row map");
+    T4R_CHECK_ARG(T >= 1, "xlnet_ff_fwd_rows: T must be positive");
+    return ff_fwd_impl(stream, h1, planes, b1, b2, gamma, beta, ffpre, ffact, ffout, mean, rstd, hout, T, D, eps, drop_p, seed,
+                       ctr_act, ctr_out, rows, n);
 }
 
 // Fused feed-forward block, backward (input gradients + bias / LayerNorm parameter gradients; the two weight gradients
 // d W2 += d ffout^T @ ffact and d W1 += d pre^T @ h1 are token-reducing GEMMs the caller issues on the rows written here).
 //   dy [T, D] = d loss / d hout;  dh1 [T, D] (overwritten) = d loss / d h1;  dffout [T, D], dpre [T, 4D] (overwritten);
 //   d_gamma, d_beta, d_b2 [D], d_b1 [4D] ACCUMULATED;  part: t4r_xlnet_ff_bwd_part_floats(T, D) floats of scratch.
-extern "C" int t4r_xlnet_ff_bwd(void* stream, const float* dy, const float* ffout, const float* h1, const float* mean,
-                                const float* rstd, const float* gamma, const float* ffpre, const float* planes,
-                                float* dh1, float* dffout, float* dpre, float* d_gamma, float* d_beta,
-                                float* d_b2, float* d_b1, float* part, int T, int D, float drop_p,
-                                unsigned long long seed, unsigned long long ctr_act, unsigned long long ctr_out) {
+static int ff_bwd_impl(void* stream, const float* dy, const float* ffout, const float* h1, const float* mean,
+                       const float* rstd, const float* gamma, const float* ffpre, const float* planes,
+                       float* dh1, float* dffout, float* dpre, float* d_gamma, float* d_beta,
+                       float* d_b2, float* d_b1, float* part, int T, int D, float drop_p,
+                       unsigned long long seed, unsigned long long ctr_act, unsigned long long ctr_out,
+                       const int* rows, int n, float* h1_rows) {
     if (T <= 0) return 0;
     T4R_CHECK_ARG(t4r_xlnet_fused_supported(D), "xlnet_ff_bwd: d_model must be 32, 64 or 128");
     T4R_CHECK_ARG(dy && ffout && h1 && mean && rstd && gamma && ffpre && planes && dh1 && dffout && dpre && part,
                   "xlnet_ff_bwd: null pointer");
-    const int R = t4r_xlnet_pick_r(T, true);
-    const int nwg = (T + 16 * R - 1) / (16 * R);
+    if (rows) {
+        T4R_CHECK_ARG(n >= 1 && n <= T, "xlnet_ff_bwd_rows: the number of mapped rows must be in [1, T]");
+        T4R_CHECK_ARG(h1_rows != nullptr, "xlnet_ff_bwd_rows: null pointer");
+        T4R_CHECK_ARG(t4r_xlnet_body_fp16x2(), "xlnet_ff_bwd_rows: the row-mapped kernels exist in the two-way fp16 form only");
+    }
+    const int Tk = rows ? n : T;       // rows the launch works on
+    const int R = t4r_xlnet_pick_r(Tk, true);
+    const int nwg = (Tk + 16 * R - 1) / (16 * R);
     float* partA = part;
     float* partB = part + (long)nwg * 3 * D;
     FFBwdParams p{dy, ffout, h1, mean, rstd, gamma, ffpre, carve_planes(planes, D), carve_planes_h(planes, D), g_ff_amax[2], g_ff_amax[3], dh1,
@@ -702,6 +815,16 @@ extern "C" int t4r_xlnet_ff_bwd(void* stream, const float* dy, const float* ffou
                   make_drop(g_ff_final_on ? drop_p : 0.f, seed, g_ff_final_ctr)};
     hipStream_t st = (hipStream_t)stream;
     auto launch = [&]() -> int {
+        if (rows) {
+            FFBwdRowsParams pr;
+            static_cast<FFBwdParams&>(pr) = p;
+            pr.T = n;
+            pr.rows = rows;
+            pr.h1c = h1_rows;
+            FUSED_DISPATCH(ff_bwd_rows_launch, D, R, st, pr);
+            t4r_set_error("xlnet_ff_bwd_rows: no instantiation");
+            return -1;
+        }
         FUSED_DISPATCH(ff_bwd_launch, D, R, st, p);
         t4r_set_error("xlnet_ff_bwd: no instantiation");
         return -1;
@@ -711,4 +834,24 @@ extern "C" int t4r_xlnet_ff_bwd(void* stream, const float* dy, const float* ffou
     int rc2 = t4r_reduce_partials_launch(st, partA, nwg, d_gamma, D, 1, d_beta, D, 1, d_b2, D, 1);
     if (rc2 != 0) return rc2;
     return t4r_reduce_partials_launch(st, partB, nwg, d_b1, 4 * D, 1, nullptr, 0, 0, nullptr, 0, 0);
+}
+extern "C" int t4r_xlnet_ff_bwd(void* stream, const float* dy, const float* ffout, const float* h1, const float* mean,
+                                const float* rstd, const float* gamma, const float* ffpre, const float* planes,
+                                float* dh1, float* dffout, float* dpre, float* d_gamma, float* d_beta,
+                                float* d_b2, float* d_b1, float* part, int T, int D, float drop_p,
+                                unsigned long long seed, unsigned long long ctr_act, unsigned long long ctr_out) {
+    return ff_bwd_impl(stream, dy, ffout, h1, mean, rstd, gamma, ffpre, planes, dh1, dffout, dpre, d_gamma, d_beta, d_b2, d_b1,
+                       part, T, D, drop_p, seed, ctr_act, ctr_out, nullptr, 0, nullptr);
+}
+// include/t4r_hip_rows.h
+extern "C" int t4r_xlnet_ff_bwd_rows(void* stream, const float* dy, const float* ffout, const float* h1, const float* mean,
+                                     const float* rstd, const float* gamma, const float* ffpre, const float* planes,
+                                     float* dh1, float* dffout, float* dpre, float* d_gamma, float* d_beta, float* d_b2,
+                                     float* d_b1, float* part, int T, int D, float drop_p, unsigned long long seed,
+                                     unsigned long long ctr_act, unsigned long long ctr_out, const int* rows, int n,
+                                     float* h1_rows) {
+    T4R_CHECK_ARG(rows != nullptr, "xlnet_ff_bwd_rows: null row map");
+    T4R_CHECK_ARG(T >= 1, "xlnet_ff_bwd_rows: T must be positive");
+    return ff_bwd_impl(stream, dy, ffout, h1, mean, rstd, gamma, ffpre, planes, dh1, dffout, dpre, d_gamma, d_beta, d_b2, d_b1,
+                       part, T, D, drop_p, seed, ctr_act, ctr_out, rows, n, h1_rows);
 }

@@ -16,6 +16,7 @@
 // xlnet_layer.hip; what they save is the operand cutting per 64 x 64 tile of the general kernel, the LayerNorm round
 // trips and the launch boundaries (measured per layer at the benchmark size, same box: see docs/DESIGN_rounds_1_to_4.md 4.1c).
 #include "xlnet_fused.h"
+#include <type_traits>
 
 // ---------------------------------------------------------------------------------------------- weight planes of a layer
 struct PlaneJob {
@@ -513,11 +514,20 @@ struct Ln1BwdParams {
     long T;
     DropCfg drop;
 };
+// The row-mapped form (include/t4r_hip_rows.h): T counts the COMPACT rows; dy is in compact order (the feed-forward backward's
+// d h1 rows), ao, h, mean, rstd are read and dh, dao, dav are written at rows[compact] (the entry zeroes the three outputs
+// first), the Philox counter is the token's; the partial sums are per workgroup of the compact launch.
+struct Ln1BwdRowsParams : Ln1BwdParams {
+    const int* rows;
+};
 
-template <int D, int R, bool HS = false>
-__global__ __launch_bounds__(D * 4) void xlnet_ln1_bwd_kernel(Ln1BwdParams p) {
+// Params = Ln1BwdRowsParams: the row-mapped form, its own instantiations (the plain ones compile to what they always were)
+template <int D, int R, bool HS = false, class Params = Ln1BwdParams>
+__global__ __launch_bounds__(D * 4) void xlnet_ln1_bwd_kernel(Params p) {
+    constexpr bool MAP = std::is_same<Params, Ln1BwdRowsParams>::value;
     constexpr int NW = D / 16, RT = 16 * R, PH = D + 16, PLN = RT * PH;
     extern __shared__ uint16_t smem16[];
+    auto tok = [&](long c) -> long { if constexpr (MAP) return (long)p.rows[c]; else return c; };     // token of a clamped compact row
     uint16_t* sh_d = smem16;                                         // [3][RT][PH] d attn_out planes
     float* sh_part = reinterpret_cast<float*>(sh_d + 3 * PLN);       // [NW][2][D]
     float* sh_inv = reinterpret_cast<float*>(sh_d + 2 * PLN);        // HS: [RT] inverse row scales
@@ -538,13 +548,16 @@ __global__ __launch_bounds__(D * 4) void xlnet_ln1_bwd_kernel(Ln1BwdParams p) {
         for (int row0 = w; row0 < RT; row0 += NW * RB) {
             float2 fo_[RB], hh_[RB], dd_[RB];
             float mu_[RB], rs_[RB];
+            long tk_[RB];       // MAP: the rows' tokens
 #pragma unroll
             for (int b = 0; b < RB; ++b) {          // unconditional loads from clamped addresses
                 const long tc = min(t0 + min(row0 + b * NW, RT - 1), p.T - 1);
-                mu_[b] = p.mean[tc]; rs_[b] = p.rstd[tc];
+                const long tt = tok(tc);
+                if constexpr (MAP) tk_[b] = tt;
+                mu_[b] = p.mean[tt]; rs_[b] = p.rstd[tt];
                 const int cc = act_lane ? c0 : 0;
-                fo_[b] = *reinterpret_cast<const float2*>(p.ao + tc * D + cc);
-                hh_[b] = *reinterpret_cast<const float2*>(p.h + tc * D + cc);
+                fo_[b] = *reinterpret_cast<const float2*>(p.ao + tt * D + cc);
+                hh_[b] = *reinterpret_cast<const float2*>(p.h + tt * D + cc);
                 dd_[b] = *reinterpret_cast<const float2*>(p.dy + tc * D + cc);
             }
 #pragma unroll
@@ -557,8 +570,9 @@ __global__ __launch_bounds__(D * 4) void xlnet_ln1_bwd_kernel(Ln1BwdParams p) {
                 const float mu = mu_[b], rs = rs_[b];
                 float xh[2] = {0.f, 0.f}, gg[2] = {0.f, 0.f}, dyv[2] = {0.f, 0.f}, m[2] = {1.f, 1.f}, dx[2];
                 float s1 = 0.f, s2 = 0.f;
+                const long tq = MAP ? tk_[b] : t;      // the token: Philox counter and output row
                 if (act_lane) {
-                    drop_scale_vec<2>(p.drop, (unsigned long long)t * D + c0, true, m);
+                    drop_scale_vec<2>(p.drop, (unsigned long long)tq * D + c0, true, m);
                     const float2 fo = fo_[b], hh = hh_[b], dd = dd_[b];
                     const float xv[2] = {fo.x * m[0] + hh.x, fo.y * m[1] + hh.y};
                     dyv[0] = dd.x; dyv[1] = dd.y;
@@ -580,8 +594,8 @@ __global__ __launch_bounds__(D * 4) void xlnet_ln1_bwd_kernel(Ln1BwdParams p) {
                     pb[e] += dyv[e];
                 }
                 if (act_lane) {
-                    *reinterpret_cast<float2*>(p.dh + t * D + c0) = make_float2(dx[0], dx[1]);
-                    *reinterpret_cast<float2*>(p.dao + t * D + c0) = make_float2(dxa[0], dxa[1]);
+                    *reinterpret_cast<float2*>(p.dh + tq * D + c0) = make_float2(dx[0], dx[1]);
+                    *reinterpret_cast<float2*>(p.dao + tq * D + c0) = make_float2(dxa[0], dxa[1]);
                 }
             }
             if constexpr (HS) {      // the gradient row positioned by its own power-of-two scale (wave-uniform)
@@ -631,7 +645,7 @@ __global__ __launch_bounds__(D * 4) void xlnet_ln1_bwd_kernel(Ln1BwdParams p) {
     for (int r = 0; r < R; ++r) {
         const long t = t0 + r * 16 + n;
         const float sc = HS ? sh_inv[r * 16 + n] * iw : 1.f;
-        if (t < p.T) st4(p.dav + t * D + f0, make_float4(acc[r][0] * sc, acc[r][1] * sc, acc[r][2] * sc, acc[r][3] * sc));
+        if (t < p.T) st4(p.dav + tok(t) * D + f0, make_float4(acc[r][0] * sc, acc[r][1] * sc, acc[r][2] * sc, acc[r][3] * sc));
     }
 }
 
@@ -926,6 +940,42 @@ extern "C" long t4r_xlnet_ln1_bwd_part_floats(long T, int D) { return ((T + 15) 
 // LayerNorm-1 backward + d attn_vec.  dy = d loss / d h1.  Overwrites dh (residual part of d loss / d h), dao (d loss / d of
 // the o-projection output: rows of the o weight gradient d o += dao^T @ attn_vec) and dav (d loss / d attn_vec);
 // d_gamma, d_beta ACCUMULATED.  part: t4r_xlnet_ln1_bwd_part_floats(T, D) floats.
+// include/t4r_hip_rows.h: the same on n mapped rows; dh, dao, dav are zeroed first (three fills on the caller's stream)
+extern "C" int t4r_xlnet_ln1_bwd_rows(void* stream, const float* dy, const float* ao, const float* h, const float* mean,
+                                      const float* rstd, const float* gamma, const float* planes, float* dh, float* dao,
+                                      float* dav, float* d_gamma, float* d_beta, float* part, long T, int D, float drop_p,
+                                      unsigned long long seed, unsigned long long ctr_hi, const int* rows, int n) {
+    T4R_CHECK_ARG(rows != nullptr, "xlnet_ln1_bwd_rows: null row map");
+    T4R_CHECK_ARG(T >= 1 && n >= 1 && n <= T, "xlnet_ln1_bwd_rows: the number of mapped rows must be in [1, T]");
+    T4R_CHECK_ARG(t4r_xlnet_fused_supported(D) && dy && ao && h && mean && rstd && gamma && planes && dh && dao && dav && part,
+                  "xlnet_ln1_bwd_rows: bad arguments");
+    T4R_CHECK_ARG(t4r_xlnet_body_fp16x2(), "xlnet_ln1_bwd_rows: the row-mapped kernels exist in the two-way fp16 form only");
+    const int R = t4r_xlnet_pick_r(n, true);
+    const int nwg = (n + 16 * R - 1) / (16 * R);
+    const LayerPlanesH PH_ = carve_planes_h(planes, D);
+    Ln1BwdRowsParams p;
+    static_cast<Ln1BwdParams&>(p) = Ln1BwdParams{dy, ao, h, mean, rstd, gamma, PH_.OT, PH_.scale + HS_O, dh, dao, dav, part, (long)n,
+                                                 make_drop(drop_p, seed, ctr_hi)};
+    p.rows = rows;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t bytes = (size_t)T * D * sizeof(float);
+    if (hipMemsetAsync(dh, 0, bytes, st) != hipSuccess || hipMemsetAsync(dao, 0, bytes, st) != hipSuccess ||
+        hipMemsetAsync(dav, 0, bytes, st) != hipSuccess) {
+        t4r_set_error("xlnet_ln1_bwd_rows: memset failed");
+        return -1;
+    }
+#define CALL(DD, RR)                                                                                             \
+    {                                                                                                            \
+        const size_t smem = (size_t)3 * 16 * RR * (DD + 16) * 2 + (size_t)(DD / 16) * 2 * DD * 4;                \
+        { static T4rLdsAttr once; t4r_ensure_dynamic_lds((const void*)xlnet_ln1_bwd_kernel<DD, RR, true, Ln1BwdRowsParams>, smem, once); } \
+        hipLaunchKernelGGL((xlnet_ln1_bwd_kernel<DD, RR, true, Ln1BwdRowsParams>), dim3((unsigned)nwg), dim3(DD * 4), smem, st, p);  \
+    }
+    ATTN_DISPATCH(CALL, D, R)
+#undef CALL
+    T4R_LAUNCH_CHECK();
+    return t4r_reduce_partials_launch(st, part, nwg, d_gamma, D, 1, d_beta, D, 1, nullptr, 0, 0);
+}
+
 extern "C" int t4r_xlnet_ln1_bwd(void* stream, const float* dy, const float* ao, const float* h, const float* mean,
                                  const float* rstd, const float* gamma, const float* planes, float* dh, float* dao, float* dav,
                                  float* d_gamma, float* d_beta, float* part, long T, int D, float drop_p,

@@ -14,6 +14,7 @@
 //   h1 = LN(attn_vec @ o^T + h) ; h2 = LN(W2 gelu(W1 h1 + b1) + b2 + h1)
 // Saved-for-backward activations live in one caller-provided workspace (offsets below).
 #include "t4r_common.h"
+#include <stdio.h>
 #include <stdlib.h>
 
 int t4r_gemm_launch(hipStream_t stream, int transA, int transB, int M, int N, int K, float alpha,
@@ -90,6 +91,16 @@ long t4r_xlnet_ln1_bwd_part_floats(long, int);
 int t4r_xlnet_ln1_bwd(void*, const float*, const float*, const float*, const float*, const float*, const float*, const float*,
                       float*, float*, float*, float*, float*, float*, long, int, float, unsigned long long, unsigned long long);
 int t4r_xlnet_dh(void*, const float*, const float*, float*, long, int);
+// include/t4r_hip_rows.h: the row-mapped forms of the three row-wise kernels
+int t4r_xlnet_ff_fwd_rows(void*, const float*, const float*, const float*, const float*, const float*, const float*, float*, float*,
+                          float*, float*, float*, float*, int, int, float, float, unsigned long long, unsigned long long,
+                          unsigned long long, const int*, int);
+int t4r_xlnet_ff_bwd_rows(void*, const float*, const float*, const float*, const float*, const float*, const float*, const float*,
+                          const float*, float*, float*, float*, float*, float*, float*, float*, float*, int, int, float,
+                          unsigned long long, unsigned long long, unsigned long long, const int*, int, float*);
+int t4r_xlnet_ln1_bwd_rows(void*, const float*, const float*, const float*, const float*, const float*, const float*, const float*,
+                           float*, float*, float*, float*, float*, float*, long, int, float, unsigned long long,
+                           unsigned long long, const int*, int);
 // xlnet_attn_block.hip: the attention half as one kernel per direction, exact fp32 matrix instructions
 int t4r_xlnet_attn_block_supported(int L, int D, int n_head);
 int t4r_xlnet_attn_block_fwd(void*, const float*, const float*, const float*, const float*, long, const float*, const float*,
@@ -224,7 +235,7 @@ extern "C" long t4r_xlnet_layer_bwd_ws_floats(int B, int L, int D, int n_head, i
            2 * align4(t4r_colreduce_ws_floats(T, 2 * D)) + align4(t4r_colreduce_ws_floats(T, D)) +
            (dropout ? align4(T * D) : 0) + 2 * align4(T * D) + align4(t4r_xlnet_ff_bwd_part_floats(T, D)) +
            align4(t4r_xlnet_ln1_bwd_part_floats(T, D)) + align4(attn_block_bwd_part(B, L, D, n_head)) +
-           align4(splitk_sink_floats(T, D));
+           align4(splitk_sink_floats(T, D)) + align4(T * D);       // last: the mapped h1 rows of t4r_xlnet_layer_bwd_rows
 }
 
 #define RUN(call)                \
@@ -233,11 +244,27 @@ extern "C" long t4r_xlnet_layer_bwd_ws_floats(int B, int L, int D, int n_head, i
         if (rc__ != 0) return rc__; \
     } while (0)
 
-extern "C" int t4r_xlnet_layer_fwd(void* stream, const float* h, const float* pos_emb,
-                                   const float* const* params, float* ws, float* h_out, int B, int L,
-                                   int D, int n_head, float ln_eps, float drop_p,
-                                   unsigned long long seed, unsigned long long offset, int layer_idx,
-                                   const int* key_len, const float* pos_emb_b) {
+// Checked before any launch by both row-mapped layer entries (include/t4r_hip_rows.h)
+static int rows_args_ok(const char* who, int B, int L, int D, int n_head, const int* key_len, const int* rows, int n) {
+    char msg[200];      // t4r_set_error copies it
+    const char* why = nullptr;
+    if (!rows) why = "null row map";
+    else if (B < 1 || L < 1 || n < 1 || (long)n > (long)B * L) why = "the number of mapped rows must be in [1, B L]";
+    else if (key_len) why = "no row map together with key_len (the padding mask)";
+    else if (n_head < 1 || D % n_head != 0 || !(use_fused(D) && use_attn_block(L, D, n_head)))
+        why = "needs the token-tile kernels (d_model 32 / 64 / 128) and the one-kernel attention forward (L <= 32, d_head 16 / 32)";
+    if (!why) return 0;
+    snprintf(msg, sizeof(msg), "%s: %s", who, why);
+    t4r_set_error(msg);
+    return -1;
+}
+
+// rows != null: the feed-forward block on the n mapped rows only (include/t4r_hip_rows.h), h_out zero elsewhere
+static int layer_fwd_impl(void* stream, const float* h, const float* pos_emb,
+                          const float* const* params, float* ws, float* h_out, int B, int L,
+                          int D, int n_head, float ln_eps, float drop_p,
+                          unsigned long long seed, unsigned long long offset, int layer_idx,
+                          const int* key_len, const float* pos_emb_b, const int* rows, int n_rows) {
     if (B == 0) return 0;
     T4R_CHECK_ARG(D % n_head == 0 && D % 4 == 0, "xlnet_layer: d_model must divide by n_head and 4");
     T4R_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f, "xlnet_layer: dropout p in [0, 1)");
@@ -290,9 +317,17 @@ extern "C" int t4r_xlnet_layer_fwd(void* stream, const float* h, const float* po
                                ln_eps, drop_p, seed, C(SITE_ATTN_OUT)));
         }
         const long ns = t4r_xlnet_ff_amax_slots(T);
+        if (rows && hipMemsetAsync(h_out, 0, (size_t)T * D * sizeof(float), st) != hipSuccess) {
+            t4r_set_error("xlnet_layer_fwd_rows: memset failed");
+            return -1;
+        }
         t4r_xlnet_ff_amax_buffers(w.amax, w.amax + ns, nullptr, nullptr);
         t4r_xlnet_ff_final_dropout(fuse_final && drop, ctr_hi(offset, 255, SITE_FINAL));
-        const int rc = t4r_xlnet_ff_fwd(stream, w.h1, w.planes, params[P_B1], params[P_B2], params[P_LN2W], params[P_LN2B], w.ffpre,
+        // with a map: ffpre / ffact / ffout in compact order [n, .] inside their full-size slots, mean2 / rstd2 at the token rows
+        const int rc = rows ? t4r_xlnet_ff_fwd_rows(stream, w.h1, w.planes, params[P_B1], params[P_B2], params[P_LN2W], params[P_LN2B],
+                                                    w.ffpre, w.ffact, w.ffout, w.mean2, w.rstd2, h_out, T, D, ln_eps, drop_p, seed,
+                                                    C(SITE_FF_ACT), C(SITE_FF_OUT), rows, n_rows)
+                            : t4r_xlnet_ff_fwd(stream, w.h1, w.planes, params[P_B1], params[P_B2], params[P_LN2W], params[P_LN2B], w.ffpre,
                                         w.ffact, w.ffout, w.mean2, w.rstd2, h_out, T, D, ln_eps, drop_p, seed, C(SITE_FF_ACT),
                                         C(SITE_FF_OUT));
         t4r_xlnet_ff_final_dropout(0, 0);
@@ -342,6 +377,23 @@ extern "C" int t4r_xlnet_layer_fwd(void* stream, const float* h, const float* po
     RUN(t4r_add_layernorm_fwd(stream, w.ffout, w.h1, params[P_LN2W], params[P_LN2B], h_out, w.mean2,
                               w.rstd2, T, D, ln_eps, drop_p, seed, C(SITE_FF_OUT)));
     return 0;
+}
+
+extern "C" int t4r_xlnet_layer_fwd(void* stream, const float* h, const float* pos_emb,
+                                   const float* const* params, float* ws, float* h_out, int B, int L,
+                                   int D, int n_head, float ln_eps, float drop_p,
+                                   unsigned long long seed, unsigned long long offset, int layer_idx,
+                                   const int* key_len, const float* pos_emb_b) {
+    return layer_fwd_impl(stream, h, pos_emb, params, ws, h_out, B, L, D, n_head, ln_eps, drop_p, seed, offset, layer_idx, key_len,
+                          pos_emb_b, nullptr, 0);
+}
+extern "C" int t4r_xlnet_layer_fwd_rows(void* stream, const float* h, const float* pos_emb, const float* const* params, float* ws,
+                                        float* h_out, int B, int L, int D, int n_head, float ln_eps, float drop_p,
+                                        unsigned long long seed, unsigned long long offset, int layer_idx, const int* key_len,
+                                        const float* pos_emb_b, const int* rows, int n) {
+    RUN(rows_args_ok("xlnet_layer_fwd_rows", B, L, D, n_head, key_len, rows, n));
+    return layer_fwd_impl(stream, h, pos_emb, params, ws, h_out, B, L, D, n_head, ln_eps, drop_p, seed, offset, layer_idx, key_len,
+                          pos_emb_b, rows, n);
 }
 
 // Weight-gradient contractions feed nothing but the optimizer, so the layer backward issues them on a
@@ -419,12 +471,13 @@ extern "C" void t4r_xlnet_layer_bwd_defer(int on) { g_defer_join = on ? 1 : 0; }
 
 // grads[] are ACCUMULATED into (zero them / let the optimizer zero them between steps).
 // dh_in [T,D] is overwritten with d loss / d h.
-extern "C" int t4r_xlnet_layer_bwd(void* stream, const float* h, const float* pos_emb,
-                                   const float* const* params, float* const* grads, const float* ws,
-                                   float* bws, const float* dh_out, float* dh_in, int B, int L, int D,
-                                   int n_head, float ln_eps, float drop_p, unsigned long long seed,
-                                   unsigned long long offset, int layer_idx, const int* key_len,
-                                   const float* pos_emb_b) {
+// rows != null: the backward of layer_fwd_impl with the same map -- dh_out is read at the n mapped rows only
+static int layer_bwd_impl(void* stream, const float* h, const float* pos_emb,
+                          const float* const* params, float* const* grads, const float* ws,
+                          float* bws, const float* dh_out, float* dh_in, int B, int L, int D,
+                          int n_head, float ln_eps, float drop_p, unsigned long long seed,
+                          unsigned long long offset, int layer_idx, const int* key_len,
+                          const float* pos_emb_b, const int* rows, int n_rows) {
     if (B == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     const int T = B * L, dh = D / n_head;
@@ -468,6 +521,7 @@ extern "C" int t4r_xlnet_layer_bwd(void* stream, const float* h, const float* po
         SinkGuard(float* ws, long cap) { t4r_splitk_sink_begin(ws, cap); }
         ~SinkGuard() { t4r_splitk_sink_end(); }
     } sink_guard(take(splitk_sink_floats(T, D)), splitk_sink_floats(T, D));
+    float* h1c = take(TD);                      // row-mapped backward: the mapped rows of h1 in compact order (W1 gradient operand)
 
     SideStream* ss = side_stream();
     struct RedirectGuard {      // second stages of the column reductions -> side stream, for this call only
@@ -513,12 +567,18 @@ extern "C" int t4r_xlnet_layer_bwd(void* stream, const float* h, const float* po
         const long ns = t4r_xlnet_ff_amax_slots(T);
         // workgroups (= maxima slots) of the forward launches and of this backward launch: the backward's tile follows the CU
         // budget (t4r_xlnet_set_cu_budget: a collective may hold CUs now), the forward's never does
-        const int na = t4r_xlnet_ff_amax_count(T), nb = t4r_xlnet_ff_amax_count_bwd(T);
+        // (with a map: the launches ran / run on n_rows compact rows; dx, dfo, dff then hold [n_rows, .] in compact order)
+        const int Tk = rows ? n_rows : T;
+        const int na = t4r_xlnet_ff_amax_count(Tk), nb = t4r_xlnet_ff_amax_count_bwd(Tk);
         float* am = w.amax;          // max |h1|, max |act| (forward), max |d pre|, max |d ffout| (now): one float per workgroup
         t4r_xlnet_ff_amax_buffers(nullptr, nullptr, am + 2 * ns, am + 3 * ns);
         {
             t4r_xlnet_ff_final_dropout(fuse_final && drop, ctr_hi(offset, 255, SITE_FINAL));
-            const int rc = t4r_xlnet_ff_bwd(stream, dh_out, w.ffout, w.h1, w.mean2, w.rstd2, params[P_LN2W], w.ffpre, w.planes,
+            const int rc = rows ? t4r_xlnet_ff_bwd_rows(stream, dh_out, w.ffout, w.h1, w.mean2, w.rstd2, params[P_LN2W], w.ffpre,
+                                                        w.planes, dx, dfo, dff, grads[P_LN2W], grads[P_LN2B], grads[P_B2],
+                                                        grads[P_B1], ff_part, T, D, drop_p, seed, C(SITE_FF_ACT), C(SITE_FF_OUT),
+                                                        rows, n_rows, h1c)
+                                : t4r_xlnet_ff_bwd(stream, dh_out, w.ffout, w.h1, w.mean2, w.rstd2, params[P_LN2W], w.ffpre, w.planes,
                                             dx, dfo, dff, grads[P_LN2W], grads[P_LN2B], grads[P_B2], grads[P_B1], ff_part,
                                             T, D, drop_p, seed, C(SITE_FF_ACT), C(SITE_FF_OUT));
             t4r_xlnet_ff_final_dropout(0, 0);
@@ -528,12 +588,13 @@ extern "C" int t4r_xlnet_layer_bwd(void* stream, const float* h, const float* po
         // the two weight gradients in the two-way fp16 form, positioned by the operand maxima the fused kernels left
         const bool hs = t4r_xlnet_body_fp16x2() && drop_p >= 0.f;
         if (hs) t4r_gemm_operand_amax2(am + 3 * ns, nb, am + ns, na);
-        RUN(t4r_gemm_launch(wg(), 1, 0, D, 4 * D, T, 1.f, dfo, D, w.ffact, 4 * D, grads[P_W2], 4 * D, nullptr,
+        // (with a map the two products contract over the n_rows compact rows)
+        RUN(t4r_gemm_launch(wg(), 1, 0, D, 4 * D, Tk, 1.f, dfo, D, w.ffact, 4 * D, grads[P_W2], 4 * D, nullptr,
                             EPI_NONE, nullptr, 0, -1, 1, 1, 0, 0, 0, nullptr));
         {
             hipStream_t s1 = wg_again();
             if (hs) t4r_gemm_operand_amax2(am + 2 * ns, nb, am, na);
-            RUN(t4r_gemm_launch(s1, 1, 0, 4 * D, D, T, 1.f, dff, 4 * D, w.h1, D, grads[P_W1], D, nullptr,
+            RUN(t4r_gemm_launch(s1, 1, 0, 4 * D, D, Tk, 1.f, dff, 4 * D, rows ? h1c : w.h1, D, grads[P_W1], D, nullptr,
                                 EPI_NONE, nullptr, 0, -1, 1, 1, 0, 0, 0, nullptr));
             // first reduction launch of the call: W2, W1 and the bias / LayerNorm-2 sums of the feed-forward half
             RUN(t4r_splitk_sink_flush(s1));
@@ -575,6 +636,12 @@ extern "C" int t4r_xlnet_layer_bwd(void* stream, const float* h, const float* po
 #endif
         {
         // LayerNorm-1 backward + d attn_vec in one launch; the attention core; d h from d q, d k, d v in one launch
+        // (with a map: dx holds the mapped rows in compact order; dh_in, dao_buf, dav are zeroed and written at the token rows, so
+        // the attention core, d h and the o product -- K = T on the zero-filled d attn_out -- run as ever)
+        if (rows)
+            RUN(t4r_xlnet_ln1_bwd_rows(stream, dx, w.ao, h, w.mean1, w.rstd1, params[P_LN1W], w.planes, dh_in, dao_buf, dav,
+                                       grads[P_LN1W], grads[P_LN1B], ln1_part, T, D, drop_p, seed, C(SITE_ATTN_OUT), rows, n_rows));
+        else
         RUN(t4r_xlnet_ln1_bwd(stream, dx, w.ao, h, w.mean1, w.rstd1, params[P_LN1W], w.planes, dh_in, dao_buf, dav,
                               grads[P_LN1W], grads[P_LN1B], ln1_part, T, D, drop_p, seed, C(SITE_ATTN_OUT)));
         // (the one-kernel forward left the probabilities in the workspace: the core reads them instead of recomputing the scores)
@@ -673,6 +740,25 @@ extern "C" int t4r_xlnet_layer_bwd(void* stream, const float* h, const float* po
         (void)hipStreamWaitEvent(st, ss->done_all, 0);
     }
     return 0;
+}
+
+extern "C" int t4r_xlnet_layer_bwd(void* stream, const float* h, const float* pos_emb,
+                                   const float* const* params, float* const* grads, const float* ws,
+                                   float* bws, const float* dh_out, float* dh_in, int B, int L, int D,
+                                   int n_head, float ln_eps, float drop_p, unsigned long long seed,
+                                   unsigned long long offset, int layer_idx, const int* key_len,
+                                   const float* pos_emb_b) {
+    return layer_bwd_impl(stream, h, pos_emb, params, grads, ws, bws, dh_out, dh_in, B, L, D, n_head, ln_eps, drop_p, seed, offset,
+                          layer_idx, key_len, pos_emb_b, nullptr, 0);
+}
+extern "C" int t4r_xlnet_layer_bwd_rows(void* stream, const float* h, const float* pos_emb, const float* const* params,
+                                        float* const* grads, const float* ws, float* bws, const float* dh_out, float* dh_in,
+                                        int B, int L, int D, int n_head, float ln_eps, float drop_p, unsigned long long seed,
+                                        unsigned long long offset, int layer_idx, const int* key_len, const float* pos_emb_b,
+                                        const int* rows, int n) {
+    RUN(rows_args_ok("xlnet_layer_bwd_rows", B, L, D, n_head, key_len, rows, n));
+    return layer_bwd_impl(stream, h, pos_emb, params, grads, ws, bws, dh_out, dh_in, B, L, D, n_head, ln_eps, drop_p, seed, offset,
+                          layer_idx, key_len, pos_emb_b, rows, n);
 }
 
 // the caller's stream waits for everything queued so far on the weight-gradient streams of the current device, whichever

@@ -19,9 +19,57 @@ class _Body(nn.ModuleList):
     def inputs(self):
         return self[0]
 
-    def forward(self, inputs, training=False, testing=False, **kwargs):
+    def forward(self, inputs, training=False, testing=False, out_rows=None, **kwargs):
+        """out_rows: () -> (rows, n) or None, handed on to the transformer block, which asks it just before its last layer"""
         x = self[0](inputs, training=training, testing=testing)
-        return self[1](x)
+        return self[1](x) if out_rows is None else self[1](x, out_rows=out_rows)
+
+
+def last_rows_gate(model, training, B, L, n_labels=None):
+    """The number of label rows n when the LAST XLNet layer of `model` may run its row-wise half (feed-forward block,
+    LayerNorm-1 backward) on the label rows only, else None (every row is computed, as ever).  It may when nothing reads the
+    other rows of the body's output and their gradient is exactly zero:
+      * a training step with gradients enabled (evaluation and inference compute every row);
+      * the XLNet body behind a plain TransformerBlock without mask_padding, nobody hooked onto the body's output;
+      * the task is NextItemPredictionTask itself with the tied head: it gathers the rows at the masking module's label
+        positions and scatters its gradient to them (prediction_task._NextItemHeadFn) -- a subclass or another head may read
+        more;
+      * the token-tile kernels and the one-kernel attention forward take the shape;
+      * the row rule: n <= transformer._LAST_ROWS_MAX_FRACTION * B * L (CLM training, labels at nearly every position, stays
+        on the full path).
+    n_labels: the count when the caller has it (tests); default: masking.n_labels(), the 4-byte copy started right after the
+    masking kernel -- asked here, just before the last layer is enqueued, instead of at the head."""
+    from . import transformer as tfm
+
+    if not (tfm._LAST_ROWS and training and torch.is_grad_enabled()):
+        return None
+    # this runs on the host's critical path of every training step: the modules and what their classes say are looked up once
+    parts = model.__dict__.get("_last_rows_parts")
+    if parts is None:
+        from .masking import CausalLanguageModeling, MaskedLanguageModeling
+        from .prediction_task import NextItemPredictionTask
+
+        block, task, body = model.transformer_block, model.prediction_task, model.heads[0].body
+        kinds = (type(block) is tfm.TransformerBlock and type(block.transformer) is tfm.XLNetModel
+                 and type(task) is NextItemPredictionTask and task.masking is not None and task.masking is body[0].masking
+                 and type(task.masking) in (MaskedLanguageModeling, CausalLanguageModeling))
+        parts = model.__dict__["_last_rows_parts"] = (block, block.transformer, task, body, kinds, {})
+    block, xl, task, body, kinds, shapes = parts
+    if not kinds or block.mask_padding or not task.weight_tying or not xl.training or not tfm._FUSED_ON:
+        return None
+    for m in (body, block, xl, task):
+        if m._forward_hooks or m._forward_pre_hooks:
+            return None
+    ok = shapes.get(L)
+    if ok is None:
+        cfg = xl.config
+        ok = shapes[L] = bool(ops.xlnet_fused_supported(cfg.d_model) and ops.xlnet_attn_block_supported(L, cfg.d_model, cfg.n_head))
+    if not ok:
+        return None
+    n = int(task.masking.n_labels() if n_labels is None else n_labels)
+    if n < 1 or n > tfm._LAST_ROWS_MAX_FRACTION * B * L:
+        return None
+    return n
 
 
 class Head(nn.Module):
@@ -76,7 +124,14 @@ class Model(nn.Module):
         inputs = {k: (v.to(torch.float32) if torch.is_floating_point(v) else v) for k, v in inputs.items()}
         inputs = self.pad_inputs(inputs)
         head = self.heads[0]
-        h = head.body(inputs, training=training, testing=testing)
+
+        def out_rows(B, L):
+            # the last layer on the label rows only, where nothing reads the others (last_rows_gate); asked by XLNetModel.forward
+            # just before it enqueues its last layer: the wait for the label count (masking.n_labels) sits there, not at the head
+            n = last_rows_gate(self, training, B, L)
+            return None if n is None else (self.prediction_task.masking.compact_labels()[1], n)
+
+        h = head.body(inputs, training=training, testing=testing, out_rows=out_rows if training else None)
         task = self.prediction_task
         if training or testing:
             return task(h, targets=targets, training=training, testing=testing)

@@ -781,9 +781,11 @@ def xlnet_pos_emb_dropout(pos_emb, B, p, seed, offset):
 
 
 def xlnet_layer_fwd(h, pos_emb, params, B, L, n_head, eps, ws=None, drop_p=0.0, seed=0, offset=0,
-                    layer_idx=0, key_len=None, pos_emb_b=None, stack_prepared=False):
+                    layer_idx=0, key_len=None, pos_emb_b=None, stack_prepared=False, rows=None, n_rows=None):
     """h [B*L, D]; params: sequence of 15 tensors in XLNET_PARAM_ORDER.  -> (h_out, ws)
-    stack_prepared: `ws` already holds this layer's weight planes and k_r (xlnet_stack_prepare)"""
+    stack_prepared: `ws` already holds this layer's weight planes and k_r (xlnet_stack_prepare)
+    rows (int32, ascending, unique, first n_rows entries valid): the feed-forward block runs on these rows only and h_out is
+    zero elsewhere (include/t4r_hip_rows.h: t4r_xlnet_layer_fwd_rows); the backward must be given the same map"""
     D = h.shape[-1]
     if ws is None:
         ws = torch.empty(xlnet_layer_ws_floats(B, L, D, n_head, drop_p > 0), device=h.device,
@@ -794,9 +796,13 @@ def xlnet_layer_fwd(h, pos_emb, params, B, L, n_head, eps, ws=None, drop_p=0.0, 
     if stack_prepared:
         lib.t4r_xlnet_stack_prepared(1)
     try:
-        call("t4r_xlnet_layer_fwd", _stream(), _chk(h, torch.float32), _chk(pos_emb, torch.float32), parr,
-             ws.data_ptr(), out.data_ptr(), B, L, D, n_head, float(eps), float(drop_p), int(seed),
-             int(offset), int(layer_idx), _p(key_len, torch.int32), _p(pos_emb_b, torch.float32))
+        args = (_stream(), _chk(h, torch.float32), _chk(pos_emb, torch.float32), parr,
+                ws.data_ptr(), out.data_ptr(), B, L, D, n_head, float(eps), float(drop_p), int(seed),
+                int(offset), int(layer_idx), _p(key_len, torch.int32), _p(pos_emb_b, torch.float32))
+        if rows is None:
+            call("t4r_xlnet_layer_fwd", *args)
+        else:
+            call("t4r_xlnet_layer_fwd_rows", *args, _chk(rows, torch.int32), int(n_rows))
     finally:
         if stack_prepared:
             lib.t4r_xlnet_stack_prepared(0)
@@ -836,8 +842,9 @@ def xlnet_stack_prepare(params_all, B, L, n_head, pos, drop, pos_dropout=None):
 
 
 def xlnet_layer_bwd(h, pos_emb, params, grads, ws, dh_out, B, L, n_head, eps, bws=None, drop_p=0.0,
-                    seed=0, offset=0, layer_idx=0, key_len=None, pos_emb_b=None, defer_join=None):
-    """defer_join: a list -> the call returns without waiting for its weight-gradient streams (csrc/xlnet_layer.hip:
+                    seed=0, offset=0, layer_idx=0, key_len=None, pos_emb_b=None, defer_join=None, rows=None, n_rows=None):
+    """rows, n_rows: the map the forward was given (xlnet_layer_fwd): dh_out is read at these rows only.
+    defer_join: a list -> the call returns without waiting for its weight-gradient streams (csrc/xlnet_layer.hip:
     deferred join) and appends every buffer those streams may still be using to the list; the caller keeps the list
     alive until it has called xlnet_layer_bwd_join()."""
     D = h.shape[-1]
@@ -851,14 +858,18 @@ def xlnet_layer_bwd(h, pos_emb, params, grads, ws, dh_out, B, L, n_head, eps, bw
     if defer_join is not None:
         lib.t4r_xlnet_layer_bwd_defer(1)
     try:
-        call("t4r_xlnet_layer_bwd", _stream(), _chk(h), _chk(pos_emb), parr, garr, _chk(ws),
-             bws.data_ptr(), _chk(dh_out), dh_in.data_ptr(), B, L, D, n_head, float(eps), float(drop_p),
-             int(seed), int(offset), int(layer_idx), _p(key_len, torch.int32), _p(pos_emb_b, torch.float32))
+        args = (_stream(), _chk(h), _chk(pos_emb), parr, garr, _chk(ws),
+                bws.data_ptr(), _chk(dh_out), dh_in.data_ptr(), B, L, D, n_head, float(eps), float(drop_p),
+                int(seed), int(offset), int(layer_idx), _p(key_len, torch.int32), _p(pos_emb_b, torch.float32))
+        if rows is None:
+            call("t4r_xlnet_layer_bwd", *args)
+        else:
+            call("t4r_xlnet_layer_bwd_rows", *args, _chk(rows, torch.int32), int(n_rows))
     finally:
         if defer_join is not None:
             lib.t4r_xlnet_layer_bwd_defer(0)
     if defer_join is not None:
-        defer_join.append((h, pos_emb, list(params), list(grads), ws, bws, dh_out, key_len, pos_emb_b))
+        defer_join.append((h, pos_emb, list(params), list(grads), ws, bws, dh_out, key_len, pos_emb_b, rows))
     return dh_in
 
 

@@ -137,15 +137,20 @@ def relative_positional_encoding(L, D):
 
 class _XLNetLayerFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, h, anchor, layer, pos_emb, n_head, eps, drop, key_len=None, pos_emb_b=None, ws=None):
-        """ws: this layer's workspace with its weight planes and k_r already in it (XLNetModel.forward: stack prologue)"""
+    def forward(ctx, h, anchor, layer, pos_emb, n_head, eps, drop, key_len=None, pos_emb_b=None, ws=None, out_rows=None):
+        """ws: this layer's workspace with its weight planes and k_r already in it (XLNetModel.forward: stack prologue)
+        out_rows: (rows int32, n) -- the consumer reads the output at these rows only and returns a gradient that is zero
+        elsewhere: the feed-forward block and LayerNorm-1 backward run on them alone (include/t4r_hip_rows.h)"""
         B, L, D = h.shape
         h2 = h.contiguous().view(B * L, D)
         params = [p.detach() for p in layer.ordered_params()]
         p, seed, offset, idx = drop
         out, ws = ops.xlnet_layer_fwd(h2, pos_emb, params, B, L, n_head, eps, ws=ws, drop_p=p, seed=seed,
                                       offset=offset, layer_idx=idx, key_len=key_len, pos_emb_b=pos_emb_b,
-                                      stack_prepared=ws is not None)
+                                      stack_prepared=ws is not None,
+                                      rows=None if out_rows is None else out_rows[0],
+                                      n_rows=None if out_rows is None else out_rows[1])
+        ctx.out_rows = out_rows
         ctx.layer, ctx.pos_emb, ctx.cfg, ctx.drop, ctx.key_len = layer, pos_emb, (B, L, D, n_head, eps), drop, key_len
         ctx.pos_emb_b = pos_emb_b
         ctx.save_for_backward(h2, ws)
@@ -165,11 +170,12 @@ class _XLNetLayerFn(torch.autograd.Function):
         dh = ops.xlnet_layer_bwd(h2, ctx.pos_emb, [q.detach() for q in plist], grads, ws,
                                  dout.contiguous().view(B * L, D), B, L, n_head, eps, drop_p=p, seed=seed,
                                  offset=offset, layer_idx=idx, key_len=ctx.key_len, pos_emb_b=ctx.pos_emb_b,
-                                 defer_join=defer)
+                                 defer_join=defer, rows=None if ctx.out_rows is None else ctx.out_rows[0],
+                                 n_rows=None if ctx.out_rows is None else ctx.out_rows[1])
         if defer is not None:
             # one callback per deferred call (idempotent): no state that an aborted backward pass could leave behind
             torch.autograd.Variable._execution_engine.queue_callback(_join_weight_gradient_streams)
-        return dh.view(B, L, D), None, None, None, None, None, None, None, None, None
+        return dh.view(B, L, D), None, None, None, None, None, None, None, None, None, None
 
 
 from ._lib import exp_env as _exp_env  # noqa: E402
@@ -178,6 +184,11 @@ _DEFER_JOIN = _exp_env("T4R_XLNET_DEFER_JOIN", "1") != "0"       # a test flips 
 _FUSED_ON = _exp_env("T4R_XLNET_FUSED", "1") != "0"
 _FUSE_FINAL = True       # module attribute (no switch): tools/ab_step.py flips it for a same-box A/B
 _FUSE_INPUT = True
+# the last layer's feed-forward block and LayerNorm-1 backward on the label rows only, where Model.forward finds that nothing
+# reads the other rows (model.last_rows_gate); module attribute (no switch): tools/ab_step.py flips it for a same-box A/B
+_LAST_ROWS = True
+# engage while n_rows <= _LAST_ROWS_MAX_FRACTION * B * L (tools/last_rows_sweep.py measures the crossover)
+_LAST_ROWS_MAX_FRACTION = 0.5
 _GEN_POS = True          # the dropped positional rows are made by the stack prologue's projection kernel
 _STACK_PROLOGUE = _exp_env("T4R_XLNET_STACK_PROLOGUE", "1") != "0" and _FUSED_ON
 _PENDING: list = []          # buffers of deferred layer backwards (kept alive until the join)
@@ -239,10 +250,14 @@ class XLNetModel(SeedMixin, nn.Module):
             self._pos_cache[key] = relative_positional_encoding(L, self.config.d_model).to(device).contiguous()
         return self._pos_cache[key]
 
-    def forward(self, inputs_embeds=None, key_len=None, **kwargs):
+    def forward(self, inputs_embeds=None, key_len=None, out_rows=None, **kwargs):
         """key_len: optional int32 [B] of valid key counts (opt-in padding mask, TransformerBlock(mask_padding=True));
-        None reproduces the reference, which passes no attention mask."""
+        None reproduces the reference, which passes no attention mask.
+        out_rows: (rows int32 [>= n] ascending and unique, n), or a callable (B, L) -> that or None -- a promise of the caller that it reads the hidden states at
+        these rows of [B L, D] only and returns a gradient that is zero elsewhere; the LAST layer then runs its row-wise half on
+        them alone and the result is zero at the other rows.  None (every direct call): every row is computed."""
         cfg = self.config
+        self.last_out_rows = None        # what the last layer of this forward ran with (tests / tools read it)
         _join_weight_gradient_streams()      # leftovers of a backward pass that raised (no-op normally)
         ops.xlnet_clear_cu_budget()          # likewise: a data-parallel backward that raised before its reducer cleared it
         B, L, D = inputs_embeds.shape
@@ -290,10 +305,17 @@ class XLNetModel(SeedMixin, nn.Module):
                 h = torch.ops.t4r_hip.xlnet_layer_infer(h.reshape(B * L, D), pos, layer.ordered_params(), B, L, cfg.n_head,
                                                         cfg.layer_norm_eps, key_len).view(B, L, D)
                 continue
+            rows_i = None
+            if (out_rows is not None and i == len(self.layer) - 1 and not infer and key_len is None and torch.is_grad_enabled()
+                    and _FUSED_ON and ops.xlnet_fused_supported(D) and ops.xlnet_attn_block_supported(L, D, cfg.n_head)):
+                r = out_rows(B, L) if callable(out_rows) else out_rows        # Model.forward: decided (and the label count awaited) here
+                if r is not None:
+                    rows_i = (r[0], int(r[1]))
+                    self.last_out_rows = rows_i[1]
             h = _XLNetLayerFn.apply(h, layer.rel_attn.q, layer, pos, cfg.n_head, cfg.layer_norm_eps,
                                     (p, self.seed, offset, i | (ops.LAYER_FUSE_FINAL if fuse_final and i == len(self.layer) - 1 else 0)
                                      | (ops.LAYER_FUSE_INPUT if fuse_in and i == 0 else 0)),
-                                    key_len, pos_b, None if ws_all is None else ws_all[i])
+                                    key_len, pos_b, None if ws_all is None else ws_all[i], rows_i)
         if p > 0 and not fuse_final:
             h = _DropoutFn.apply(h, p, self.seed, ops.dropout_ctr_hi(offset, 255, ops.SITE_FINAL))
         return (h,)
@@ -355,8 +377,11 @@ class TransformerBlock(nn.Module):
         return cls(reg[transformer].build(d_model=d_model, n_head=n_head, n_layer=n_layer,
                                           total_seq_length=total_seq_length), masking)
 
-    def forward(self, inputs_embeds, **kwargs):
+    def forward(self, inputs_embeds, out_rows=None, **kwargs):
         # the reference passes inputs_embeds only for XLNet + MLM/CLM (block/transformer.py:183-199)
+        # out_rows: XLNetModel.forward (Model.forward sets it; never with mask_padding, never for the GPT-2 / BERT bodies)
+        if out_rows is not None and not self.mask_padding and isinstance(self.transformer, XLNetModel):
+            return self.transformer(inputs_embeds=inputs_embeds, out_rows=out_rows)[0]
         if self.mask_padding:
             ids = getattr(self.masking, "last_item_ids", None) if self.masking is not None else None
             if ids is None:
