@@ -12,6 +12,9 @@ timed here for the record (bench.py reports configs[1]):
 
     python tools/c45_bench.py c4 [steps]
     python tools/c45_bench.py c5 [steps] [precision] [batch]
+
+"rowsparse" anywhere on the command line (c4 only: its head is sampled, so every table's gradient is row-sparse) steps the tables
+with optim.RowSparseAdam and the rest with FusedAdam over one bucket, instead of FusedAdam over both buckets.
 """
 import json
 import os
@@ -24,6 +27,8 @@ import torch
 import transformers4rec_amd as tr
 from transformers4rec_amd import ops
 
+ROWSPARSE = "rowsparse" in sys.argv
+sys.argv = [a for a in sys.argv if a != "rowsparse"]
 dev = torch.device("cuda", 0)
 which = sys.argv[1] if len(sys.argv) > 1 else "c4"
 n = int(sys.argv[2]) if len(sys.argv) > 2 else (20 if which == "c4" else 3)
@@ -45,8 +50,23 @@ with torch.device(dev):          # parameters are created in HBM (a 20 GB table 
         task = tr.NextItemPredictionTask(weight_tying=True)      # head_mode "auto" -> fused at this size
     model = cfg.to_torch_model(inputs, task)
 ops.set_precision(prec)
-dense, tables = tr.flatten_model(model)
-opt = tr.FusedAdam([dense, tables], lr=1e-3)
+if ROWSPARSE:
+    from transformers4rec_amd import optim
+
+    sparse = dict(optim.row_sparse_tables(model))
+    if which != "c4" or not sparse:
+        raise SystemExit("rowsparse: only c4 (sampled head) has tables a lazy step may own")
+    dense = optim.FlatParams((n_, p_) for n_, p_ in model.named_parameters() if n_ not in sparse)
+    opt_d, opt_s = tr.FusedAdam([dense], lr=1e-3), optim.RowSparseAdam(sparse.values(), lr=1e-3).attach()
+
+    class opt:        # the pair behind the one name the step below uses
+        @staticmethod
+        def step():
+            opt_d.step()
+            opt_s.step()
+else:
+    dense, tables = tr.flatten_model(model)
+    opt = tr.FusedAdam([dense, tables], lr=1e-3)
 model.train()
 batches = [tr.random_data_from_schema(schema, B, L, seed=i, device=dev) for i in range(2)]
 
@@ -69,7 +89,7 @@ for i in range(n):
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
 N = n_lab // n
-res = {"config": which, "V": V, "d_model": D, "layers": NL, "seq_len": L, "batch": B, "precision": ops.get_precision(),
+res = {"config": which, "optimizer": "FusedAdam + RowSparseAdam" if ROWSPARSE else "FusedAdam", "V": V, "d_model": D, "layers": NL, "seq_len": L, "batch": B, "precision": ops.get_precision(),
        "head_mode": task.resolve_head_mode(N, V + 1) if which == "c5" else "sampled",
        "steps": n, "ms_per_step": round(1e3 * dt / n, 2), "sessions_per_s": round(B * n / dt, 1),
        "label_rows_per_step": N, "loss": round(float(out["loss"].detach()), 4),

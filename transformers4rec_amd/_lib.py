@@ -17,6 +17,7 @@ OPTIM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_opt
 PRETRAINED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_pretrained.h")
 ATTN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_attn.h")
 ROWS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_rows.h")
+ROWADAM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_rowadam.h")
 
 _P, _I, _L, _F, _Q = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_ulonglong
 _C = {"p": _P, "i": _I, "l": _L, "f": _F, "Q": _Q}
@@ -213,6 +214,14 @@ _SIGS_ROWS = {
     "t4r_xlnet_layer_bwd_rows": ("i", _SIGS["t4r_xlnet_layer_bwd"][1] + "pi"),
 }
 
+# the eighth header, include/t4r_hip_rowadam.h (tests/test_row_adam_cpu.py checks this table against it): the row-sparse Adam
+# step; the arguments are stream, param, exp_avg, exp_avg_sq, V, D, keys, perm, grad_rows, ld_grad, n, step, the six floats
+# (lr, beta1, beta2, eps, weight_decay | decoupled | grad_scale), ws, ws_bytes
+_SIGS_ROWADAM = {
+    "t4r_row_adam_ws_bytes": ("l", "li"),
+    "t4r_row_adam_step": ("i", "pppp" + "li" + "ppp" + "lli" + "fffff" + "if" + "pl"),
+}
+
 _lib = None
 
 
@@ -261,6 +270,11 @@ def rows_header_symbols():
     return _declared(ROWS_HEADER_PATH)
 
 
+def rowadam_header_symbols():
+    """Function names declared in include/t4r_hip_rowadam.h."""
+    return _declared(ROWADAM_HEADER_PATH)
+
+
 def load():
     """Loads the library and sets ctypes prototypes.  Raises if it is not built."""
     global _lib
@@ -272,7 +286,7 @@ def load():
             "(run `python -m transformers4rec_amd.build`). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (ret, args) in (list(_SIGS.items()) + list(_SIGS_SAMPLING.items()) + list(_SIGS_FILTER.items()) + list(_SIGS_OPTIM.items())
-                              + list(_SIGS_PRETRAINED.items()) + list(_SIGS_ATTN.items()) + list(_SIGS_ROWS.items())):
+                              + list(_SIGS_PRETRAINED.items()) + list(_SIGS_ATTN.items()) + list(_SIGS_ROWS.items()) + list(_SIGS_ROWADAM.items())):
         fn = getattr(lib, name)
         fn.restype = ctypes.c_char_p if ret == "s" else (None if ret == "v" else _C[ret])
         fn.argtypes = [_C[a] for a in args]

@@ -35,6 +35,20 @@ def _hip_apply(d_table, ids, rows, padding_idx):
     ops.scatter_rows_sorted(d_table, ids, rows, padding_idx)
 
 
+def lookup_rows(ids, grad_rows, col, dim, ids_div):
+    """-> [n, dim] gradient rows of one feature's n = ids.numel() lookups, out of the block's grad_rows [n * ids_div, W]: the
+    columns [col, col + dim), summed over the ids_div positions a per-session id was broadcast to.  Shared by the sinks
+    (SparseRowExchange.add, optim.RowSparseAdam.add)."""
+    from . import ops
+
+    W = grad_rows.shape[-1]
+    if ids_div > 1:
+        return ops.seq_sum_cols(grad_rows, col, dim, ids.numel(), ids_div)
+    if W != dim:
+        return ops.copy_cols_out(grad_rows, col, dim)
+    return grad_rows
+
+
 class SparseRowExchange:
     """Sink for row-sparse table gradients.  `attach(param)` routes the HIP backward of that table
     (features._table_scatter, the sampled head) here instead of into `param.grad`; `exchange()` --
@@ -68,17 +82,7 @@ class SparseRowExchange:
     def add(self, tab, ids, grad_rows, col, dim, ids_div, padding_idx):
         """lookup scatter of one feature: grad_rows [n * ids_div, W]; the rows of this feature are the
         columns [col, col + dim), summed over the ids_div positions a per-session id was broadcast to"""
-        from . import ops
-
-        W = grad_rows.shape[-1]
-        n = ids.numel()
-        if ids_div > 1:
-            rows = ops.seq_sum_cols(grad_rows, col, dim, n, ids_div)
-        elif W != dim:
-            rows = ops.copy_cols_out(grad_rows, col, dim)
-        else:
-            rows = grad_rows
-        self.add_rows(tab, ids.reshape(-1), rows, padding_idx)
+        self.add_rows(tab, ids.reshape(-1), lookup_rows(ids, grad_rows, col, dim, ids_div), padding_idx)
 
     def add_rows(self, tab, ids, rows, padding_idx=-1):
         self._pending.append((tab, ids.contiguous(), rows.contiguous(), int(padding_idx)))

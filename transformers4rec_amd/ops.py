@@ -1557,6 +1557,37 @@ def adamw_step_(param, grad, exp_avg, exp_avg_sq, step, lr=1e-3, betas=(0.9, 0.9
     return n
 
 
+# ---- include/t4r_hip_rowadam.h: the row-sparse (lazy) Adam step of a table (optim.RowSparseAdam drives it)
+def row_adam_step_(param, exp_avg, exp_avg_sq, ids, rows, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                   decoupled=False, grad_scale=1.0, padding_idx=-1):
+    """One Adam / AdamW step of the rows of `param` [V, D] that `ids` names, with the gradient of row r = the sum of rows[i]
+    over ids[i] == r in lookup order (the bits of scatter_rows_sorted into a zeroed buffer); every other row of param and of
+    the two moments is neither read nor written.  ids int64 [n]; rows fp32 [n, D], unit inner stride, any row pitch >= D;
+    ids equal to padding_idx or outside [0, V) carry nothing."""
+    for t, name in ((param, "param"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq"), (ids, "ids"), (rows, "rows")):
+        if not t.is_cuda:
+            raise _lib.T4RHipError(f"row_adam_step_: {name} must live on the GPU (got {t.device}); there is no CPU path")
+    if param.dim() != 2 or exp_avg.shape != param.shape or exp_avg_sq.shape != param.shape:
+        raise ValueError("row_adam_step_: param, exp_avg and exp_avg_sq are [V, D] tensors of one shape")
+    V, D = param.shape
+    ids = ids.reshape(-1)
+    n = ids.numel()
+    if rows.dim() != 2 or rows.shape != (n, D) or rows.dtype != torch.float32 or (D > 1 and rows.stride(1) != 1):
+        raise ValueError(f"row_adam_step_: rows must be fp32 [{n}, {D}] with unit inner stride")
+    if n == 0:
+        return
+    ld = _row_pitch(rows, D)
+    if ld < D:
+        raise ValueError("row_adam_step_: the row pitch of rows must be at least D")
+    keys, perm = sort_ids(ids, V, padding_idx)
+    nb = _lib.load().t4r_row_adam_ws_bytes(n, D)
+    ws = torch.empty(max(nb, 1), device=param.device, dtype=torch.uint8)
+    call("t4r_row_adam_step", _stream(), _chk(param, torch.float32, "param"), _chk(exp_avg, torch.float32, "exp_avg"),
+         _chk(exp_avg_sq, torch.float32, "exp_avg_sq"), V, D, keys.data_ptr(), perm.data_ptr(), rows.data_ptr(), ld, n,
+         int(step), float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(bool(decoupled)),
+         float(grad_scale), ws.data_ptr(), nb)
+
+
 # ------------------------------------------------------------------------------------ pretrained-embedding features
 # (include/t4r_hip_pretrained.h, csrc/pretrained_proj.hip)
 def _pretrained_image(what, image, ids, E):

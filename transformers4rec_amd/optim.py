@@ -211,3 +211,155 @@ class FusedAdam:
         self._join()
         for f in self.flats:
             f.grad.zero_()
+
+
+def _is_table(name, p):
+    return ((".embedding_tables." in name and name.endswith(".weight") and p.ndim == 2 and "continuous_module" not in name)
+            or name.endswith("output_layer"))
+
+
+def row_sparse_tables(model):
+    """-> [(name, param)]: the tables of `model` (flatten_model's "tables" bucket) whose whole gradient arrives as (ids, rows)
+    and which RowSparseAdam may therefore step.  With a sampled-softmax head that is every table.  A full-softmax head writes
+    a dense d W into its weight's .grad -- the tied item table, or an untied output_layer -- and that one is left out."""
+    task = model.prediction_task
+    dense_w = None
+    if not getattr(task, "sampled_softmax", False):
+        dense_w = task.pre.module.output_weights
+    out, seen = [], set()
+    for name, p in model.named_parameters():
+        if id(p) in seen or not p.requires_grad or not _is_table(name, p) or p is dense_w:
+            continue
+        seen.add(id(p))
+        out.append((name, p))
+    return out
+
+
+class RowSparseAdam:
+    """torch.optim.SparseAdam semantics for embedding tables whose gradient arrives as (ids, rows): one step reads and writes
+    only the rows that have a gradient (csrc/row_adam.hip), so neither a dense [V, D] gradient nor a pass over the table exists.
+
+    "Lazy": a row without a gradient keeps its parameters and its moments -- they do not decay -- while the bias corrections use
+    the global step count; weight_decay (coupled, or decoupled with decoupled_weight_decay=True) applies to touched rows only.
+    A dense Adam step agrees with it exactly while the untouched rows' moments are zero (the first step; always for rows never
+    seen), and moves a row seen earlier a little further on its decaying first moment where this one leaves it alone.
+
+    The object is the sink of its tables: attach() routes the HIP backward of every table (features._table_scatter, the sampled
+    head) here instead of into .grad.  A table that also receives a DENSE gradient -- the weight of a full-softmax head -- cannot
+    be stepped lazily; row_sparse_tables(model) names the ones that can.  The recipe:
+
+        sparse = dict(optim.row_sparse_tables(model))
+        dense = optim.FlatParams((n, p) for n, p in model.named_parameters() if n not in sparse)
+        opt_d = optim.FusedAdam([dense], lr)
+        opt_s = optim.RowSparseAdam(sparse.values(), lr).attach()
+        ... loss.backward(); opt_d.step(); opt_s.step()
+
+    params: 2-D fp32 contiguous parameters on the GPU (views into a FlatParams buffer are fine).  No gradient clipping:
+    max_grad_norm over dense and row-sparse gradients together is out of scope; clip the dense bucket with FusedAdam alone or
+    not at all.  Several entries for one table in one step (a tied sampled head's rows and the lookups' rows) are summed as
+    ONE list in arrival order; the dense route sums each scatter on its own and adds the sums, so a row that several entries
+    name can differ from it in the last bits of its gradient."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled_weight_decay=False):
+        self.params = []
+        for p in params:
+            if any(p is q for q in self.params):
+                continue
+            if p.ndim != 2 or p.dtype != torch.float32 or not p.is_contiguous():
+                raise ValueError("RowSparseAdam: every parameter is a 2-D fp32 contiguous table")
+            self.params.append(p)
+        if not self.params:
+            raise ValueError("no tables to step")
+        self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
+        self.decoupled_weight_decay = bool(decoupled_weight_decay)
+        self.base_lr, self._schedule = lr, None
+        self.state = [(torch.zeros_like(p.data), torch.zeros_like(p.data)) for p in self.params]
+        self.step_count = 0
+        self._pending = []
+
+    # ---- the sink (distributed.SparseRowExchange has the same three)
+    def attach(self):
+        for p in self.params:
+            sink = getattr(p, "_t4r_sparse_sink", None)
+            if sink is not None and sink is not self:
+                raise RuntimeError("RowSparseAdam.attach: the table already has a row-sparse sink; detach that one first (for data "
+                                   "parallel, keep the SparseRowExchange attached and hand it this optimizer's add_rows as apply_fn)")
+        for p in self.params:
+            p._t4r_sparse_sink = self
+        return self
+
+    def detach(self):
+        for p in self.params:
+            if getattr(p, "_t4r_sparse_sink", None) is self:
+                del p._t4r_sparse_sink
+        return self
+
+    def add(self, tab, ids, grad_rows, col, dim, ids_div, padding_idx):
+        """lookup scatter of one feature (called from the backward pass): as SparseRowExchange.add"""
+        from .distributed import lookup_rows
+
+        self.add_rows(tab, ids.reshape(-1), lookup_rows(ids, grad_rows, col, dim, ids_div), padding_idx)
+
+    def add_rows(self, tab, ids, rows, padding_idx=-1):
+        if not any(tab is p for p in self.params):
+            raise ValueError("RowSparseAdam.add_rows: not a table of this optimizer")
+        self._pending.append((tab, ids.reshape(-1), rows, int(padding_idx)))
+
+    # ---- the optimizer
+    def set_schedule(self, f):
+        """as FusedAdam.set_schedule"""
+        self._schedule = f
+        return self
+
+    def step(self, grad_scale=1.0):
+        FusedAdam._join()
+        self.step_count += 1
+        if self._schedule is not None:
+            self.lr = self.base_lr * self._schedule(self.step_count - 1)
+        pending, self._pending = self._pending, []
+        for p, (m, v) in zip(self.params, self.state):
+            mine = [(ids, rows, pad) for tab, ids, rows, pad in pending if tab is p]
+            if not mine:
+                continue
+            if len(mine) == 1:
+                ids, rows, pad = mine[0]
+            else:
+                # one list in arrival order.  Entries that disagree on the padding id: each one's padding lookups get the
+                # out-of-range id V, which carries nothing
+                pads = {pad for _, _, pad in mine}
+                pad = pads.pop() if len(pads) == 1 else -1
+                V = p.shape[0]
+                ids = torch.cat([i if (q == pad or q < 0) else torch.where(i == q, torch.full_like(i, V), i) for i, _, q in mine])
+                rows = torch.cat([r for _, r, _ in mine])
+            ops.row_adam_step_(p.data, m, v, ids, rows, self.step_count, self.lr, self.betas, self.eps, self.weight_decay,
+                               self.decoupled_weight_decay, grad_scale, padding_idx=pad)
+            # the kernel wrote the table behind torch's version counter: a maximum FusedAdam left for the head is stale now
+            if hasattr(p, "_t4r_w_amax"):
+                del p._t4r_w_amax
+
+    def zero_grad(self):
+        """drops the rows collected since the last step"""
+        FusedAdam._join()
+        self._pending = []
+
+    def state_dict(self):
+        """moments per table (copies), step count and hyper-parameters; a schedule is code and is set again by the caller"""
+        return {"step_count": self.step_count,
+                "state": [{"exp_avg": m.detach().clone(), "exp_avg_sq": v.detach().clone()} for m, v in self.state],
+                "hyper": {"lr": self.base_lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay,
+                          "decoupled_weight_decay": self.decoupled_weight_decay}}
+
+    def load_state_dict(self, sd):
+        if len(sd["state"]) != len(self.state):
+            raise ValueError(f"state_dict has {len(sd['state'])} tables, the optimizer {len(self.state)}")
+        for (m, v), s in zip(self.state, sd["state"]):
+            if s["exp_avg"].shape != m.shape or s["exp_avg_sq"].shape != v.shape:
+                raise ValueError("state_dict table shapes do not match the optimizer's")
+        for (m, v), s in zip(self.state, sd["state"]):
+            m.copy_(s["exp_avg"])
+            v.copy_(s["exp_avg_sq"])
+        h = sd["hyper"]
+        self.step_count = int(sd["step_count"])
+        self.base_lr = self.lr = h["lr"]
+        self.betas, self.eps, self.weight_decay = tuple(h["betas"]), h["eps"], h["weight_decay"]
+        self.decoupled_weight_decay = bool(h["decoupled_weight_decay"])
