@@ -18,6 +18,7 @@ PRETRAINED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hi
 ATTN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_attn.h")
 ROWS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_rows.h")
 ROWADAM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_rowadam.h")
+CONTPROJ_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_contproj.h")
 
 _P, _I, _L, _F, _Q = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_ulonglong
 _C = {"p": _P, "i": _I, "l": _L, "f": _F, "Q": _Q}
@@ -222,6 +223,17 @@ _SIGS_ROWADAM = {
     "t4r_row_adam_step": ("i", "pppp" + "li" + "ppp" + "lli" + "fffff" + "if" + "pl"),
 }
 
+# the ninth header, include/t4r_hip_contproj.h (tests/test_cont_proj_cpu.py checks this table against it): the first layer of
+# `continuous_projection`; the common arguments are xs (host array of C device pointers), per_session (host ints), ntok, L, C, P,
+# W, b
+_CP = "pp" + "liii" + "pp"
+_SIGS_CONTPROJ = {
+    "t4r_cont_proj_supported": ("i", "ii"),
+    "t4r_cont_proj_bwd_ws_floats": ("l", "lii"),
+    "t4r_cont_proj_fwd": ("i", "p" + _CP + "p"),
+    "t4r_cont_proj_bwd": ("i", "p" + "pli" + _CP + "pppp"),
+}
+
 _lib = None
 
 
@@ -275,6 +287,11 @@ def rowadam_header_symbols():
     return _declared(ROWADAM_HEADER_PATH)
 
 
+def contproj_header_symbols():
+    """Function names declared in include/t4r_hip_contproj.h."""
+    return _declared(CONTPROJ_HEADER_PATH)
+
+
 def load():
     """Loads the library and sets ctypes prototypes.  Raises if it is not built."""
     global _lib
@@ -286,7 +303,8 @@ def load():
             "(run `python -m transformers4rec_amd.build`). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (ret, args) in (list(_SIGS.items()) + list(_SIGS_SAMPLING.items()) + list(_SIGS_FILTER.items()) + list(_SIGS_OPTIM.items())
-                              + list(_SIGS_PRETRAINED.items()) + list(_SIGS_ATTN.items()) + list(_SIGS_ROWS.items()) + list(_SIGS_ROWADAM.items())):
+                              + list(_SIGS_PRETRAINED.items()) + list(_SIGS_ATTN.items()) + list(_SIGS_ROWS.items()) + list(_SIGS_ROWADAM.items())
+                              + list(_SIGS_CONTPROJ.items())):
         fn = getattr(lib, name)
         fn.restype = ctypes.c_char_p if ret == "s" else (None if ret == "v" else _C[ret])
         fn.argtypes = [_C[a] for a in args]

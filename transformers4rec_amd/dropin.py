@@ -210,6 +210,38 @@ def shadow_pretrained(rp):
                                          normalizer="layer-norm" if post else None)
 
 
+def shadow_continuous_projection(rk):
+    """HIP-side ContinuousProjection of the reference's SequentialBlock(ContinuousFeatures, MLPBlock(dims), AsTabular)
+    (features/tabular.py:90-117, built); parameters are tied by name by the caller"""
+    members = list(rk)
+    if len(members) != 3 or _cls(members[2]) != "AsTabular":
+        raise NotImplementedError("dropin: a continuous SequentialBlock other than continuous_projection's (ContinuousFeatures, "
+                                  "MLPBlock, AsTabular) is off the HIP hot path")
+    rc, mlp = members[0], members[1]
+    if _cls(rc) != "ContinuousFeatures":
+        raise NotImplementedError(f"dropin: continuous_projection over {_cls(rc)} is off the HIP hot path: its first member "
+                                  "must be ContinuousFeatures")
+    if _cls(mlp) == "MLPBlock":
+        raise NotImplementedError("dropin: the reference continuous_projection is not built yet (no Linear layers)")
+    if _transformations(getattr(rc, "post", None)):
+        raise NotImplementedError("dropin: post transformations under continuous_projection are off the HIP hot path")
+    dims = []
+    for dense in mlp:
+        parts = list(dense)
+        lin = parts[0] if parts else None
+        if lin is None or _cls(lin) != "Linear":
+            raise NotImplementedError(f"dropin: continuous_projection layer {_cls(dense)} does not start with a Linear")
+        if lin.bias is None:
+            raise NotImplementedError("dropin: a continuous_projection MLP without bias (use_bias=False) is off the HIP hot path")
+        rest = [_cls(m) for m in parts[1:]]
+        if rest != ["ReLU"]:
+            raise NotImplementedError(f"dropin: continuous_projection layers are Linear(bias=True) + ReLU on the HIP hot path; "
+                                      f"the reference MLP has {['Linear'] + rest} (other activation, normalization or dropout)")
+        dims.append(int(lin.weight.shape[0]))
+    names = list(rc.filter_features.to_include) if hasattr(rc, "filter_features") else list(rc.names)
+    return F.ContinuousProjection(F.ContinuousFeatures(names, pre=_map_pre(getattr(rc, "pre", None))), dims)
+
+
 def shadow_features(ref):
     """HIP-side TabularSequenceFeatures sharing every parameter with the reference module `ref`."""
     merge = ref.to_merge
@@ -243,9 +275,10 @@ def shadow_features(ref):
                 names = list(rk.filter_features.to_include) if hasattr(rk, "filter_features") else list(rk.names)
                 cont = F.ContinuousFeatures(names, pre=_map_pre(getattr(rk, "pre", None)),
                                             post=_map_post(getattr(rk, "post", None)))
+            elif kind == "SequentialBlock":
+                cont = shadow_continuous_projection(rk)
             else:
-                raise NotImplementedError(f"dropin: continuous module {kind} (e.g. continuous_projection) is off "
-                                          "the HIP hot path")
+                raise NotImplementedError(f"dropin: continuous module {kind} is off the HIP hot path")
         pt = None
         if "pretrained_embedding_module" in merge and not _empty(merge["pretrained_embedding_module"]):
             pt = shadow_pretrained(merge["pretrained_embedding_module"])

@@ -350,6 +350,127 @@ class ContinuousFeatures(nn.Module):
         self.post = None
 
 
+class _AsTabular(nn.Module):
+    """the parameter-free marker that names a block's output (reference tabular/base.py: AsTabular)"""
+
+    def __init__(self, output_name):
+        super().__init__()
+        self.output_name = output_name
+
+    def extra_repr(self):
+        return repr(self.output_name)
+
+
+CONTINUOUS_PROJECTION = "continuous_projection"
+
+
+class ContinuousProjection(nn.Sequential):
+    """The continuous module after `project_continuous_features(dims)` (reference features/tabular.py:90-117,
+    features/sequence.py:271-284): SequentialBlock(ContinuousFeatures(aggregation="concat"), MLPBlock(dims),
+    AsTabular("continuous_projection")).  The C continuous columns, in sorted-name order, go through ReLU(Linear) layers
+    (block/mlp.py:68-143: no dropout, no normalisation) and come out as ONE feature, `continuous_projection`, of width
+    dims[-1].  Members and state-dict names are the reference's: [0] the parameter-free ContinuousFeatures, [1] a sequence of
+    one-Linear sequences (`1.<i>.0.{weight,bias}`, torch.nn.Linear's default init), [2] the marker.  The first layer runs in
+    csrc/cont_proj.hip from the separate column tensors, the others on the general GEMM."""
+
+    def __init__(self, continuous, dims):
+        if not isinstance(continuous, ContinuousFeatures):
+            raise NotImplementedError("continuous_projection projects plain ContinuousFeatures; soft embeddings fed into the "
+                                      "projection (continuous_soft_embeddings=True) are off the hot path")
+        if not continuous.names:
+            raise ValueError("continuous_projection needs at least one continuous column")
+        if continuous._post is not None:
+            raise NotImplementedError("post transformations on a continuous module with continuous_projection are off the hot "
+                                      "path")
+        dims = [dims] if isinstance(dims, int) else list(dims)
+        if not dims or any(not isinstance(d, int) or d < 1 for d in dims):
+            raise ValueError(f"continuous_projection takes an int or a non-empty list of positive ints, got {dims!r}")
+        C = len(continuous.names)
+        if not 1 <= C <= 64 or not 1 <= dims[0] <= 1024:
+            raise NotImplementedError(f"continuous_projection: {C} columns into {dims[0]} units is outside what the first-layer "
+                                      "kernel takes (1..64 columns, 1..1024 units)")
+        sizes = [C] + dims
+        mlp = nn.Sequential(*[nn.Sequential(_Linear(i, o)) for i, o in zip(sizes[:-1], sizes[1:])])
+        super().__init__(continuous, mlp, _AsTabular(CONTINUOUS_PROJECTION))
+        self.dims = dims
+
+    @property
+    def names(self):
+        """the raw continuous columns in the order the first layer's weight columns follow"""
+        return sorted(self[0].names)
+
+    @property
+    def layers(self):
+        return [dense[0] for dense in self[1]]
+
+    @property
+    def output_dim(self):
+        return self.dims[-1]
+
+    @property
+    def _pre(self):
+        return self[0]._pre
+
+    @property
+    def embedding_tables(self):
+        return self[0].embedding_tables
+
+
+def _cont_proj_fwd(cont, inputs, B, L):
+    """the rows [B * L, dims[-1]] of the `continuous_projection` feature -> (rows, record for _cont_proj_bwd)"""
+    xs, flags = [], []
+    for n in cont.names:
+        x = inputs[n].contiguous().float()
+        if x.ndim == 1 and x.shape[0] == B:
+            flags.append(True)          # a per-session column, broadcast over L (reference: tabular/base.py:53-63)
+        elif tuple(x.shape) == (B, L):
+            flags.append(False)
+        else:
+            raise ValueError(f"continuous feature {n!r}: expected [{B}, {L}] or [{B}], got {tuple(x.shape)}")
+        xs.append(x)
+    layers = cont.layers
+    acts = [ops.cont_proj_fwd(xs, flags, layers[0].weight.detach(), layers[0].bias.detach(), T=B * L)]
+    for lin in layers[1:]:
+        acts.append(ops.gemm(acts[-1], lin.weight.detach(), False, True, bias=lin.bias.detach(), epilogue=ops.EPI_BIAS_RELU))
+    return acts[-1], dict(xs=xs, flags=flags, acts=acts)
+
+
+def _cont_proj_bwd(cont, rec, d2, col):
+    """parameter gradients of the projection MLP from columns [col, col + dims[-1]) of the aggregate's gradient d2 [B * L, W];
+    d2 is read only"""
+    layers, acts = cont.layers, rec["acts"]
+    g, gcol = d2, col
+    for i in range(len(layers) - 1, 0, -1):
+        lin, y = layers[i], acts[i]
+        N = lin.out_features
+        if g.shape[1] != N:
+            g = dg = ops.copy_cols_out(g, gcol, N)
+        else:
+            dg = torch.empty_like(g)    # d2 belongs to every feature of the aggregation
+        db = _grad_buf(lin.bias)
+        if N % 4 == 0:
+            ops.act_bwd_bias(g, y, db, 1, out=dg)
+        else:
+            # the ReLU mask is element-wise: the kernel takes the buffers as rows of four (zero-padded copies where tokens * width
+            # is no multiple of 4); the column sum as a product with ones
+            n = g.numel()
+            if n % 4 == 0:
+                ops.act_bwd_bias(g.view(-1, 4), y.view(-1, 4), None, 1, out=dg.view(-1, 4))
+            else:
+                flat = torch.zeros((3, (n + 3) // 4, 4), device=g.device, dtype=torch.float32)
+                flat[0].view(-1)[:n] = g.reshape(-1)
+                flat[1].view(-1)[:n] = y.reshape(-1)
+                ops.act_bwd_bias(flat[0], flat[1], None, 1, out=flat[2])
+                dg = flat[2].view(-1)[:n].view(g.shape)
+            ones = torch.ones((dg.shape[0], 1), device=dg.device, dtype=torch.float32)
+            ops.gemm(dg, ones, True, False, accumulate=True, out=db.view(N, 1))
+        ops.gemm_wgrad(dg, acts[i - 1], _grad_buf(lin.weight))
+        g, gcol = ops.gemm(dg, lin.weight.detach(), False, False), 0
+    lin = layers[0]
+    ops.cont_proj_bwd_(g, gcol, rec["xs"], rec["flags"], lin.weight.detach(), lin.bias.detach(), _grad_buf(lin.weight),
+                       _grad_buf(lin.bias))
+
+
 class PretrainedEmbeddingFeatures(nn.Module):
     """Drop-in for tr.PretrainedEmbeddingFeatures (features/embedding.py:599-740): frozen text / image vectors of the items
     (or of the session), optionally projected (`projection.<feature>`, torch.nn.Linear with its default init) and normalised
@@ -627,6 +748,7 @@ class _SeqFeaturesFn(torch.autograd.Function):
             mask_mode = masking.apply_mode(training, testing)
             L_out = mask.shape[1]
         feats, soft_saved, post_saved, pt_saved = [], {}, {}, {}
+        ctx.cp_saved = None
         step = mod._post_step
         for fidx, name in enumerate(names):
             col, dim = mod._cols[name], mod._dims[name]
@@ -652,6 +774,9 @@ class _SeqFeaturesFn(torch.autograd.Function):
                 f, pt_saved[name] = _pretrained_fwd(mod, pt, name, inputs, B, L, col, dim, mod._err_flag(item_ids.device),
                                                     save=ctx.needs_input_grad[0])
                 feats.append(f)
+            elif isinstance(cont, ContinuousProjection):
+                rows, ctx.cp_saved = _cont_proj_fwd(cont, inputs, B, L)
+                feats.append(dict(kind=1, input=rows, table=None, dim=dim, col=col))
             elif isinstance(cont, ContinuousFeatures):
                 x = inputs[name].contiguous().float().view(B * L, 1)
                 if cont._post is not None:
@@ -737,6 +862,8 @@ class _SeqFeaturesFn(torch.autograd.Function):
             def again(n):   # the feature as the forward aggregated it (post-transformed rows are recomputed)
                 if n in ctx.pt_saved:
                     return dict(ctx.pt_saved[n]["feat"], dim=W, col=0)
+                if n == CONTINUOUS_PROJECTION and ctx.cp_saved is not None:
+                    return dict(kind=1, input=ctx.cp_saved["acts"][-1], table=None, dim=W, col=0)
                 ids_n = ctx.inputs[n].contiguous()
                 tabn = cat.embedding_tables[n].weight.detach()
                 f = dict(kind=2 if ids_n.ndim == 1 else 0, input=ids_n, table=tabn, dim=W, col=0, rows=tabn.shape[0])
@@ -775,6 +902,9 @@ class _SeqFeaturesFn(torch.autograd.Function):
             elif name in ctx.pt_saved:
                 src = d_other if agg == "element-wise-sum-item-multi" else d
                 _pretrained_bwd(ctx.pt_saved[name], src.view(B * L, -1), col, dim, B, L)
+            elif isinstance(cont, ContinuousProjection):
+                src = d_other if agg == "element-wise-sum-item-multi" else d
+                _cont_proj_bwd(cont, ctx.cp_saved, src.view(B * L, -1), col)
             elif isinstance(cont, ContinuousFeatures):
                 continue    # no parameters behind a pass-through column
             else:
@@ -816,8 +946,24 @@ class TabularSequenceFeatures(nn.Module):
             mods["pretrained_embedding_module"] = pretrained_embedding_module
         self.to_merge = nn.ModuleDict(mods)
         self._aggregation = aggregation
+        self.projection_module = None
+        self._layout()
+        if projection_dim:
+            # MLPBlock([d_output]) -> SequentialBlock(DenseBlock(Linear, ReLU)) (block/mlp.py:68-143)
+            self.projection_module = nn.Sequential(nn.Sequential(_Linear(self._agg_width, projection_dim)))
+        self._masking = None
+        self.set_masking(masking)
+        self._err = None
+        self._post_step = 0     # Philox stream position of the post-dropout / swap-noise draws
+
+    def _layout(self):
+        """names, widths and columns of the features the aggregation sees, from the modules in `to_merge`"""
+        categorical_module, continuous_module = self.categorical_module, self.continuous_module
+        pretrained_embedding_module, aggregation = self.pretrained_module, self._aggregation
         dims = {n: t.embedding_dim for n, t in categorical_module.embedding_tables.items()}
-        if isinstance(continuous_module, ContinuousFeatures):
+        if isinstance(continuous_module, ContinuousProjection):
+            dims[CONTINUOUS_PROJECTION] = continuous_module.output_dim
+        elif isinstance(continuous_module, ContinuousFeatures):
             dims.update({n: 1 for n in continuous_module.names})
         elif continuous_module is not None:
             dims.update({n: s.embedding_table.embedding_dim for n, s in continuous_module.embedding_tables.items()})
@@ -839,14 +985,6 @@ class TabularSequenceFeatures(nn.Module):
             if len(set(dims.values())) != 1:
                 raise ValueError(f"All features must have the same dimension for element-wise aggregation: {dims}")
             self._cols, self._agg_width = {n: 0 for n in dims}, next(iter(dims.values()))
-        self.projection_module = None
-        if projection_dim:
-            # MLPBlock([d_output]) -> SequentialBlock(DenseBlock(Linear, ReLU)) (block/mlp.py:68-143)
-            self.projection_module = nn.Sequential(nn.Sequential(_Linear(self._agg_width, projection_dim)))
-        self._masking = None
-        self.set_masking(masking)
-        self._err = None
-        self._post_step = 0     # Philox stream position of the post-dropout / swap-noise draws
 
     # ------------------------------------------------------------------ reference attribute contract
     @property
@@ -908,8 +1046,12 @@ class TabularSequenceFeatures(nn.Module):
                     normalizer=None, pretrained_input_dims=None, **kwargs):
         """Same keyword surface as the reference (features/sequence.py:140-229,
         features/embedding.py:103-221, :313-410) for the arguments the hot path uses."""
-        if projection is not None or continuous_projection is not None:
-            raise NotImplementedError("only d_output (ReLU MLP) projection is on the hot path")
+        if projection is not None:
+            raise NotImplementedError("projection (a custom block): only d_output (ReLU MLP) and continuous_projection are on "
+                                      "the hot path")
+        if continuous_projection is not None and continuous_soft_embeddings:
+            raise NotImplementedError("continuous_projection with continuous_soft_embeddings=True (soft embeddings fed into the "
+                                      "projection) is off the hot path")
         cat_schema = schema.select_by_tag(list(categorical_tags))
         cards = categorical_cardinalities(cat_schema)
         if not cards:
@@ -941,6 +1083,10 @@ class TabularSequenceFeatures(nn.Module):
             cont = SoftEmbeddingFeatures(
                 {n: (sc.get(n, soft_embedding_cardinality_default), sd.get(n, soft_embedding_dim_default))
                  for n in cont_names}, layer_norm=layer_norm, pre=pre, post=None if layer_norm else post)
+        if continuous_projection is not None:
+            if cont is None:
+                raise ValueError("continuous_projection: the schema has no continuous column to project")
+            cont = ContinuousProjection(cont, continuous_projection)
         if (masking or d_output) and not aggregation:
             aggregation = "concat"
         out = cls(cat, cont, aggregation or "concat", d_output, None, schema, max_sequence_length, pretrained_embedding_module=pt)
@@ -949,6 +1095,34 @@ class TabularSequenceFeatures(nn.Module):
             raise ValueError("For masking a categorical_module is required including an item_id.")
         out.set_masking(parse_masking(masking, hidden, **kwargs))
         return out
+
+    def project_continuous_features(self, mlp_layers_dims):
+        """features/tabular.py:90-117: puts ReLU MLP layers over the concatenated continuous columns; they then enter the
+        aggregation as the one feature `continuous_projection`.  Returns self."""
+        cont = self.continuous_module
+        if cont is None:
+            raise ValueError("project_continuous_features (continuous_projection): there is no continuous module to project")
+        if isinstance(cont, ContinuousProjection):
+            raise ValueError("project_continuous_features (continuous_projection): the continuous module is projected already")
+        width = self._agg_width
+        device = self.item_embedding_table.weight.device         # a block that was moved already gets its new layers there
+        self.to_merge["continuous_module"] = ContinuousProjection(cont, mlp_layers_dims).to(device)
+        try:
+            self._layout()
+        except ValueError:
+            self.to_merge["continuous_module"] = cont
+            self._layout()
+            raise
+        if self._agg_width != width:
+            if self.projection_module is not None:
+                lin = self.projection_module[0][0]
+                self.projection_module = nn.Sequential(nn.Sequential(_Linear(self._agg_width, lin.out_features))).to(device)
+            elif self._masking is not None:
+                self.to_merge["continuous_module"] = cont
+                self._layout()
+                raise ValueError("project_continuous_features (continuous_projection) changes the width the masking module was "
+                                 "built for: project before the masking is set")
+        return self
 
     # ------------------------------------------------------------------ forward
     def _apply_pre(self, inputs):
@@ -963,7 +1137,7 @@ class TabularSequenceFeatures(nn.Module):
             if out is inputs:
                 out = dict(inputs)
                 item_ids = inputs[self.categorical_module.item_id].contiguous()
-            names = list(m.names) if isinstance(m, ContinuousFeatures) else list(m.embedding_tables.keys())
+            names = list(m.names) if isinstance(m, (ContinuousFeatures, ContinuousProjection)) else list(m.embedding_tables.keys())
             out.update(ssn.augment_module(inputs, [n for n in names if n in inputs], item_ids, mname, mi))
             active[id(ssn)] = ssn
         for ssn in active.values():     # one stream position per forward, also when modules share the object

@@ -119,12 +119,14 @@ def input_block_of(model):
     """-> (params, spec) of the model's input block for `session_step`: tables / soft embeddings / projection in the column
     order the module mirror concatenates them (sorted feature names).  Supported shape = BASELINE configs[1] and [2]:
     sequence categoricals + SoftEmbedding continuous features, concat, optional ReLU projection, MLM; anything else raises."""
-    from .features import ContinuousFeatures
+    from .features import ContinuousFeatures, ContinuousProjection
 
     f = model.input_features
     cat, cont = f.categorical_module, f.continuous_module
     if getattr(f, "pretrained_module", None) is not None:
         raise NotImplementedError("functional path: pretrained-embedding features run through the module path only")
+    if isinstance(cont, ContinuousProjection):
+        raise NotImplementedError("functional path: continuous_projection runs through the module path only")
     if f._aggregation != "concat" and len(f._feature_order) > 1:
         raise NotImplementedError("functional path: concat aggregation only")
     if cat._post is not None or getattr(cat, "_pre", None) is not None:

@@ -1641,3 +1641,83 @@ def pretrained_proj_bwd(dout, image, ids, ln_w, xhat, rstd, d_W, d_b, d_ln_w=Non
          _chk(ids, torch.int64, "ids"), T, T // ids.numel(), _chk(dout, torch.float32, "dout"), ld, int(col),
          _p(ln_w, torch.float32, "ln_w"), _p(xhat), _p(rstd), E, P, _chk(d_W, torch.float32, "d_W"), _p(d_b, torch.float32, "d_b"),
          _p(d_ln_w), _p(d_ln_b), ws.data_ptr())
+
+
+# ------------------------------------------------------------------------------------ continuous-feature projection
+# (include/t4r_hip_contproj.h, csrc/cont_proj.hip): the first layer of `continuous_projection`
+def cont_proj_supported(C, P):
+    return bool(_lib.load().t4r_cont_proj_supported(int(C), int(P)))
+
+
+def _cont_proj_args(what, xs, per_session, weight, bias, T=None):
+    """checks of the arguments both directions share -> (T, L, C, P, host array of the C column pointers, host array of the
+    flags); T (tokens) is the size of the [B, L] columns, and has to be given where every column is per-session.  (Kept short:
+    at the sizes of an input block the call is a few launches, and the host's share of it counts.)"""
+    C = len(xs)
+    if C == 0 or C != len(per_session):
+        raise ValueError(f"{what}: xs and per_session must be non-empty lists of one length")
+    if weight.dim() != 2 or weight.shape[1] != C or bias.dim() != 1 or bias.shape[0] != weight.shape[0]:
+        raise ValueError(f"{what}: weight must be [P, {C}] and bias [P], got {tuple(weight.shape)} and {tuple(bias.shape)}")
+    P = weight.shape[0]
+    if C > 64 or not 1 <= P <= 1024:
+        raise ValueError(f"{what}: C = {C}, P = {P} outside 1 <= C <= 64, 1 <= P <= 1024")
+    ptrs, flags = (ctypes.c_void_p * C)(), (ctypes.c_int * C)()
+    n_seq = n_ses = None
+    for i, x in enumerate(xs):
+        ptrs[i] = _chk(x, torch.float32, "xs")
+        n = x.numel()
+        if per_session[i]:
+            flags[i] = 1
+            if n_ses is not None and n != n_ses:
+                raise ValueError(f"{what}: the per-session columns must share one size")
+            n_ses = n
+        else:
+            if n_seq is not None and n != n_seq:
+                raise ValueError(f"{what}: the sequence columns must share one size")
+            n_seq = n
+    _chk(weight, torch.float32, "weight")
+    _chk(bias, torch.float32, "bias")
+    if T is None:
+        if n_seq is None:
+            raise ValueError(f"{what}: every column is per-session: the token count T has to be given")
+        T = n_seq
+    elif n_seq is not None and n_seq != T:
+        raise ValueError(f"{what}: the sequence columns hold {n_seq} values for {T} tokens")
+    L = 1
+    if n_ses is not None:
+        if n_ses == 0 or T % n_ses:
+            raise ValueError(f"{what}: {n_ses} per-session values do not divide {T} tokens")
+        L = T // n_ses
+    return int(T), L, C, P, ptrs, flags
+
+
+def cont_proj_fwd(xs, per_session, weight, bias, T=None):
+    """relu(bias + weight @ [x_0 .. x_{C-1}]) per token without the [T, C] operand: xs the C column tensors, fp32 [B, L] or --
+    where per_session[c] -- [B] (broadcast over the sequence); weight [P, C], bias [P] -> rows [T, P], T = B * L (taken
+    from the [B, L] columns; to be given where there is none)"""
+    T, L, C, P, ptrs, flags = _cont_proj_args("cont_proj_fwd", xs, per_session, weight, bias, T)
+    out = torch.empty((T, P), device=weight.device, dtype=torch.float32)
+    call("t4r_cont_proj_fwd", _stream(), ptrs, flags, T, L, C, P, weight.data_ptr(), bias.data_ptr(), out.data_ptr())
+    return out
+
+
+def cont_proj_bwd_(dout2d, col, xs, per_session, weight, bias, d_w, d_b, want_dpre=False):
+    """the parameter gradients of cont_proj_fwd, ACCUMULATED into d_w [P, C] and d_b [P], from columns [col, col + P) of dout2d
+    [T, ld]; the ReLU mask is recomputed from the inputs.  Bit-reproducible (no float atomics).  -> the masked gradient [T, P]
+    when want_dpre, else None"""
+    if not dout2d.is_cuda:
+        raise _lib.T4RHipError(f"cont_proj_bwd_: dout2d must live on the GPU (got {dout2d.device}); there is no CPU path")
+    if dout2d.dim() != 2:
+        raise ValueError(f"cont_proj_bwd_: dout2d must be 2-D, got {tuple(dout2d.shape)}")
+    T, L, C, P, ptrs, flags = _cont_proj_args("cont_proj_bwd_", xs, per_session, weight, bias, dout2d.shape[0])
+    if col < 0 or dout2d.shape[1] < col + P:
+        raise ValueError(f"cont_proj_bwd_: dout2d must be [{T}, >= col + {P}], got {tuple(dout2d.shape)} with col = {col}")
+    if d_w.shape != weight.shape or d_b.shape != bias.shape:
+        raise ValueError("cont_proj_bwd_: d_w and d_b must have the shapes of weight and bias")
+    ld = dout2d.shape[1]
+    dpre = torch.empty((T, P), device=weight.device, dtype=torch.float32) if want_dpre else None
+    ws = torch.empty(max(1, _lib.load().t4r_cont_proj_bwd_ws_floats(T, C, P)), device=weight.device, dtype=torch.float32)
+    call("t4r_cont_proj_bwd", _stream(), _chk(dout2d, torch.float32, "dout2d"), ld, int(col), ptrs, flags, T, L, C, P,
+         weight.data_ptr(), bias.data_ptr(), _chk(d_w, torch.float32, "d_w"), _chk(d_b, torch.float32, "d_b"), _p(dpre),
+         ws.data_ptr())
+    return dpre
