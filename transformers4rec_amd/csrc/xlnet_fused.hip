@@ -61,7 +61,9 @@ struct FFFwdRowsParams : FFFwdParams {
 // own power-of-two scale; the activation rows are positioned by a per-token BOUND known before the first chunk
 // (|gelu(x)| <= |x|, |pre[t][f]| <= D max|W1| max|h1[t]| + max|b1|, the dropout factor on top): one scale for all four
 // chunks of a token, as their products share an accumulator.  The bound is loose by one to two orders of magnitude, which
-// costs nothing: fp16 keeps its 11 + 11 bits over 2^17 of range below the bound.
+// costs nothing: fp16 keeps its 11 + 11 bits down to 2^-3 in scaled units, i.e. over 2^16 (the bound at the bottom of
+// [2^13, 2^14)) to 2^17 (at its top) of range below the bound; further down an element is off by at most 2^-25 scaled
+// (tests/body_split_restatement.py: the budget, tests/test_body_split_gpu.py: families C and D).
 template <int D, int R, bool FULL, bool TRAIN, bool HS, bool MAP = false, class Params = FFFwdParams>
 __device__ __forceinline__ void ff_fwd_body(const Params& p, uint16_t* smem) {
     constexpr int NW = D / 16, NT = NW * 64, RT = 16 * R, PH = D + 16, PLN = RT * PH, DI = 4 * D;
