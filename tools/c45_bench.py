@@ -15,6 +15,9 @@ timed here for the record (bench.py reports configs[1]):
 
 "rowsparse" anywhere on the command line (c4 only: its head is sampled, so every table's gradient is row-sparse) steps the tables
 with optim.RowSparseAdam and the rest with FusedAdam over one bucket, instead of FusedAdam over both buckets.
+"clipped" anywhere on the command line runs the reference's Trainer recipe, FusedAdam(max_grad_norm=1.0,
+decoupled_weight_decay=True, weight_decay=0.01), over both buckets; with "rowsparse" as the linked pair
+FusedAdam(...).link(RowSparseAdam(...)): one global norm over the bucket and the tables' rows, one step() for both.
 """
 import json
 import os
@@ -28,7 +31,9 @@ import transformers4rec_amd as tr
 from transformers4rec_amd import ops
 
 ROWSPARSE = "rowsparse" in sys.argv
-sys.argv = [a for a in sys.argv if a != "rowsparse"]
+CLIPPED = "clipped" in sys.argv
+sys.argv = [a for a in sys.argv if a not in ("rowsparse", "clipped")]
+HP = dict(lr=1e-3, weight_decay=0.01, decoupled_weight_decay=True) if CLIPPED else dict(lr=1e-3)
 dev = torch.device("cuda", 0)
 which = sys.argv[1] if len(sys.argv) > 1 else "c4"
 n = int(sys.argv[2]) if len(sys.argv) > 2 else (20 if which == "c4" else 3)
@@ -57,16 +62,20 @@ if ROWSPARSE:
     if which != "c4" or not sparse:
         raise SystemExit("rowsparse: only c4 (sampled head) has tables a lazy step may own")
     dense = optim.FlatParams((n_, p_) for n_, p_ in model.named_parameters() if n_ not in sparse)
-    opt_d, opt_s = tr.FusedAdam([dense], lr=1e-3), optim.RowSparseAdam(sparse.values(), lr=1e-3).attach()
+    opt_s = optim.RowSparseAdam(sparse.values(), **HP).attach()
+    if CLIPPED:       # the linked pair: one step() for both, one norm over both
+        opt = tr.FusedAdam([dense], max_grad_norm=1.0, **HP).link(opt_s)
+    else:
+        opt_d = tr.FusedAdam([dense], **HP)
 
-    class opt:        # the pair behind the one name the step below uses
-        @staticmethod
-        def step():
-            opt_d.step()
-            opt_s.step()
+        class opt:        # the pair behind the one name the step below uses
+            @staticmethod
+            def step():
+                opt_d.step()
+                opt_s.step()
 else:
     dense, tables = tr.flatten_model(model)
-    opt = tr.FusedAdam([dense, tables], lr=1e-3)
+    opt = tr.FusedAdam([dense, tables], max_grad_norm=1.0 if CLIPPED else None, **HP)
 model.train()
 batches = [tr.random_data_from_schema(schema, B, L, seed=i, device=dev) for i in range(2)]
 
@@ -89,12 +98,14 @@ for i in range(n):
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
 N = n_lab // n
-res = {"config": which, "optimizer": "FusedAdam + RowSparseAdam" if ROWSPARSE else "FusedAdam", "V": V, "d_model": D, "layers": NL, "seq_len": L, "batch": B, "precision": ops.get_precision(),
+res = {"config": which, "optimizer": ("FusedAdam + RowSparseAdam" if ROWSPARSE else "FusedAdam") + (", AdamW clipped at 1.0" if CLIPPED else ""), "V": V, "d_model": D, "layers": NL, "seq_len": L, "batch": B, "precision": ops.get_precision(),
        "head_mode": task.resolve_head_mode(N, V + 1) if which == "c5" else "sampled",
        "steps": n, "ms_per_step": round(1e3 * dt / n, 2), "sessions_per_s": round(B * n / dt, 1),
        "label_rows_per_step": N, "loss": round(float(out["loss"].detach()), 4),
        "peak_memory_GB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1),
        "logits_if_materialised_GB": round(4.0 * N * (V + 1) / 2 ** 30, 1)}
+if CLIPPED:
+    res["last_grad_norm"] = round(float(opt.last_grad_norm), 4)
 if which == "c5":
     flops_head = 4 * 2.0 * N * (V + 1) * D          # fwd + recompute + dX + dW
     res["head_TFLOP_per_step"] = round(flops_head / 1e12, 1)

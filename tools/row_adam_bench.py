@@ -2,8 +2,8 @@
 (V 1 M, D 256) and of configs[1] (V 100 k, D 128), for the rows one step of configs[3] names: n = 1024 * 50 lookups + 15 000 head
 rows, Zipf(1.0) over the table.
 
-One process per shape (started by the driver under its own time limit), device events, the two legs alternated inside every
-iteration so that a drift of the box hits both alike:
+One process per shape (started by the driver under its own time limit), device events, the three legs alternated inside every
+iteration so that a drift of the box hits all alike:
 
   dense   what FusedAdam's table bucket runs: ops.scatter_rows_sorted of (ids, rows) into the [V, D] gradient (sort + segmented
           sum) + ops.adam_step_ over the whole bucket, which also zeroes the gradient again.  At least 7 V D 4 bytes: param,
@@ -11,7 +11,12 @@ iteration so that a drift of the box hits both alike:
   lazy    ops.row_adam_step_ on the same (ids, rows), sort included (csrc/row_adam.hip).  About (n + 8 U) D 4 bytes for U distinct
           rows -- n gradient rows read, the compact gradient written and read, three table rows read and written -- plus the sort.
 
-Before anything is timed the two legs run once from one state and the rows that have a gradient are compared bit for bit.
+  clipped the same step in its two halves with the global norm in between (include/t4r_hip_rowclip.h): ops.row_adam_reduce_ (sort,
+          stages 1 and 2, the sum of squares of the compact rows) + ops.grad_clip_coef_ over its partials + ops.row_adam_apply_ with
+          the device coefficient (max_norm = inf: the coefficient is 1 and the bits are the lazy leg's).  The model adds one read of
+          the compact buffer, 4 U D bytes, and two launches (the sum of squares, the one-workgroup coefficient) to the lazy leg.
+
+Before anything is timed the legs run once from one state and the rows that have a gradient are compared bit for bit.
 
     python tools/row_adam_bench.py [--iters 50] [--warmup 10] [--out profiles/row_adam_ab.json]
 """
@@ -54,6 +59,9 @@ def one(V, D, iters, warmup):
     p0 = 0.05 * torch.randn(V, D, generator=g, device=dev)
     dense = dict(p=p0.clone(), g=torch.zeros(V, D, device=dev), m=torch.zeros(V, D, device=dev), v=torch.zeros(V, D, device=dev))
     lazy = dict(p=p0.clone(), m=torch.zeros(V, D, device=dev), v=torch.zeros(V, D, device=dev))
+    clip = dict(p=p0.clone(), m=torch.zeros(V, D, device=dev), v=torch.zeros(V, D, device=dev))
+    part = torch.zeros(ops.row_grad_sumsq_parts(n, D), device=dev, dtype=torch.float64)
+    out2 = torch.zeros(2, device=dev)
     del p0
     hp = dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0)
 
@@ -64,21 +72,28 @@ def one(V, D, iters, warmup):
     def leg_lazy(ids, rows, step):
         ops.row_adam_step_(lazy["p"], lazy["m"], lazy["v"], ids, rows, step, **hp)
 
+    def leg_clipped(ids, rows, step):
+        cnt, st = ops.row_adam_reduce_(ids, rows, V, -1, part)
+        ops.grad_clip_coef_(part, cnt, 1.0, float("inf"), out2)
+        ops.row_adam_apply_(clip["p"], clip["m"], clip["v"], st, step, clip_coef=out2[1:], **hp)
+
     # same results first: one step from one state, the rows that have a gradient bit for bit (every other row has zero moments
     # and a zero gradient in the dense leg: it does not move there either)
     leg_dense(*sets[0], 1)
     leg_lazy(*sets[0], 1)
+    leg_clipped(*sets[0], 1)
     torch.cuda.synchronize()
-    same = all(bool(torch.equal(dense[k].view(torch.int32), lazy[k].view(torch.int32))) for k in ("p", "m", "v"))
+    same = all(bool(torch.equal(dense[k].view(torch.int32), other[k].view(torch.int32))) for k in ("p", "m", "v") for other in (lazy, clip))
+    same = same and float(out2[1]) == 1.0
     if not same:
-        raise SystemExit(f"row_adam_bench: the two legs disagree after one step at V={V} D={D}; nothing timed")
+        raise SystemExit(f"row_adam_bench: the legs disagree after one step at V={V} D={D}; nothing timed")
 
-    legs = {"dense": leg_dense, "lazy": leg_lazy}
+    legs = {"dense": leg_dense, "lazy": leg_lazy, "clipped": leg_clipped}
     times = {k: [] for k in legs}
     order = list(legs)
     for it in range(warmup + iters):
         ids, rows = sets[it % N_ID_SETS]
-        for name in order[it % 2:] + order[:it % 2]:
+        for name in order[it % 3:] + order[:it % 3]:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             legs[name](ids, rows, it + 2)
@@ -96,7 +111,10 @@ def one(V, D, iters, warmup):
     return {"V": V, "D": D, "n": n, "distinct_rows_mean": round(U, 1), "first_step_bits_equal": same, "legs": res,
             "dense_over_lazy": round(res["dense"]["median_us"] / res["lazy"]["median_us"], 2),
             "outside_spread": res["lazy"]["p90_us"] < res["dense"]["p10_us"],
-            "model_bytes": {"dense_at_least": 7 * V * D * 4, "lazy_about": int((n + 8 * U) * D * 4) + 2 * n * 4},
+            "clipped_minus_lazy_us": round(res["clipped"]["median_us"] - res["lazy"]["median_us"], 2),
+            "clipped_norm": round(float(out2[0]), 6),
+            "model_bytes": {"dense_at_least": 7 * V * D * 4, "lazy_about": int((n + 8 * U) * D * 4) + 2 * n * 4,
+                            "clipped_adds_about": int(U * D * 4)},
             "device": torch.cuda.get_device_name(0)}
 
 
@@ -120,7 +138,7 @@ def main():
             raise SystemExit(f"row_adam_bench: V={V} D={D} ended with {r.returncode}\n{r.stdout}\n{r.stderr}")
         shapes.append(json.loads(r.stdout.strip().splitlines()[-1]))
     record = {"tool": "tools/row_adam_bench.py", "iters": args.iters, "warmup": args.warmup,
-              "timing": "device events around each leg, one process per shape, legs alternated within every iteration; microseconds",
+              "timing": "device events around each leg, one process per shape, the three legs alternated within every iteration; microseconds",
               "ids": f"Zipf(1.0) over the table, {N_ID_SETS} sets of n = 1024 * 50 + 15 000 rotated over the iterations",
               "shapes": shapes}
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -19,6 +19,7 @@ ATTN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_attn
 ROWS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_rows.h")
 ROWADAM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_rowadam.h")
 CONTPROJ_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_contproj.h")
+ROWCLIP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_rowclip.h")
 
 _P, _I, _L, _F, _Q = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_ulonglong
 _C = {"p": _P, "i": _I, "l": _L, "f": _F, "Q": _Q}
@@ -234,6 +235,16 @@ _SIGS_CONTPROJ = {
     "t4r_cont_proj_bwd": ("i", "p" + "pli" + _CP + "pppp"),
 }
 
+# the tenth header, include/t4r_hip_rowclip.h (tests/test_row_clip_cpu.py checks this table against it): the row-sparse Adam step
+# in two halves for global-norm clipping.  reduce: stream, V, D, keys, perm, grad_rows, ld_grad, n, ws, ws_bytes, part; apply:
+# stream, param, exp_avg, exp_avg_sq, V, D, n, step, the six floats (lr, beta1, beta2, eps, weight_decay | decoupled | grad_scale),
+# clip_coef, ws, ws_bytes
+_SIGS_ROWCLIP = {
+    "t4r_row_grad_sumsq_parts": ("l", "li"),
+    "t4r_row_adam_reduce": ("i", "pli" + "ppp" + "ll" + "pl" + "p"),
+    "t4r_row_adam_apply": ("i", "pppp" + "li" + "li" + "fffff" + "if" + "p" + "pl"),
+}
+
 _lib = None
 
 
@@ -292,6 +303,11 @@ def contproj_header_symbols():
     return _declared(CONTPROJ_HEADER_PATH)
 
 
+def rowclip_header_symbols():
+    """Function names declared in include/t4r_hip_rowclip.h."""
+    return _declared(ROWCLIP_HEADER_PATH)
+
+
 def load():
     """Loads the library and sets ctypes prototypes.  Raises if it is not built."""
     global _lib
@@ -304,7 +320,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (ret, args) in (list(_SIGS.items()) + list(_SIGS_SAMPLING.items()) + list(_SIGS_FILTER.items()) + list(_SIGS_OPTIM.items())
                               + list(_SIGS_PRETRAINED.items()) + list(_SIGS_ATTN.items()) + list(_SIGS_ROWS.items()) + list(_SIGS_ROWADAM.items())
-                              + list(_SIGS_CONTPROJ.items())):
+                              + list(_SIGS_CONTPROJ.items()) + list(_SIGS_ROWCLIP.items())):
         fn = getattr(lib, name)
         fn.restype = ctypes.c_char_p if ret == "s" else (None if ret == "v" else _C[ret])
         fn.argtypes = [_C[a] for a in args]

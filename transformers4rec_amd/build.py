@@ -1,5 +1,5 @@
 """Builds libt4r_hip.so (all HIP kernels + the C ABI of include/t4r_hip.h, include/t4r_hip_sampling.h,
-include/t4r_hip_filter.h, include/t4r_hip_optim.h, include/t4r_hip_pretrained.h, include/t4r_hip_attn.h, include/t4r_hip_rows.h, include/t4r_hip_rowadam.h and include/t4r_hip_contproj.h) for gfx950 with
+include/t4r_hip_filter.h, include/t4r_hip_optim.h, include/t4r_hip_pretrained.h, include/t4r_hip_attn.h, include/t4r_hip_rows.h, include/t4r_hip_rowadam.h, include/t4r_hip_contproj.h and include/t4r_hip_rowclip.h) for gfx950 with
 hipcc, in-tree (transformers4rec_amd/lib/).  hipcc cross-compiles without a GPU.
 
     python -m transformers4rec_amd.build [--force]

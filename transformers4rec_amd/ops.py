@@ -1588,6 +1588,87 @@ def row_adam_step_(param, exp_avg, exp_avg_sq, ids, rows, step, lr=1e-3, betas=(
          float(grad_scale), ws.data_ptr(), nb)
 
 
+# ---- include/t4r_hip_rowclip.h: the same step in two halves, for a global norm over dense buckets and lazily stepped tables
+# (optim.FusedAdam(max_grad_norm=).link(RowSparseAdam) drives them)
+def row_grad_sumsq_parts(n, D):
+    """how many partials row_adam_reduce_ over n lookups of width D writes (a pure function of (n, D), <= 2048)"""
+    return _lib.load().t4r_row_grad_sumsq_parts(int(n), int(D))
+
+
+class RowAdamReduced:
+    """what row_adam_reduce_ leaves for row_adam_apply_: the workspace (ranks, table rows, the compact summed gradient) and the
+    (n, V, D) it was laid out for.  Opaque; good for one apply."""
+    __slots__ = ("ws", "nbytes", "n", "V", "D")
+
+    def __init__(self, ws, nbytes, n, V, D):
+        self.ws, self.nbytes, self.n, self.V, self.D = ws, nbytes, n, V, D
+
+
+def row_adam_reduce_(ids, rows, V, padding_idx, part):
+    """The first half of row_adam_step_ for a table of V rows: sorts the ids, sums rows[i] per distinct valid id into a compact
+    buffer (the bits of scatter_rows_sorted into a zeroed [V, D] buffer) and writes part[:count] (float64) = per-workgroup sums
+    of the squares of those sums, squared and added in double -- the table's share of the global gradient norm, ready to stand
+    beside grad_sumsq_'s partials in front of grad_clip_coef_.  count = row_grad_sumsq_parts(n, D) whatever the ids are;
+    slots beyond it are untouched.  -> (count, state for row_adam_apply_).  ids int64 [n]; rows fp32 [n, D], unit inner stride, any
+    row pitch >= D; ids equal to padding_idx or outside [0, V) carry nothing."""
+    for t, name in ((ids, "ids"), (rows, "rows"), (part, "part")):
+        if not t.is_cuda:
+            raise _lib.T4RHipError(f"row_adam_reduce_: {name} must live on the GPU (got {t.device}); there is no CPU path")
+    ids = ids.reshape(-1)
+    n = ids.numel()
+    if rows.dim() != 2 or rows.shape[0] != n or rows.dtype != torch.float32 or (rows.shape[1] > 1 and rows.stride(1) != 1):
+        raise ValueError(f"row_adam_reduce_: rows must be fp32 [{n}, D] with unit inner stride")
+    D = rows.shape[1]
+    V = int(V)
+    if V < 1 or D < 1:
+        raise ValueError("row_adam_reduce_: V and D must be at least 1")
+    _chk(part, torch.float64, "part")
+    lib = _lib.load()
+    need = lib.t4r_row_grad_sumsq_parts(n, D)
+    if part.numel() < need:
+        raise ValueError(f"part holds {part.numel()} partials, {need} are written")
+    if n == 0:
+        return 0, RowAdamReduced(None, 0, 0, V, D)
+    ld = _row_pitch(rows, D)
+    if ld < D:
+        raise ValueError("row_adam_reduce_: the row pitch of rows must be at least D")
+    keys, perm = sort_ids(ids, V, padding_idx)
+    nb = lib.t4r_row_adam_ws_bytes(n, D)
+    ws = torch.empty(max(nb, 1), device=rows.device, dtype=torch.uint8)
+    cnt = lib.t4r_row_adam_reduce(_stream(), V, D, keys.data_ptr(), perm.data_ptr(), rows.data_ptr(), ld, n, ws.data_ptr(), nb,
+                                  part.data_ptr())
+    if cnt < 0:
+        raise _lib.T4RHipError(lib.t4r_last_error().decode())
+    return cnt, RowAdamReduced(ws, nb, n, V, D)
+
+
+def row_adam_apply_(param, exp_avg, exp_avg_sq, state, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                    decoupled=False, grad_scale=1.0, clip_coef=None):
+    """The second half: one Adam / AdamW step of the rows of `param` [V, D] that the ids of `state`'s row_adam_reduce_ named,
+    with the gradient (sum * grad_scale) * clip_coef -- clip_coef a 1-element fp32 device tensor (grad_clip_coef_'s out[1:]) or
+    None (1: the bits of row_adam_step_).  Every other row of param and of the two moments is neither read nor written."""
+    for t, name in ((param, "param"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        if not t.is_cuda:
+            raise _lib.T4RHipError(f"row_adam_apply_: {name} must live on the GPU (got {t.device}); there is no CPU path")
+    if not isinstance(state, RowAdamReduced):
+        raise TypeError("row_adam_apply_: state is what row_adam_reduce_ returned")
+    if param.dim() != 2 or exp_avg.shape != param.shape or exp_avg_sq.shape != param.shape:
+        raise ValueError("row_adam_apply_: param, exp_avg and exp_avg_sq are [V, D] tensors of one shape")
+    if tuple(param.shape) != (state.V, state.D):
+        raise ValueError(f"row_adam_apply_: the rows were reduced for a [{state.V}, {state.D}] table, param is {tuple(param.shape)}")
+    if clip_coef is not None and clip_coef.numel() != 1:
+        raise ValueError("clip_coef is one float")
+    if state.n == 0:
+        return
+    if state.ws is None:
+        raise RuntimeError("row_adam_apply_: this state was applied already; the workspace is good for one apply")
+    call("t4r_row_adam_apply", _stream(), _chk(param, torch.float32, "param"), _chk(exp_avg, torch.float32, "exp_avg"),
+         _chk(exp_avg_sq, torch.float32, "exp_avg_sq"), state.V, state.D, state.n, int(step), float(lr), float(betas[0]),
+         float(betas[1]), float(eps), float(weight_decay), int(bool(decoupled)), float(grad_scale),
+         _p(clip_coef, torch.float32, "clip_coef"), state.ws.data_ptr(), state.nbytes)
+    state.ws = None                            # consumed: the workspace is undefined after the apply
+
+
 # ------------------------------------------------------------------------------------ pretrained-embedding features
 # (include/t4r_hip_pretrained.h, csrc/pretrained_proj.hip)
 def _pretrained_image(what, image, ids, E):

@@ -95,7 +95,20 @@ class FusedAdam:
     over all buckets as torch.nn.utils.clip_grad_norm_ does, with the norm and the coefficient left on the device.  The
     reference's Trainer recipe (AdamW, max_grad_norm 1.0, warm-up) is
         FusedAdam(flats, lr, weight_decay=0.01, decoupled_weight_decay=True, max_grad_norm=1.0) + set_schedule(warmup_schedule(...)).
-    With both new arguments at their defaults step() launches exactly what it always has."""
+    With both new arguments at their defaults step() launches exactly what it always has.
+
+    link(opt_s) hands it a RowSparseAdam whose tables this optimizer steps WITH its buckets -- the linked pair,
+        opt_d = FusedAdam([dense], lr, ..., max_grad_norm=1.0).link(opt_s)
+    (a method, as set_schedule: the constructor's parameter list is as it was).  One step() then steps both, and with max_grad_norm the norm is the global one, over the buckets and over the rows the tables received
+    (csrc/row_adam.hip, include/t4r_hip_rowclip.h): the sum of squares of every bucket, then of every table's summed rows
+    (ops.row_adam_reduce_: the non-zero rows of the dense gradient clip_grad_norm_ would have seen, bit for bit), ONE coefficient,
+    the buckets' steps, the tables' steps (ops.row_adam_apply_) with the same device coefficient; last_grad_norm is the joint
+    norm.  The RowSparseAdam keeps its own step count, schedule, hyper-parameters and state_dict; calling its step() directly
+    raises.  Without max_grad_norm the linked pair runs the two unclipped paths: the bits of stepping the two objects one after the other.
+    Data parallel needs no further collective: after GradReducer.reduce_all the buckets are equal on every rank and, with
+    SparseRowExchange(apply_fn=opt_s.add_rows), every rank holds the same concatenation of (ids, rows) -- no float atomics
+    anywhere, so every rank computes the same partials and the same coefficient bits.  The linked step() must therefore run
+    AFTER reduce_all."""
 
     def __init__(self, flats, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None,
                  decoupled_weight_decay=False):
@@ -107,9 +120,11 @@ class FusedAdam:
         self.base_lr, self._schedule = lr, None
         self.state = [(torch.zeros_like(f.data), torch.zeros_like(f.data)) for f in self.flats]
         self.step_count = 0
-        # clipping: the partial sums of squares of every bucket side by side, and (norm, coefficient); allocated at the first
-        # clipped step (the partial counts come from the library)
+        # clipping: the partial sums of squares of every bucket (and of every linked table) side by side, and (norm,
+        # coefficient); allocated at the first clipped step (the partial counts come from the library) and, with linked tables,
+        # grown when a step's lookups need more: their count depends on n
         self._clip_part = self._clip_out = None
+        self.row_sparse = None                         # the linked RowSparseAdam (link()); not state: no state_dict carries it
         # per bucket: (parameter, offset, partial-maxima buffer) of its largest 2-D table on the GPU, or None
         self._amax_targets = []
         for f in self.flats:
@@ -126,6 +141,16 @@ class FusedAdam:
         from .transformer import _join_weight_gradient_streams
         _join_weight_gradient_streams()
 
+    def link(self, row_sparse):
+        """row_sparse: the RowSparseAdam this optimizer steps with its buckets from now on (see the class docstring).  One
+        RowSparseAdam per FusedAdam and one FusedAdam per RowSparseAdam.  -> self"""
+        if not isinstance(row_sparse, RowSparseAdam):
+            raise TypeError(f"link: expected a RowSparseAdam, got {type(row_sparse).__name__}")
+        if row_sparse._linked not in (None, self) or self.row_sparse not in (None, row_sparse):
+            raise RuntimeError("link: one of the two optimizers is already linked to another")
+        self.row_sparse, row_sparse._linked = row_sparse, self
+        return self
+
     def set_schedule(self, f):
         """f(step) -> multiplier of the constructor's lr (warmup_schedule); None: constant.  The step that makes step_count == t
         runs at base_lr * f(t - 1): a torch scheduler is stepped AFTER the optimizer, so its first step runs at f(0)."""
@@ -134,7 +159,7 @@ class FusedAdam:
 
     @property
     def last_grad_norm(self):
-        """0-d device tensor: the norm of the scaled gradient over all buckets BEFORE the clip of the last step; None when
+        """0-d device tensor: the norm of the scaled gradient over all buckets (and the linked tables' rows) BEFORE the clip of the last step; None when
         clipping is off or no step was taken.  Reading it synchronises the caller, not step()."""
         return None if self._clip_out is None else self._clip_out[0]
 
@@ -143,8 +168,16 @@ class FusedAdam:
         self.step_count += 1
         if self._schedule is not None:
             self.lr = self.base_lr * self._schedule(self.step_count - 1)
+        rs = self.row_sparse
+        if rs is not None:
+            rs._advance()
         if self.max_grad_norm is not None or self.decoupled_weight_decay:
             return self._step_ext(grad_scale)
+        self._step_plain(grad_scale)
+        if rs is not None:
+            rs._step_tables(grad_scale)
+
+    def _step_plain(self, grad_scale):
         for k, (f, (m, v)) in enumerate(zip(self.flats, self.state)):
             f.ensure_grads()
             tgt = self._amax_targets[k]
@@ -160,18 +193,29 @@ class FusedAdam:
             p._t4r_w_amax = (part, n, p.data_ptr(), p._version, f.data, f.data._version)
 
     def _step_ext(self, grad_scale):
-        """sum of squares per bucket -> one coefficient launch -> one t4r_adamw_step per bucket"""
+        """sum of squares per bucket (and per linked table) -> one coefficient launch -> one t4r_adamw_step per bucket (and one
+        t4r_row_adam_apply per table)"""
         for f in self.flats:
             f.ensure_grads()
-        coef = None
+        rs = self.row_sparse
+        coef, reduced = None, None
         if self.max_grad_norm is not None:
-            if self._clip_part is None:
-                dev = self.flats[0].data.device
-                self._clip_part = torch.zeros(sum(ops.grad_sumsq_parts(f.numel) for f in self.flats), device=dev, dtype=torch.float64)
+            tables = rs._take_pending() if rs is not None else []
+            need = (sum(ops.grad_sumsq_parts(f.numel) for f in self.flats)
+                    + sum(ops.row_grad_sumsq_parts(ids.numel(), p.shape[1]) for p, _, _, ids, _, _ in tables))
+            dev = self.flats[0].data.device
+            if self._clip_part is None or self._clip_part.numel() < need:
+                self._clip_part = torch.zeros(need, device=dev, dtype=torch.float64)
+            if self._clip_out is None:
                 self._clip_out = torch.zeros(2, device=dev, dtype=torch.float32)
             n_part = 0
             for f in self.flats:
                 n_part += ops.grad_sumsq_(f.grad, self._clip_part[n_part:])
+            reduced = []
+            for p, m, v, ids, rows, pad in tables:
+                k, st = ops.row_adam_reduce_(ids, rows, p.shape[0], pad, self._clip_part[n_part:])
+                n_part += k
+                reduced.append((p, m, v, st))
             ops.grad_clip_coef_(self._clip_part, n_part, grad_scale, self.max_grad_norm, self._clip_out)
             coef = self._clip_out[1:]
         for k, (f, (m, v)) in enumerate(zip(self.flats, self.state)):
@@ -182,6 +226,14 @@ class FusedAdam:
             if tgt is not None:       # as step(): the table's maximum after the update, for the head of the next step
                 p = tgt[0]
                 p._t4r_w_amax = (tgt[2], n, p.data_ptr(), p._version, f.data, f.data._version)
+        if rs is None:
+            return
+        if reduced is None:                             # decoupled weight decay without a clip: the unclipped lazy step
+            return rs._step_tables(grad_scale)
+        for p, m, v, st in reduced:
+            ops.row_adam_apply_(p.data, m, v, st, rs.step_count, rs.lr, rs.betas, rs.eps, rs.weight_decay,
+                                rs.decoupled_weight_decay, grad_scale, clip_coef=coef)
+            rs._wrote(p)
 
     def state_dict(self):
         """moments per bucket (copies), step count and hyper-parameters; a schedule is code and is set again by the caller"""
@@ -254,9 +306,17 @@ class RowSparseAdam:
         opt_s = optim.RowSparseAdam(sparse.values(), lr).attach()
         ... loss.backward(); opt_d.step(); opt_s.step()
 
-    params: 2-D fp32 contiguous parameters on the GPU (views into a FlatParams buffer are fine).  No gradient clipping:
-    max_grad_norm over dense and row-sparse gradients together is out of scope; clip the dense bucket with FusedAdam alone or
-    not at all.  Several entries for one table in one step (a tied sampled head's rows and the lookups' rows) are summed as
+    or, linked, for the reference's Trainer recipe (AdamW, max_grad_norm over ALL parameters):
+
+        opt_s = optim.RowSparseAdam(sparse.values(), lr, weight_decay=0.01, decoupled_weight_decay=True).attach()
+        opt_d = optim.FusedAdam([dense], lr, weight_decay=0.01, decoupled_weight_decay=True, max_grad_norm=1.0).link(opt_s)
+        ... loss.backward(); opt_d.step()               # steps both; opt_s.step() raises while linked
+
+    Gradient clipping: FusedAdam(max_grad_norm=).link(this optimizer) clips the global norm over the dense buckets and
+    these tables' rows together, with one device coefficient (see FusedAdam); under data parallel that step runs after
+    GradReducer.reduce_all, which delivers the exchanged rows here.  Clipping by value is out of scope.
+
+    params: 2-D fp32 contiguous parameters on the GPU (views into a FlatParams buffer are fine).  Several entries for one table in one step (a tied sampled head's rows and the lookups' rows) are summed as
     ONE list in arrival order; the dense route sums each scatter on its own and adds the sums, so a row that several entries
     name can differ from it in the last bits of its gradient."""
 
@@ -276,6 +336,7 @@ class RowSparseAdam:
         self.state = [(torch.zeros_like(p.data), torch.zeros_like(p.data)) for p in self.params]
         self.step_count = 0
         self._pending = []
+        self._linked = None                        # the FusedAdam that steps these tables (FusedAdam.link), if any
 
     # ---- the sink (distributed.SparseRowExchange has the same three)
     def attach(self):
@@ -312,11 +373,23 @@ class RowSparseAdam:
         return self
 
     def step(self, grad_scale=1.0):
+        if self._linked is not None:
+            raise RuntimeError("RowSparseAdam.step: this optimizer is linked to a FusedAdam (link()); the pair is stepped "
+                               "through the FusedAdam's step()")
         FusedAdam._join()
+        self._advance()
+        self._step_tables(grad_scale)
+
+    def _advance(self):
         self.step_count += 1
         if self._schedule is not None:
             self.lr = self.base_lr * self._schedule(self.step_count - 1)
+
+    def _take_pending(self):
+        """-> [(param, exp_avg, exp_avg_sq, ids, rows, padding_idx)]: one entry per table that received rows since the last
+        step, in table order; the pending list is empty afterwards"""
         pending, self._pending = self._pending, []
+        out = []
         for p, (m, v) in zip(self.params, self.state):
             mine = [(ids, rows, pad) for tab, ids, rows, pad in pending if tab is p]
             if not mine:
@@ -331,11 +404,20 @@ class RowSparseAdam:
                 V = p.shape[0]
                 ids = torch.cat([i if (q == pad or q < 0) else torch.where(i == q, torch.full_like(i, V), i) for i, _, q in mine])
                 rows = torch.cat([r for _, r, _ in mine])
+            out.append((p, m, v, ids, rows, pad))
+        return out
+
+    @staticmethod
+    def _wrote(p):
+        # the kernel wrote the table behind torch's version counter: a maximum FusedAdam left for the head is stale now
+        if hasattr(p, "_t4r_w_amax"):
+            del p._t4r_w_amax
+
+    def _step_tables(self, grad_scale):
+        for p, m, v, ids, rows, pad in self._take_pending():
             ops.row_adam_step_(p.data, m, v, ids, rows, self.step_count, self.lr, self.betas, self.eps, self.weight_decay,
                                self.decoupled_weight_decay, grad_scale, padding_idx=pad)
-            # the kernel wrote the table behind torch's version counter: a maximum FusedAdam left for the head is stale now
-            if hasattr(p, "_t4r_w_amax"):
-                del p._t4r_w_amax
+            self._wrote(p)
 
     def zero_grad(self):
         """drops the rows collected since the last step"""
