@@ -453,3 +453,59 @@ def test_model_level_dropout_fusions_do_not_change_the_step(ops, switch, monkeyp
     assert p1.keys() == p0.keys() and len(p1) >= 3 * 13
     for n in p1:
         assert torch.equal(p1[n], p0[n]), n
+
+
+def test_stand_alone_entries_are_not_coloured_by_a_layer_call(ops):
+    """The layer hands its per-launch options (operand maxima of a GEMM, the maxima buffers and the fused model-level dropouts of
+    the token-tile kernels) to internal entries as arguments; the public entries pass "off".  So a stand-alone call gives the
+    same bits before and after a layer forward + backward of the same thread that used every option (first AND last layer of a
+    stack, dropout on).  T = 60 is no multiple of 16: a ragged last tile."""
+    import test_kernels_gpu as K
+
+    B, L, D, n = 3, 20, 64, 4
+    T, p_drop, seed = B * L, 0.1, 777
+    assert ops.xlnet_attn_block_supported(L, D, n)
+    g = torch.Generator().manual_seed(60)
+    prm = {k: K.cu(v) for k, v in K._layer_params(g, D, n).items()}
+    params = [prm[k] for k in K.ORDER]
+    rnd = lambda *s: K.cu(torch.randn(*s, generator=g))
+    h, dy, dqkv, dh0 = rnd(T, D), rnd(T, D), rnd(3, T, D), rnd(T, D)
+    ga, gb, c0 = rnd(T, D), rnd(T, 4 * D), rnd(D, 4 * D)          # the GEMM: c0[64, 256] += ga[60, 64]^T @ gb[60, 256]
+    pos = K.cu(O.xlnet_pos_emb(L, D))
+    planes = ops.xlnet_layer_prepare(params, D)
+    kr = ops.xlnet_kr_proj(pos, planes)
+    ctr = lambda site: ops.dropout_ctr_hi(3, 1, site)
+
+    def stand_alone():
+        out = []
+        hout, saved = ops.xlnet_ff_fwd(h, planes, prm["b1"], prm["b2"], prm["ff_ln_w"], prm["ff_ln_b"], 0.03, drop_p=p_drop,
+                                       seed=seed, ctr_act=ctr(ops.SITE_FF_ACT), ctr_out=ctr(ops.SITE_FF_OUT))
+        out += [hout] + [saved[k] for k in ("ffpre", "ffact", "ffout", "mean", "rstd")]
+        dsum = [torch.zeros(D, device=DEV), torch.zeros(D, device=DEV), torch.zeros(D, device=DEV), torch.zeros(4 * D, device=DEV)]
+        out += list(ops.xlnet_ff_bwd(dy, h, saved, prm["ff_ln_w"], planes, *dsum, drop_p=p_drop, seed=seed,
+                                     ctr_act=ctr(ops.SITE_FF_ACT), ctr_out=ctr(ops.SITE_FF_OUT))) + dsum
+        out.append(ops.xlnet_dh_(dqkv, planes, dh0.clone()))
+        h1, sv = ops.xlnet_attn_block_fwd(h, planes, prm["o"], kr, prm["r_w_bias"], prm["r_r_bias"], prm["ln_w"], prm["ln_b"], B, L,
+                                          n, 0.03, drop_p=p_drop, seed=seed, ctr_prob=ctr(ops.SITE_PROB),
+                                          ctr_out=ctr(ops.SITE_ATTN_OUT))
+        out += [h1] + [sv[k] for k in ("qkv", "av", "lse", "ao", "mean", "rstd")]
+        prev = ops.set_precision("fp32_bf16x3")
+        try:
+            out.append(ops.gemm(ga, gb, trans_a=True, splitk=-1, accumulate=True, out=c0.clone()))
+        finally:
+            ops.set_precision(prev)
+        torch.cuda.synchronize()
+        return out
+
+    first = stand_alone()
+    flags = 1 | ops.LAYER_FUSE_INPUT | ops.LAYER_FUSE_FINAL
+    kw = dict(drop_p=p_drop, seed=seed, offset=3, layer_idx=flags)
+    out, ws = ops.xlnet_layer_fwd(h, pos, params, B, L, n, 0.03, **kw)
+    grads = [torch.zeros_like(t) for t in params]
+    dh = ops.xlnet_layer_bwd(h, pos, params, grads, ws, dy, B, L, n, 0.03, **kw)
+    torch.cuda.synchronize()
+    assert float((out == 0).float().mean()) > 0.05 and float((dh == 0).float().mean()) > 0.05      # both fused sites were active
+    again = stand_alone()
+    assert len(first) == len(again) == 22
+    for i, (a, b) in enumerate(zip(first, again)):
+        assert a.data_ptr() != b.data_ptr() and torch.equal(a, b), i

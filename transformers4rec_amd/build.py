@@ -43,7 +43,8 @@ def _stale(target, deps):
 def build(force=False, verbose=False):
     os.makedirs(LIBDIR, exist_ok=True)
     hipcc = _hipcc()
-    hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    inc = os.path.join(os.path.dirname(HERE), "include")       # the public headers: the sources that define their entries include them
+    hdrs = [os.path.join(d, f) for d in (CSRC, inc) for f in os.listdir(d) if f.endswith(".h")]
     objs, jobs = [], []
     for s in SOURCES:
         src = os.path.join(CSRC, s)

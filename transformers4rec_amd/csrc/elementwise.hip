@@ -6,7 +6,8 @@
 //   column sums                   : bias gradients
 //   fused Adam                    : torch.optim.Adam semantics (reference Model.fit, torch/model/base.py:669-718)
 // All are one pass over their operands with 16-byte accesses where the row width allows.
-#include "t4r_common.h"
+#include "t4r_internal.h"
+#include "../../include/t4r_hip.h"
 #include "adam_kernel.h"
 // ---------------------------------------------------------------- residual + LayerNorm fwd
 template <int VEC>
@@ -172,8 +173,6 @@ void t4r_reduce_redirect(hipStream_t side, hipEvent_t* events, int n_events) {
     g_red_side = side; g_red_events = events; g_red_n = side ? n_events : 0; g_red_used = 0;
 }
 
-bool t4r_splitk_sink_add_reduce(const float* part, int nblocks, int n, float* const* outs, const int* lens, const int* accs,
-                                int n_seg);     // gemm_f32.hip
 int t4r_reduce_partials_launch(hipStream_t st, const float* part, int nblocks, float* o0, int n0, int a0,
                                float* o1, int n1, int a1, float* o2, int n2, int a2) {
     const int n = n0 + n1 + n2;

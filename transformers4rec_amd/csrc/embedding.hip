@@ -14,7 +14,7 @@
 //   ElementwiseSum / ElementwiseSumItemMulti                torch/tabular/aggregation.py:140-193
 //   MaskSequence.apply_mask_to_inputs (MLM / CLM variants)  torch/masking.py:302-337,473-498
 //   _pad_ragged_tensor / pad_inputs                         torch/utils/padding.py:48-68,126-164
-#include "t4r_common.h"
+#include "t4r_internal.h"
 
 #define T4R_MAX_FEATS 16
 #define T4R_SOFT_MAXK 32
@@ -473,8 +473,6 @@ static void apply_mask_bwd_launch(hipStream_t st, const float* src, float* dst, 
     else hipLaunchKernelGGL(apply_mask_bwd_kernel, dim3(nblk), dim3(256), 0, st, src, dst, mask, ws, ntok, L, H, mode);
 }
 
-int t4r_reduce_partials_launch(hipStream_t st, const float* part, int nblocks, float* o0, int n0, int a0,
-                               float* o1, int n1, int a1, float* o2, int n2, int a2);   // elementwise.hip
 extern "C" long t4r_apply_mask_bwd_ws_floats(int B, int L, int H) {
     return (((long)B * L + T4R_MASK_BWD_TOK - 1) / T4R_MASK_BWD_TOK) * H;
 }
@@ -791,8 +789,6 @@ extern "C" long t4r_soft_embedding_bwd_ws_floats(long ntok, int K, int D) {
 }
 
 // ws: t4r_soft_embedding_bwd_ws_floats(ntok, K, D) floats of scratch (per-workgroup partial sums)
-int t4r_reduce_partials_launch(hipStream_t st, const float* part, int nblocks, float* o0, int n0, int a0,
-                               float* o1, int n1, int a1, float* o2, int n2, int a2);   // elementwise.hip
 extern "C" int t4r_soft_embedding_bwd(void* stream, const float* dout, const float* x,
                                       const float* proj_w, const float* proj_b, const float* table,
                                       const float* ln_w, float* d_proj_w, float* d_proj_b,

@@ -2,6 +2,8 @@
 // The kernel template lives in gemm_kernel.h (shared with gemm_half.hip, which instantiates the
 // bf16 / fp16 matrix-core variants in its own translation unit).
 #include "gemm_kernel.h"
+#include "t4r_internal.h"
+#include "../../include/t4r_hip.h"
 #include <atomic>
 
 // k-tile depth of the fp32 form: 16.  BK = 32 (16 MFMAs per barrier) won isolated long-K launches (square 111 ->
@@ -73,8 +75,6 @@ extern "C" int t4r_get_precision(void) {
     }
     return m;
 }
-int t4r_gemm_half_dispatch(const GemmParams& p, int batch, int ta, int tb, int bm, int bn, int prec, hipStream_t stream);   // gemm_half.hip
-int t4r_tok_gemm_try(const GemmParams& p, int batch, int ta, int tb, hipStream_t stream);     // tok_gemm.hip
 
 // shapes on which the split form beat the fp32 matrix cores (tools/gemm_bench.py --prec, profiles/r02_*)
 constexpr double kAutoSplitMinFlop = 2e9;
@@ -198,33 +198,15 @@ bool t4r_splitk_sink_add_reduce(const float* part, int nblocks, int n, float* co
     return true;
 }
 
-// operand maxima of the NEXT launch (device words: bits of max |A|, max |B|): a launch that would run in the three-plane
-// bf16 form runs in the two-way fp16 form instead (gemm_kernel.h: PREC 4).  Consumed by that launch.
-static thread_local const float* g_amax_a = nullptr;
-static thread_local const float* g_amax_b = nullptr;
-static thread_local int g_amax_n = 0, g_amax_nb = 0;
-void t4r_gemm_operand_amax(const float* a, const float* b, int n) { g_amax_a = a; g_amax_b = b; g_amax_n = g_amax_nb = n; }
-void t4r_gemm_operand_amax2(const float* a, int na, const float* b, int nb) { g_amax_a = a; g_amax_b = b; g_amax_n = na; g_amax_nb = nb; }
-
-#ifdef T4R_EXPERIMENTAL     /* tools/experimental/wgrad_stream.hip: the K-streaming weight-gradient kernel (measured slower inside the step) */
-void t4r_wgrad_stream_plan(int K, int* splits, int* kper);
-bool t4r_wgrad_stream_ok(const GemmParams& p);
-int t4r_wgrad_stream_launch(const GemmParams& p, int batch, int kper, float* part, hipStream_t st);
-// tools/experimental/wgrad_units.hip: read-once, cut-once 128 x 128 units in the two-way fp16 form (T4R_WGRAD_UNITS=1)
-void t4r_wgrad_units_plan(int K, int* splits, int* kper);
-bool t4r_wgrad_units_ok(const GemmParams& p);
-int t4r_wgrad_units_launch(const GemmParams& p, int batch, int kper, float* part, hipStream_t st);
-#endif
-
+// amax (null: none): the operand maxima of this launch (t4r_internal.h: GemmAmax)
 // force_fp32 (the fused top-k head only: t4r_gemm_fp32_nt_launch / t4r_gemm_topk_collect_launch): this launch runs form 0
 // whatever the process-wide mode says, so that its outputs carry the bits of the materialised fp32 scores
 template <bool TA, bool TB>
-static int launch_layout(GemmParams& p, int batch, int splitk_req, hipStream_t stream, bool force_fp32 = false) {
+static int launch_layout(GemmParams& p, int batch, int splitk_req, hipStream_t stream, const GemmAmax* amax, bool force_fp32) {
     auto launch_precision = [&]() { return force_fp32 ? 0 : t4r_get_precision(); };
-    const float* amax_a = g_amax_a;
-    const float* amax_b = g_amax_b;
-    const int amax_n = g_amax_n, amax_nb = g_amax_nb;
-    g_amax_a = g_amax_b = nullptr;
+    const float* amax_a = amax ? amax->a : nullptr;
+    const float* amax_b = amax ? amax->b : nullptr;
+    const int amax_n = amax ? amax->na : 0, amax_nb = amax ? amax->nb : 0;
     p.amaxA = p.amaxB = nullptr; p.n_amax = p.n_amax_b = 0;
 #ifdef T4R_EXPERIMENTAL
     // long-K weight gradients with a split-K sink installed (the XLNet layer backward): the K-streaming kernel (wgrad_stream.hip)
@@ -330,8 +312,9 @@ static int gemm_launch_impl(hipStream_t stream, int transA, int transB, int M, i
                             const float* A, long lda, const float* B, long ldb, float* C, long ldc,
                             const float* bias, int epilogue, float* aux, long ldaux, int splitk,
                             int accumulate, int batch, long sA, long sB, long sC, const DropCfg* drop,
-                            const SoftmaxGradA* sg, const RankEpi* rank, const TopkEpi* topk, bool force_fp32) {
-    if (M <= 0 || N <= 0) { g_amax_a = g_amax_b = nullptr; return 0; }     // operand maxima announced for THIS launch die with it
+                            const SoftmaxGradA* sg, const RankEpi* rank, const TopkEpi* topk, bool force_fp32,
+                            const GemmAmax* amax = nullptr) {
+    if (M <= 0 || N <= 0) return 0;
     T4R_CHECK_ARG(K > 0 && A && B && C && batch >= 1, "gemm: bad arguments");
     GemmParams p;
     p.M = M; p.N = N; p.K = K;
@@ -360,20 +343,20 @@ static int gemm_launch_impl(hipStream_t stream, int transA, int transB, int M, i
         p.sg_rows = sg->rows; p.sg_V = sg->V; p.sg_smooth = sg->smooth; p.sg_yoff = sg->yoff;
     }
     if (transA) {
-        if (transB) return launch_layout<true, true>(p, batch, splitk, stream, force_fp32);
-        return launch_layout<true, false>(p, batch, splitk, stream, force_fp32);
+        if (transB) return launch_layout<true, true>(p, batch, splitk, stream, amax, force_fp32);
+        return launch_layout<true, false>(p, batch, splitk, stream, amax, force_fp32);
     }
-    if (transB) return launch_layout<false, true>(p, batch, splitk, stream, force_fp32);
-    return launch_layout<false, false>(p, batch, splitk, stream, force_fp32);
+    if (transB) return launch_layout<false, true>(p, batch, splitk, stream, amax, force_fp32);
+    return launch_layout<false, false>(p, batch, splitk, stream, amax, force_fp32);
 }
 
 // Internal C++ entry used by the composite (layer / head) launchers.
 int t4r_gemm_launch(hipStream_t stream, int transA, int transB, int M, int N, int K, float alpha,
                     const float* A, long lda, const float* B, long ldb, float* C, long ldc,
                     const float* bias, int epilogue, float* aux, long ldaux, int splitk,
-                    int accumulate, int batch, long sA, long sB, long sC, const DropCfg* drop) {
+                    int accumulate, int batch, long sA, long sB, long sC, const DropCfg* drop, const GemmAmax* amax) {
     return gemm_launch_impl(stream, transA, transB, M, N, K, alpha, A, lda, B, ldb, C, ldc, bias, epilogue, aux, ldaux, splitk,
-                            accumulate, batch, sA, sB, sC, drop, nullptr, nullptr, nullptr, false);
+                            accumulate, batch, sA, sB, sC, drop, nullptr, nullptr, nullptr, false, amax);
 }
 
 extern "C" int t4r_gemm_f32(void* stream, int transA, int transB, int M, int N, int K, float alpha,

@@ -10,6 +10,7 @@
 //   128 x 64   PREC 1, plain launches of >= 2e10 FLOP, all four layouts
 //   128 x 128  PREC 2 / 3, the plain NT logits product (the three-plane images of such a tile would take 101 KB of LDS)
 #include "gemm_kernel.h"
+#include "t4r_internal.h"
 
 // the 64 x 64 forms: the A-operand transform or epilogue of the launch picks FEAT.  The layout error is a guard kept on purpose
 // (gemm_f32.hip: launch_cfg says why): launch_layout sends a softmax-gradient launch with transB = 1 to fp32.

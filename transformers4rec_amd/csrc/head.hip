@@ -10,7 +10,7 @@
 //   top-k at inference                           :466-470
 // HBM-bound: the [N, V] matrix is read exactly once per pass with 16-byte loads; one
 // workgroup per row, online (max, sum-exp) per thread then a workgroup reduction.
-#include "t4r_common.h"
+#include "t4r_internal.h"
 
 __device__ __forceinline__ void online_merge(float& m, float& s, float m2, float s2) {
     const float mn = fmaxf(m, m2);
@@ -250,10 +250,6 @@ __global__ __launch_bounds__(256) void sampled_fix_kernel(const float* __restric
 __global__ __launch_bounds__(256) void sampled_rows_kernel(const float* __restrict__ W, const long* __restrict__ ids,
                                                             float* __restrict__ out, float* __restrict__ dW,
                                                             const float* __restrict__ add, int n, int D);
-int t4r_gemm_launch(hipStream_t stream, int transA, int transB, int M, int N, int K, float alpha,
-                    const float* A, long lda, const float* B, long ldb, float* C, long ldc,
-                    const float* bias, int epilogue, float* aux, long ldaux, int splitk,
-                    int accumulate, int batch, long sA, long sB, long sC, const DropCfg* drop);
 
 // ws: n_neg * D floats of scratch (NULL: the row-wise kernel)
 extern "C" int t4r_sampled_logits_fwd(void* stream, const float* x, const long* labels, const float* W,
@@ -315,10 +311,6 @@ extern "C" int t4r_log_uniform_sample(void* stream, long* out, int n, long min_i
 //   d W_neg  = (1/T) G_neg^T[S,N] @ x[N,D]            then added to the S rows of dW
 // after the accidental-hit entries of G were zeroed in place; the positive column (one row of W per
 // label) stays a row-wise kernel with atomics on dW[y] (labels rarely collide).
-int t4r_gemm_launch(hipStream_t stream, int transA, int transB, int M, int N, int K, float alpha,
-                    const float* A, long lda, const float* B, long ldb, float* C, long ldc,
-                    const float* bias, int epilogue, float* aux, long ldaux, int splitk,
-                    int accumulate, int batch, long sA, long sB, long sC, const DropCfg* drop);
 
 __global__ __launch_bounds__(256) void sampled_mask_hits_kernel(float* __restrict__ g, const long* __restrict__ y,
                                                                  const long* __restrict__ neg, int N, int S) {
@@ -609,14 +601,6 @@ extern "C" int t4r_topk(void* stream, const float* scores, int N, int V, long ld
 // it to the two gradient contractions whose A operand forms the softmax gradient on the fly
 // (t4r_gemm_softmax_grad_launch): neither the logits nor their gradient ever exist at [N, V].
 //   stats: m[N] | s[N] | tot[N] | tgt[N]   (running max, sum exp(x - m), sum x, logit of the label)
-int t4r_gemm_launch(hipStream_t stream, int transA, int transB, int M, int N, int K, float alpha,
-                    const float* A, long lda, const float* B, long ldb, float* C, long ldc,
-                    const float* bias, int epilogue, float* aux, long ldaux, int splitk,
-                    int accumulate, int batch, long sA, long sB, long sC, const DropCfg* drop);
-int t4r_gemm_softmax_grad_launch(hipStream_t stream, int transA, int n_rows, int Vc, int V, int yoff, int N,
-                                 float alpha, const float* logits, long ld_logits, const float* lse,
-                                 const long* labels, const float* grad_out, float label_smoothing, const float* B,
-                                 long ldb, float* C, long ldc, int splitk, int accumulate);
 
 // one workgroup per row: online softmax statistics of the chunk's Vc columns merged into the running ones
 __global__ __launch_bounds__(256) void ce_chunk_stats_kernel(const float* __restrict__ chunk, long ld, int Vc,

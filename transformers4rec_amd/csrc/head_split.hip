@@ -33,6 +33,7 @@
 // k = 16 s + 8 (lane >> 5) + i, i = position in the lane's 16 bytes -- the same map for A and B, so any
 // consistent order is a valid contraction order.
 #include "gemm_kernel.h"
+#include "t4r_internal.h"
 
 namespace {
 
@@ -1677,7 +1678,6 @@ extern "C" int t4r_head_split_logits(void* stream, void* ws, const float* W, lon
 
 // logits + mean cross-entropy in one pass over the vocabulary: C as t4r_head_split_logits, plus loss_rows [N], lse [N]
 // and (optional) the mean loss -- replaces t4r_softmax_ce_fwd on the materialised logits
-int t4r_mean_launch(hipStream_t stream, const float* x, int n, float* out);      // head.hip
 extern "C" int t4r_head_split_logits_ce(void* stream, void* ws, const float* W, long ldw, float* C, long ldc,
                                         const long* labels, float* loss_rows, float* lse, float* loss_mean, int N, int V,
                                         int D, float alpha, float label_smoothing, void* note) {

@@ -27,15 +27,7 @@
 // The SAMPLING form of the same call (t4r_item_sample_f32, include/t4r_hip_sampling.h) is the same four steps over the
 // perturbed score fp32(s + g(row, item)) (gumbel_noise.h): ItkNoisyHead (item_topk_plan.h) around this head.
 #include "item_topk_plan.h"
-
-int t4r_gemm_fp32_nt_launch(hipStream_t stream, int M, int N, int K, float alpha, const float* A, long lda,
-                            const float* B, long ldb, float* C, long ldc);
-int t4r_gemm_topk_collect_launch(hipStream_t stream, int n_rows, int V, int D, float alpha, const float* X, long ldx,
-                                 const float* W, long ldw, const float* thr, long thr_ld, int* count, float* cand_val,
-                                 int* cand_idx, int cap, const GumbelCfg* noise);
-int t4r_gemm_topk_collect_filtered_launch(hipStream_t stream, int n_rows, int V, int D, float alpha, const float* X, long ldx,
-                                          const float* W, long ldw, const float* thr, long thr_ld, int* count, float* cand_val,
-                                          int* cand_idx, int cap, const GumbelCfg* noise, const ItkFilter* filt);
+#include "t4r_internal.h"
 
 namespace {
 

@@ -16,18 +16,10 @@
 // read as wave-uniform broadcasts.  Forward = one online-softmax pass saving the row
 // log-sum-exp; backward recomputes the probabilities twice (once per phase) instead of
 // storing an [L, L] tile, so LDS holds only 4 * L * (dh + 4) floats (109 KB at L=100, dh=64).
-#include "t4r_common.h"
+#include "t4r_internal.h"
+#include "../../include/t4r_hip.h"
 
 #define MHA_PAD 4
-
-// mha_mfma.hip: matrix-core kernels for d_head 32 / 64
-bool t4r_mha_mfma_ok(int L, int d_head, long ld, long ld_out, long ld_d);
-int t4r_mha_mfma_fwd(hipStream_t st, const float* q, const float* k, const float* v, long ld, float* out,
-                     long ld_out, float* lse, int B, int L, int n_head, int d_head, float scale, int causal,
-                     DropCfg drop, const int* key_len);
-int t4r_mha_mfma_bwd(hipStream_t st, const float* q, const float* k, const float* v, long ld, const float* out,
-                     const float* dout, long ld_out, const float* lse, float* dq, float* dk, float* dv, long ld_d,
-                     int B, int L, int n_head, int d_head, float scale, int causal, DropCfg drop, const int* key_len);
 
 template <int DH>
 __global__ __launch_bounds__(128) void mha_fwd_kernel(
@@ -237,13 +229,7 @@ static int mha_bwd_launch(hipStream_t st, const float* q, const float* k, const 
 
 // q,k,v: rows of `ld` floats (ld = 3*D for GPT-2's fused c_attn output, D for separate buffers),
 // head h at columns [h*d_head, (h+1)*d_head).  out/dout rows of ld_out floats.  lse [B, n, L].
-// general kernels (xlnet_attn_long.hip): any L, d_head up to 256
-int t4r_mha_long_ok(int L, int d_head);
-int t4r_mha_long_fwd(hipStream_t st, const float* q, const float* k, const float* v, long ld, float* out, long ld_out, float* lse,
-                     int B, int L, int n_head, int d_head, float scale, int causal, DropCfg drop, const int* key_len);
-int t4r_mha_long_bwd(hipStream_t st, const float* q, const float* k, const float* v, long ld, const float* out, const float* dout,
-                     long ld_out, const float* lse, float* dq, float* dk, float* dv, long ld_d, int B, int L, int n_head,
-                     int d_head, float scale, int causal, DropCfg drop, const int* key_len);
+// (the matrix-core kernels of mha_mfma.hip and the general ones of xlnet_attn_long.hip -- any L, d_head up to 256: t4r_internal.h)
 static bool mha_short_ok(int L, int d_head) { return L <= 128 && (d_head == 16 || d_head == 32 || d_head == 64); }
 
 extern "C" int t4r_mha_fwd(void* stream, const float* q, const float* k, const float* v, long ld, float* out,

@@ -17,7 +17,7 @@
 // resident).  P is recomputed from the saved log-sum-exp, D_i = dO_i . O_i parks in LDS.
 // Measured before this kernel (BERT-like B 256, L 100, 8 heads x 64): mha_bwd 2.0 ms, mha_fwd
 // 0.47 ms per layer.
-#include "t4r_common.h"
+#include "t4r_internal.h"
 
 #include "mfma_frag.h"
 

@@ -16,6 +16,7 @@
 // Grid: (token tiles of 128, column groups of NBW x 32 columns, batch).  Epilogues and dropout-mask indexing are the
 // general kernel's (same C fragment layout: lane = column, registers = rows), so masks and results line up with it.
 #include "gemm_kernel.h"
+#include "t4r_internal.h"
 #include <atomic>
 
 namespace {

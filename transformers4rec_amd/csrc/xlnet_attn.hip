@@ -16,7 +16,9 @@
 // reads for the lane-dependent k_r row j+L-i; k_j / v_j rows are wave-uniform broadcasts).
 // Forward is a single online-softmax pass and saves only the row log-sum-exp; backward
 // recomputes the probabilities (no [B,n,L,L] tensor ever goes to HBM).
-#include "t4r_common.h"
+#include "t4r_internal.h"
+#include "../../include/t4r_hip.h"
+#include "../../include/t4r_hip_attn.h"
 // additive score of a masked key (opt-in padding mask): HF modeling_xlnet.py subtracts 1e30 * attn_mask in fp32
 #define T4R_KEY_MASKED (-1e30f)
 #include <stdlib.h>
@@ -496,9 +498,6 @@ __global__ __launch_bounds__(64) void xlnet_attn_bwd_pairs_kernel(
     }
 }
 
-int t4r_reduce_partials_launch(hipStream_t st, const float* part, int nblocks, float* o0, int n0, int a0,
-                               float* o1, int n1, int a1, float* o2, int n2, int a2);
-
 static size_t attn_fwd_smem(int L, int D) { return (size_t)(4 * L) * (D + ATT_PAD) * sizeof(float); }
 static size_t attn_bwd_smem(int L, int D, int n, int per_batch_kr = 0) {
     return ((size_t)((per_batch_kr ? 6 : 8) * L) * (D + ATT_PAD) + (size_t)2 * n * L * (L + 1) + 2 * D) * sizeof(float);
@@ -509,7 +508,6 @@ static long attn_bwd_part_floats(int B, int L, int D, int n_head) {
     const int hpb = (D / n_head) >= 32 ? 4 : 8;
     return (long)t4r_xlnet_attn_bwd_blocks(B) * ((n_head + hpb - 1) / hpb) * (2L * L * D + 2L * D);
 }
-int t4r_xlnet_attn_mfma_ok(int L, int d_head);
 // Which shapes leave the one-wave kernels for the general ones of xlnet_attn_long.hip: more than 64 positions, a head width
 // without an instance, or (VALU kernels only: 32 < L <= 64, or d_head 8) a session whose K / V / k_r rows do not fit the LDS.
 // dir: 0 forward, 1 backward with the shared k_r, 2 backward with per-session k_r, 3 either backward form
@@ -528,33 +526,8 @@ static bool attn_uses_long(int L, int D, int n_head, int dir) {
 extern "C" long t4r_xlnet_attn_bwd_ws_floats(int B, int L, int D, int n_head) {
     return attn_bwd_part_floats(B, L, D, n_head) + (attn_uses_long(L, D, n_head, 3) ? (long)B * n_head * L : 0L);
 }
-int t4r_xlnet_attn_long_ok(int L, int d_head);
-int t4r_xlnet_attn_long_fwd(hipStream_t st, const float* q, const float* k, const float* v, const float* kr, const float* rw,
-                            const float* rr, float* out, float* lse, int B, int L, int n_head, int d_head, float scale,
-                            long kr_bstride, DropCfg drop, const int* key_len);
-int t4r_xlnet_attn_long_bwd(hipStream_t st, const float* q, const float* k, const float* v, const float* kr, const float* rw,
-                            const float* rr, const float* out, const float* lse, const float* dout, float* dq, float* dk,
-                            float* dv, float* part, float* delta, float* dkr, float* d_rw, float* d_rr, int B, int L, int n_head,
-                            int d_head, float scale, long kr_bstride, DropCfg drop, const int* key_len);
-
-// MFMA kernels for L <= 32, d_head 16 / 32 (xlnet_attn_mfma.hip); T4R_ATTN_MFMA=0 keeps the VALU kernels
-int t4r_xlnet_attn_mfma_ok(int L, int d_head);
-int t4r_xlnet_attn_mfma_fwd(hipStream_t st, const float* q, const float* k, const float* v, const float* kr,
-                            const float* rw, const float* rr, float* out, float* lse, int B, int L, int n_head,
-                            int d_head, float scale, long kr_bstride, DropCfg drop, const int* key_len);
-int t4r_xlnet_attn_mfma_bwd(hipStream_t st, const float* q, const float* k, const float* v, const float* kr,
-                            const float* rw, const float* rr, const float* lse, const float* prob, const float* dout,
-                            float* dq, float* dk, float* dv, float* part, float* dkr, float* d_rw, float* d_rr, int B,
-                            int L, int n_head, int d_head, float scale, long kr_bstride, DropCfg drop, const int* key_len);
-#ifdef T4R_EXPERIMENTAL
-// the fp32-MFMA core with the permuted k-slots (tools/experimental: phase 3 of the one-kernel backward as its own launch;
-// measured slower than xlnet_attn_mfma_bwd_kernel, not in the product library)
-int t4r_xlnet_attn_core16_ok(int L, int D, int n_head);
-int t4r_xlnet_attn_core16_bwd(hipStream_t st, const float* qkv, const float* kr, const float* rw, const float* rr,
-                              const float* lse, const float* dout, float* dqkv, float* part, float* dkr, float* d_rw,
-                              float* d_rr, int B, int L, int n_head, int d_head, float scale, long kr_bstride, DropCfg drop,
-                              const int* key_len);
-#endif
+// (the general kernels of xlnet_attn_long.hip and the MFMA kernels for L <= 32, d_head 16 / 32 of xlnet_attn_mfma.hip --
+// T4R_ATTN_MFMA=0 keeps the VALU kernels: t4r_internal.h)
 static bool use_mfma(int L, int d_head) {
     static int en = -1;
     if (en < 0) { const char* e = t4r_exp_getenv("T4R_ATTN_MFMA"); en = e ? atoi(e) : 1; }

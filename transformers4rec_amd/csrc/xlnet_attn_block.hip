@@ -32,6 +32,8 @@
 // LayerNorm, with q, k, v, attn_vec making a round trip through HBM between them) took 55 us per layer for 22 us of
 // fp32 matrix time.  In one kernel the matrix pipe is the bound: measured numbers in docs/DESIGN_rounds_1_to_4.md (4.1d).
 #include "xlnet_fused.h"
+#include "../../include/t4r_hip.h"
+#include "../../include/t4r_hip_attn.h"
 
 namespace {
 
@@ -655,7 +657,6 @@ __global__ __launch_bounds__(D * 4) void xlnet_attn_block_fwd_kernel(AttnBlockFw
 #endif
 
 // ------------------------------------------------------------------------------------------------ host side (forward)
-extern "C" int t4r_xlnet_fused_supported(int D);
 static size_t attn_block_smem(int D) { return ((size_t)AB_RT * (3 * D + 4) + (size_t)(D / 16) * 16 * AB_PR) * sizeof(float); }
 
 // 1 when the attention half of a layer of this shape runs as the one-kernel-per-direction block of this file
@@ -671,21 +672,16 @@ static int attn_block_sessions(int L) { return AB_RT / L; }
 // attn_vec av [T][D], lse [B][n_head][L] and (training: ao != NULL) ao [T][D], mean / rstd [T] for the backward.
 // planes: t4r_xlnet_layer_prepare's buffer (its fp32 transposes); o: the layer's o weight [D][n_head][d_head] as stored;
 // kr: k_r = pos_emb @ r, [2 L][D] (kr_bstride 0) or per session [B][2 L][D] (kr_bstride 2 L D).
-// set and cleared inside one layer call (csrc/xlnet_layer.hip, T4R_LAYER_FUSE_INPUT): the next t4r_xlnet_attn_block_fwd of this
-// thread applies the model-level input dropout keyed by `ctr` to h on load and leaves the dropped rows in `hin`
-static thread_local int g_ab_in_on = 0;
-static thread_local unsigned long long g_ab_in_ctr = 0;
-static thread_local float* g_ab_hin = nullptr;
-void t4r_xlnet_attn_block_input_dropout(int on, unsigned long long ctr, float* hin) { g_ab_in_on = on; g_ab_in_ctr = ctr; g_ab_hin = hin; }
 // prob: null, or [B][n_head][L][L] fp32, 16-byte aligned: the attention probabilities before dropout (exact zeros at masked
-// columns) are stored there for the core's backward.  An internal entry: the layer (xlnet_layer.hip) and the two public ones
-// below call it.
+// columns) are stored there for the core's backward.  in_on (the first layer of a stack, T4R_LAYER_FUSE_INPUT): the model-level
+// input dropout keyed by in_ctr is applied to h on load and the dropped rows are left in hin.  An internal entry
+// (t4r_internal.h): the layer (xlnet_layer.hip) and the two public ones below call it.
 int t4r_xlnet_attn_block_fwd_impl(void* stream, const float* h, const float* planes, const float* o, const float* kr,
                                   long kr_bstride, const float* r_w_bias, const float* r_r_bias, const float* gamma,
                                   const float* beta, float* qkv, float* av, float* lse, float* prob, float* ao, float* mean,
                                   float* rstd, float* h1, int B, int L, int D, int n_head, float eps, float drop_p,
                                   unsigned long long seed, unsigned long long ctr_prob, unsigned long long ctr_out,
-                                  const int* key_len) {
+                                  const int* key_len, int in_on, unsigned long long in_ctr, float* hin) {
     if (B <= 0) return 0;
     T4R_CHECK_ARG((reinterpret_cast<uintptr_t>(prob) & 15) == 0, "xlnet_attn_block_fwd: prob must be 16-byte aligned");
     T4R_CHECK_ARG(t4r_xlnet_attn_block_supported(L, D, n_head), "xlnet_attn_block_fwd: unsupported shape (L <= 32, d_head 16 / 32, d_model 32 / 64 / 128)");
@@ -707,9 +703,9 @@ int t4r_xlnet_attn_block_fwd_impl(void* stream, const float* h, const float* pla
     p.scale = 1.0f / sqrtf((float)dh); p.eps = eps;
     p.drop_p = make_drop(drop_p, seed, ctr_prob);
     p.drop_o = make_drop(drop_p, seed, ctr_out);
-    p.drop_in = make_drop(g_ab_in_on ? drop_p : 0.f, seed, g_ab_in_ctr);
-    p.hin = g_ab_in_on ? g_ab_hin : nullptr;
-    T4R_CHECK_ARG(!(g_ab_in_on && drop_p > 0.f) || p.hin, "xlnet_attn_block_fwd: the fused input dropout needs its output buffer");
+    p.drop_in = make_drop(in_on ? drop_p : 0.f, seed, in_ctr);
+    p.hin = in_on ? hin : nullptr;
+    T4R_CHECK_ARG(!(in_on && drop_p > 0.f) || p.hin, "xlnet_attn_block_fwd: the fused input dropout needs its output buffer");
 #ifdef T4R_AB_STAMPS
     p.stamps = g_ab_stamps;
 #endif
@@ -750,7 +746,8 @@ extern "C" int t4r_xlnet_attn_block_fwd(void* stream, const float* h, const floa
                                         unsigned long long seed, unsigned long long ctr_prob, unsigned long long ctr_out,
                                         const int* key_len) {
     return t4r_xlnet_attn_block_fwd_impl(stream, h, planes, o, kr, kr_bstride, r_w_bias, r_r_bias, gamma, beta, qkv, av, lse, nullptr,
-                                         ao, mean, rstd, h1, B, L, D, n_head, eps, drop_p, seed, ctr_prob, ctr_out, key_len);
+                                         ao, mean, rstd, h1, B, L, D, n_head, eps, drop_p, seed, ctr_prob, ctr_out, key_len,
+                                         0, 0, nullptr);
 }
 // include/t4r_hip_attn.h
 extern "C" int t4r_xlnet_attn_block_fwd_prob(void* stream, const float* h, const float* planes, const float* o, const float* kr,
@@ -760,7 +757,8 @@ extern "C" int t4r_xlnet_attn_block_fwd_prob(void* stream, const float* h, const
                                              float drop_p, unsigned long long seed, unsigned long long ctr_prob,
                                              unsigned long long ctr_out, const int* key_len) {
     return t4r_xlnet_attn_block_fwd_impl(stream, h, planes, o, kr, kr_bstride, r_w_bias, r_r_bias, gamma, beta, qkv, av, lse, prob,
-                                         ao, mean, rstd, h1, B, L, D, n_head, eps, drop_p, seed, ctr_prob, ctr_out, key_len);
+                                         ao, mean, rstd, h1, B, L, D, n_head, eps, drop_p, seed, ctr_prob, ctr_out, key_len,
+                                         0, 0, nullptr);
 }
 
 #ifdef T4R_EXPERIMENTAL

@@ -21,7 +21,7 @@
 //   backward, rel    thread = relative position m:  d k_r[m] = sum_{i, j = m - L + i} dS_ij (q_i + r_r_bias)   (per session, or
 //                    summed over the sessions of the workgroup for the shared k_r: partials reduced in block order)
 // Batch-reduced gradients go through the same partial buffer and reduction launch as the short kernels: deterministic.
-#include "t4r_common.h"
+#include "t4r_internal.h"
 #include <stdlib.h>
 
 #define T4R_KEY_MASKED (-1e30f)
@@ -472,9 +472,6 @@ static int cap_of(int d_head) { return d_head <= 8 ? 8 : d_head <= 16 ? 16 : d_h
 
 }  // namespace
 
-int t4r_reduce_partials_launch(hipStream_t st, const float* part, int nblocks, float* o0, int n0, int a0,
-                               float* o1, int n1, int a1, float* o2, int n2, int a2);
-extern "C" int t4r_xlnet_attn_bwd_blocks(int B);
 
 // any L >= 1; head widths up to 256 (16-byte requests when the width is a multiple of 4, element by element otherwise; above 64
 // the per-thread vectors spill to scratch: slow, but these are the shapes nothing else takes)

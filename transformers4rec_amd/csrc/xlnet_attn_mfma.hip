@@ -22,7 +22,7 @@
 //   Operands whose k is the ROW index of a row-major matrix ("column fragment") are 128-byte
 //   coalesced scalar loads.  Only layout changes go through LDS (accumulator layout -> row layout,
 //   transposes, the rel_shift gather / scatter): ~12.5 KB per wave.
-#include "t4r_common.h"
+#include "t4r_internal.h"
 
 #include "mfma_frag.h"
 
@@ -480,8 +480,6 @@ __global__ __launch_bounds__(HAVE_P ? T4R_ATTN_BWD_P_BOUNDS : T4R_ATTN_BWD_BOUND
     }
 }
 
-int t4r_reduce_partials_launch(hipStream_t st, const float* part, int nblocks, float* o0, int n0, int a0,
-                               float* o1, int n1, int a1, float* o2, int n2, int a2);
 
 // internal entry points used by xlnet_attn.hip's dispatch (same argument meaning as the VALU kernels)
 int t4r_xlnet_attn_mfma_ok(int L, int d_head) { return L >= 1 && L <= 32 && (d_head == 16 || d_head == 32); }

@@ -2,20 +2,13 @@
 // xlnet_fused_attn.hip: the projections around the attention core): three-plane bf16 operands, the six-product MFMA
 // chain, the weight-plane layout of a layer.  See xlnet_fused.hip for the design.
 #pragma once
-#include "t4r_common.h"
+#include "t4r_internal.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-int t4r_reduce_partials_launch(hipStream_t st, const float* part, int nblocks, float* o0, int n0, int a0,
-                               float* o1, int n1, int a1, float* o2, int n2, int a2);   // elementwise.hip
-// token blocks (of 16 rows) per workgroup tile of the token-tile kernels for T rows (xlnet_fused.hip).  backward = true: the
-// launch may run next to a resident collective -- the CU budget of t4r_xlnet_set_cu_budget applies (forward launches never do)
-int t4r_xlnet_pick_r(long T, bool backward);
-bool t4r_xlnet_body_fp16x2();      // xlnet_fused.hip: the token-tile kernels on the two-way fp16 split (T4R_XLNET_FP16X2, default 1)?
 
 __device__ __forceinline__ f32x4 zero4() { f32x4 z = {0.f, 0.f, 0.f, 0.f}; return z; }
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }

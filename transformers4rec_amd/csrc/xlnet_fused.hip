@@ -34,6 +34,8 @@
 // activation-chunk planes [3][16R][D + 16] (written by the
 // FF1 epilogue, B operand of FF2; d_inner = 4 D is walked in four chunks of D, two barriers per chunk).
 #include "xlnet_fused.h"
+#include "../../include/t4r_hip.h"
+#include "../../include/t4r_hip_rows.h"
 #include <type_traits>
 
 struct FFFwdParams {
@@ -593,20 +595,6 @@ bool t4r_xlnet_body_fp16x2() {
     if (on < 0) { const char* e = t4r_exp_getenv("T4R_XLNET_FP16X2"); on = e ? (atoi(e) != 0) : 1; }
     return on != 0;
 }
-// Where the next t4r_xlnet_ff_fwd / _bwd calls of this thread leave their per-workgroup operand maxima (four arrays of
-// t4r_xlnet_ff_amax_slots(T) floats: max |h1|, max |act| from the forward, max |d pre|, max |d ffout| from the backward), or
-// nulls (default: stand-alone use).  The layer (xlnet_layer.hip) sets them and hands the arrays to its two feed-forward
-// weight-gradient launches, which then run in the two-way fp16 form (gemm_kernel.h: PREC 4).
-static thread_local float* g_ff_amax[4] = {nullptr, nullptr, nullptr, nullptr};
-// set and cleared inside one layer call (csrc/xlnet_layer.hip): the next t4r_xlnet_ff_fwd / _bwd of this thread also applies
-// the model-level output dropout keyed by `ctr` (the last layer of a stack: one launch less per direction and no extra pass
-// over [T, D]); 0 = off
-static thread_local unsigned long long g_ff_final_ctr = 0;
-static thread_local int g_ff_final_on = 0;
-void t4r_xlnet_ff_final_dropout(int on, unsigned long long ctr) { g_ff_final_on = on; g_ff_final_ctr = ctr; }
-void t4r_xlnet_ff_amax_buffers(float* h1, float* act, float* dpre, float* dfo) {
-    g_ff_amax[0] = h1; g_ff_amax[1] = act; g_ff_amax[2] = dpre; g_ff_amax[3] = dfo;
-}
 static int pick_r(long T) { return t4r_xlnet_pick_r(T, false); }
 int t4r_xlnet_ff_amax_count(long T) { const int R = pick_r(T); return (int)((T + 16 * R - 1) / (16 * R)); }   // workgroups of a forward launch
 int t4r_xlnet_ff_amax_count_bwd(long T) { const int R = t4r_xlnet_pick_r(T, true); return (int)((T + 16 * R - 1) / (16 * R)); }   // of a backward launch
@@ -735,11 +723,11 @@ static int ff_bwd_rows_launch(hipStream_t st, const FFBwdRowsParams& p) {
 // Fused feed-forward block, forward.  h1 [T, D] -> hout [T, D]; saves ffpre / ffact [T, 4D], ffout [T, D], mean / rstd [T]
 // for the backward when the pointers are given (all or none).  planes: the buffer t4r_xlnet_ff_prepare filled.
 // replaces: HF modeling_xlnet.py:297-305 (layer_1, activation, dropout, layer_2, dropout, layer_norm(output + inp))
-// rows != null: the row-mapped form on n rows (include/t4r_hip_rows.h)
-static int ff_fwd_impl(void* stream, const float* h1, const float* planes, const float* b1, const float* b2,
-                       const float* gamma, const float* beta, float* ffpre, float* ffact, float* ffout, float* mean,
-                       float* rstd, float* hout, int T, int D, float eps, float drop_p, unsigned long long seed,
-                       unsigned long long ctr_act, unsigned long long ctr_out, const int* rows, int n) {
+// rows != null: the row-mapped form on n rows (include/t4r_hip_rows.h).  opt: t4r_internal.h
+int t4r_xlnet_ff_fwd_impl(void* stream, const float* h1, const float* planes, const float* b1, const float* b2,
+                          const float* gamma, const float* beta, float* ffpre, float* ffact, float* ffout, float* mean,
+                          float* rstd, float* hout, int T, int D, float eps, float drop_p, unsigned long long seed,
+                          unsigned long long ctr_act, unsigned long long ctr_out, const int* rows, int n, const FFOpts& opt) {
     if (T <= 0) return 0;
     T4R_CHECK_ARG(t4r_xlnet_fused_supported(D), "xlnet_ff_fwd: d_model must be 32, 64 or 128");
     T4R_CHECK_ARG(h1 && planes && b1 && b2 && gamma && beta && hout, "xlnet_ff_fwd: null pointer");
@@ -747,10 +735,10 @@ static int ff_fwd_impl(void* stream, const float* h1, const float* planes, const
     T4R_CHECK_ARG((ffact != nullptr) == train && (ffout != nullptr) == train && (mean != nullptr) == train &&
                       (rstd != nullptr) == train, "xlnet_ff_fwd: ffpre, ffact, ffout, mean, rstd are saved together or not at all");
     T4R_CHECK_ARG(train || drop_p == 0.f, "xlnet_ff_fwd: dropout needs the saved activations (training mode)");
-    FFFwdParams p{h1, b1, b2, gamma, beta, carve_planes(planes, D), carve_planes_h(planes, D), g_ff_amax[0], g_ff_amax[1], ffpre, ffact, ffout,
+    FFFwdParams p{h1, b1, b2, gamma, beta, carve_planes(planes, D), carve_planes_h(planes, D), opt.amax0, opt.amax1, ffpre, ffact, ffout,
                   mean, rstd, hout, T, eps,
                   make_drop(drop_p, seed, ctr_act), make_drop(drop_p, seed, ctr_out),
-                  make_drop(g_ff_final_on ? drop_p : 0.f, seed, g_ff_final_ctr)};
+                  make_drop(opt.final_on ? drop_p : 0.f, seed, opt.final_ctr)};
     if (rows) {
         T4R_CHECK_ARG(n >= 1 && n <= T, "xlnet_ff_fwd_rows: the number of mapped rows must be in [1, T]");
         T4R_CHECK_ARG(t4r_xlnet_body_fp16x2(), "xlnet_ff_fwd_rows: the row-mapped kernels exist in the two-way fp16 form only");
@@ -772,8 +760,8 @@ extern "C" int t4r_xlnet_ff_fwd(void* stream, const float* h1, const float* plan
                                 const float* gamma, const float* beta, float* ffpre, float* ffact, float* ffout, float* mean,
                                 float* rstd, float* hout, int T, int D, float eps, float drop_p, unsigned long long seed,
                                 unsigned long long ctr_act, unsigned long long ctr_out) {
-    return ff_fwd_impl(stream, h1, planes, b1, b2, gamma, beta, ffpre, ffact, ffout, mean, rstd, hout, T, D, eps, drop_p, seed,
-                       ctr_act, ctr_out, nullptr, 0);
+    return t4r_xlnet_ff_fwd_impl(stream, h1, planes, b1, b2, gamma, beta, ffpre, ffact, ffout, mean, rstd, hout, T, D, eps, drop_p,
+                                 seed, ctr_act, ctr_out, nullptr, 0, FFOpts());
 }
 // include/t4r_hip_rows.h
 extern "C" int t4r_xlnet_ff_fwd_rows(void* stream, const float* h1, const float* planes, const float* b1, const float* b2,
@@ -783,20 +771,21 @@ extern "C" int t4r_xlnet_ff_fwd_rows(void* stream, const float* h1, const float*
                                      const int* rows, int n) {
     T4R_CHECK_ARG(rows != nullptr, "xlnet_ff_fwd_rows: null row map");
     T4R_CHECK_ARG(T >= 1, "xlnet_ff_fwd_rows: T must be positive");
-    return ff_fwd_impl(stream, h1, planes, b1, b2, gamma, beta, ffpre, ffact, ffout, mean, rstd, hout, T, D, eps, drop_p, seed,
-                       ctr_act, ctr_out, rows, n);
+    return t4r_xlnet_ff_fwd_impl(stream, h1, planes, b1, b2, gamma, beta, ffpre, ffact, ffout, mean, rstd, hout, T, D, eps, drop_p,
+                                 seed, ctr_act, ctr_out, rows, n, FFOpts());
 }
 
 // Fused feed-forward block, backward (input gradients + bias / LayerNorm parameter gradients; the two weight gradients
 // d W2 += d ffout^T @ ffact and d W1 += d pre^T @ h1 are token-reducing GEMMs the caller issues on the rows written here).
 //   dy [T, D] = d loss / d hout;  dh1 [T, D] (overwritten) = d loss / d h1;  dffout [T, D], dpre [T, 4D] (overwritten);
 //   d_gamma, d_beta, d_b2 [D], d_b1 [4D] ACCUMULATED;  part: t4r_xlnet_ff_bwd_part_floats(T, D) floats of scratch.
-static int ff_bwd_impl(void* stream, const float* dy, const float* ffout, const float* h1, const float* mean,
-                       const float* rstd, const float* gamma, const float* ffpre, const float* planes,
-                       float* dh1, float* dffout, float* dpre, float* d_gamma, float* d_beta,
-                       float* d_b2, float* d_b1, float* part, int T, int D, float drop_p,
-                       unsigned long long seed, unsigned long long ctr_act, unsigned long long ctr_out,
-                       const int* rows, int n, float* h1_rows) {
+// rows != null: the row-mapped form on n rows (include/t4r_hip_rows.h).  opt: t4r_internal.h
+int t4r_xlnet_ff_bwd_impl(void* stream, const float* dy, const float* ffout, const float* h1, const float* mean,
+                          const float* rstd, const float* gamma, const float* ffpre, const float* planes,
+                          float* dh1, float* dffout, float* dpre, float* d_gamma, float* d_beta,
+                          float* d_b2, float* d_b1, float* part, int T, int D, float drop_p,
+                          unsigned long long seed, unsigned long long ctr_act, unsigned long long ctr_out,
+                          const int* rows, int n, float* h1_rows, const FFOpts& opt) {
     if (T <= 0) return 0;
     T4R_CHECK_ARG(t4r_xlnet_fused_supported(D), "xlnet_ff_bwd: d_model must be 32, 64 or 128");
     T4R_CHECK_ARG(dy && ffout && h1 && mean && rstd && gamma && ffpre && planes && dh1 && dffout && dpre && part,
@@ -811,10 +800,10 @@ static int ff_bwd_impl(void* stream, const float* dy, const float* ffout, const 
     const int nwg = (Tk + 16 * R - 1) / (16 * R);
     float* partA = part;
     float* partB = part + (long)nwg * 3 * D;
-    FFBwdParams p{dy, ffout, h1, mean, rstd, gamma, ffpre, carve_planes(planes, D), carve_planes_h(planes, D), g_ff_amax[2], g_ff_amax[3], dh1,
+    FFBwdParams p{dy, ffout, h1, mean, rstd, gamma, ffpre, carve_planes(planes, D), carve_planes_h(planes, D), opt.amax0, opt.amax1, dh1,
                   dffout, dpre, partA, partB, T,
                   make_drop(drop_p, seed, ctr_act), make_drop(drop_p, seed, ctr_out),
-                  make_drop(g_ff_final_on ? drop_p : 0.f, seed, g_ff_final_ctr)};
+                  make_drop(opt.final_on ? drop_p : 0.f, seed, opt.final_ctr)};
     hipStream_t st = (hipStream_t)stream;
     auto launch = [&]() -> int {
         if (rows) {
@@ -842,8 +831,8 @@ extern "C" int t4r_xlnet_ff_bwd(void* stream, const float* dy, const float* ffou
                                 float* dh1, float* dffout, float* dpre, float* d_gamma, float* d_beta,
                                 float* d_b2, float* d_b1, float* part, int T, int D, float drop_p,
                                 unsigned long long seed, unsigned long long ctr_act, unsigned long long ctr_out) {
-    return ff_bwd_impl(stream, dy, ffout, h1, mean, rstd, gamma, ffpre, planes, dh1, dffout, dpre, d_gamma, d_beta, d_b2, d_b1,
-                       part, T, D, drop_p, seed, ctr_act, ctr_out, nullptr, 0, nullptr);
+    return t4r_xlnet_ff_bwd_impl(stream, dy, ffout, h1, mean, rstd, gamma, ffpre, planes, dh1, dffout, dpre, d_gamma, d_beta, d_b2,
+                                 d_b1, part, T, D, drop_p, seed, ctr_act, ctr_out, nullptr, 0, nullptr, FFOpts());
 }
 // include/t4r_hip_rows.h
 extern "C" int t4r_xlnet_ff_bwd_rows(void* stream, const float* dy, const float* ffout, const float* h1, const float* mean,
@@ -854,6 +843,6 @@ extern "C" int t4r_xlnet_ff_bwd_rows(void* stream, const float* dy, const float*
                                      float* h1_rows) {
     T4R_CHECK_ARG(rows != nullptr, "xlnet_ff_bwd_rows: null row map");
     T4R_CHECK_ARG(T >= 1, "xlnet_ff_bwd_rows: T must be positive");
-    return ff_bwd_impl(stream, dy, ffout, h1, mean, rstd, gamma, ffpre, planes, dh1, dffout, dpre, d_gamma, d_beta, d_b2, d_b1,
-                       part, T, D, drop_p, seed, ctr_act, ctr_out, rows, n, h1_rows);
+    return t4r_xlnet_ff_bwd_impl(stream, dy, ffout, h1, mean, rstd, gamma, ffpre, planes, dh1, dffout, dpre, d_gamma, d_beta, d_b2,
+                                 d_b1, part, T, D, drop_p, seed, ctr_act, ctr_out, rows, n, h1_rows, FFOpts());
 }

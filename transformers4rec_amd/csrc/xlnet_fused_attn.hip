@@ -16,6 +16,8 @@
 // xlnet_layer.hip; what they save is the operand cutting per 64 x 64 tile of the general kernel, the LayerNorm round
 // trips and the launch boundaries (measured per layer at the benchmark size, same box: see docs/DESIGN_rounds_1_to_4.md 4.1c).
 #include "xlnet_fused.h"
+#include "../../include/t4r_hip.h"
+#include "../../include/t4r_hip_rows.h"
 #include <type_traits>
 
 // ---------------------------------------------------------------------------------------------- weight planes of a layer
@@ -270,7 +272,6 @@ static int prepare_launch(hipStream_t st, const float* q, const float* k, const 
     return launch_jobs(st, js, aj);
 }
 
-extern "C" int t4r_xlnet_fused_supported(int D);
 
 // cuts every weight matrix of one layer into its bf16 planes: ONE launch per layer call (planes:
 // t4r_xlnet_layer_planes_floats(D) floats).  params: host array of 15 device pointers, order of t4r_xlnet_layer_fwd.
@@ -1008,21 +1009,14 @@ extern "C" int t4r_xlnet_ln1_bwd(void* stream, const float* dy, const float* ao,
 }
 
 // dh [T, D] += d q @ W_q^T + d k @ W_k^T + d v @ W_v^T   (dqkv [3][T][D])
-// set and cleared inside one layer call (T4R_LAYER_FUSE_INPUT): the next t4r_xlnet_dh masks its result with the input dropout
-static thread_local int g_dh_in_on = 0;
-static thread_local float g_dh_in_p = 0.f;
-static thread_local unsigned long long g_dh_in_seed = 0, g_dh_in_ctr = 0;
-void t4r_xlnet_dh_input_dropout(int on, float p, unsigned long long seed, unsigned long long ctr) {
-    g_dh_in_on = on; g_dh_in_p = p; g_dh_in_seed = seed; g_dh_in_ctr = ctr;
-}
-extern "C" int t4r_xlnet_dh(void* stream, const float* dqkv, const float* planes, float* dh, long T, int D) {
+// drop_in (p = 0: off): the result is masked with the model-level input dropout of a first layer (T4R_LAYER_FUSE_INPUT)
+int t4r_xlnet_dh_impl(void* stream, const float* dqkv, const float* planes, float* dh, long T, int D, const DropCfg& drop_in) {
     if (T <= 0) return 0;
     T4R_CHECK_ARG(t4r_xlnet_fused_supported(D) && dqkv && planes && dh, "xlnet_dh: bad arguments");
     const int R = t4r_xlnet_pick_r(T, true);
     const bool hs = t4r_xlnet_body_fp16x2();
     const LayerPlanesH PH_ = carve_planes_h(planes, D);
-    DhParams p{dqkv, hs ? PH_.QKVN : carve_planes(planes, D).QKVN, PH_.scale + HS_Q, dh, T,
-               make_drop(g_dh_in_on ? g_dh_in_p : 0.f, g_dh_in_seed, g_dh_in_ctr)};
+    DhParams p{dqkv, hs ? PH_.QKVN : carve_planes(planes, D).QKVN, PH_.scale + HS_Q, dh, T, drop_in};
     hipStream_t st = (hipStream_t)stream;
 #define CALL(DD, RR)                                                                                             \
     {                                                                                                            \
@@ -1040,4 +1034,7 @@ extern "C" int t4r_xlnet_dh(void* stream, const float* dqkv, const float* planes
 #undef CALL
     T4R_LAUNCH_CHECK();
     return 0;
+}
+extern "C" int t4r_xlnet_dh(void* stream, const float* dqkv, const float* planes, float* dh, long T, int D) {
+    return t4r_xlnet_dh_impl(stream, dqkv, planes, dh, T, D, make_drop(0.f, 0, 0));
 }

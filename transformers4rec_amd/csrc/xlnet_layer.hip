@@ -13,29 +13,13 @@
 //   attn_vec [T,D] = rel-attention(q,k,v,k_r)         (xlnet_attn.hip)
 //   h1 = LN(attn_vec @ o^T + h) ; h2 = LN(W2 gelu(W1 h1 + b1) + b2 + h1)
 // Saved-for-backward activations live in one caller-provided workspace (offsets below).
-#include "t4r_common.h"
+#include "t4r_internal.h"
+#include "../../include/t4r_hip.h"
+#include "../../include/t4r_hip_rows.h"
+#include "../../include/t4r_hip_attn.h"
 #include <stdio.h>
 #include <stdlib.h>
 
-int t4r_gemm_launch(hipStream_t stream, int transA, int transB, int M, int N, int K, float alpha,
-                    const float* A, long lda, const float* B, long ldb, float* C, long ldc,
-                    const float* bias, int epilogue, float* aux, long ldaux, int splitk,
-                    int accumulate, int batch, long sA, long sB, long sC, const DropCfg* drop);
-extern "C" {
-int t4r_add_layernorm_fwd(void*, const float*, const float*, const float*, const float*, float*,
-                          float*, float*, int, int, float, float, unsigned long long, unsigned long long);
-int t4r_add_layernorm_bwd(void*, const float*, const float*, const float*, const float*,
-                          const float*, const float*, float*, float*, float*, float*, float*, int, int,
-                          int, float, unsigned long long, unsigned long long);
-int t4r_act_bwd_bias(void*, const float*, const float*, float*, float*, float*, long, int, int, float,
-                     unsigned long long, unsigned long long);
-int t4r_colsum(void*, const float*, float*, float*, long, int, long);
-long t4r_colreduce_ws_floats(long, int);
-}
-void t4r_reduce_redirect(hipStream_t side, hipEvent_t* events, int n_events);   // elementwise.hip
-void t4r_gemm_operand_amax(const float* a, const float* b, int n);               // gemm_f32.hip: next launch in the fp16 split form
-void t4r_xlnet_ff_amax_buffers(float* h1, float* act, float* dpre, float* dfo);  // xlnet_fused.hip
-void t4r_xlnet_ff_final_dropout(int on, unsigned long long ctr);                 // xlnet_fused.hip
 // layer_idx carries flags above its low byte (the Philox counters use the low byte only, ctr_hi):
 //   T4R_LAYER_FUSE_FINAL  this is the LAST layer of the stack and the model runs in training mode: the model-level output
 //                         dropout (HF modeling_xlnet.py:1177, key (offset, 255, SITE_FINAL)) is applied by this layer's
@@ -48,78 +32,6 @@ void t4r_xlnet_ff_final_dropout(int on, unsigned long long ctr);                
 //                         in xlnet_dh's final store -- instead of two element-wise launches over [T, D].  Needs the one-kernel
 //                         attention forward (t4r_xlnet_attn_block_supported) and the fused kernels.
 #define T4R_LAYER_FUSE_INPUT 0x200
-void t4r_xlnet_attn_block_input_dropout(int on, unsigned long long ctr, float* hin);     // xlnet_attn_block.hip
-void t4r_xlnet_dh_input_dropout(int on, float p, unsigned long long seed, unsigned long long ctr);   // xlnet_fused_attn.hip
-int t4r_xlnet_ff_amax_count(long T);
-int t4r_xlnet_ff_amax_count_bwd(long T);
-void t4r_gemm_operand_amax2(const float* a, int na, const float* b, int nb);   // gemm_f32.hip: the two producers ran different grids
-long t4r_xlnet_ff_amax_slots(long T);
-bool t4r_xlnet_body_fp16x2();
-// xlnet_attn.hip / xlnet_attn_block.hip: the public entries plus the `prob` pointer (the attention probabilities before dropout
-// [B][n_head][L][L]: the one-kernel forward stores them, the core's backward reads them instead of recomputing the scores)
-int t4r_xlnet_attn_bwd_impl(void*, const float*, const float*, const float*, const float*, const float*, const float*, const float*,
-                            const float*, const float*, const float*, float*, float*, float*, float*, float*, float*, float*, int,
-                            int, int, int, int, float, unsigned long long, unsigned long long, const int*);
-int t4r_xlnet_attn_block_fwd_impl(void*, const float*, const float*, const float*, const float*, long, const float*, const float*,
-                                  const float*, const float*, float*, float*, float*, float*, float*, float*, float*, float*, int,
-                                  int, int, int, float, float, unsigned long long, unsigned long long, unsigned long long,
-                                  const int*);
-void t4r_splitk_sink_begin(float* ws, long cap_floats);                          // gemm_f32.hip: deterministic split-K
-int t4r_splitk_sink_flush(hipStream_t st);
-void t4r_splitk_sink_end();
-extern "C" {
-int t4r_dropout(void*, const float*, float*, unsigned char*, long, long, float, unsigned long long,
-                unsigned long long);
-int t4r_xlnet_attn_fwd(void*, const float*, const float*, const float*, const float*, const float*,
-                       const float*, float*, float*, int, int, int, int, int, float, unsigned long long,
-                       unsigned long long, const int*);
-int t4r_xlnet_attn_bwd(void*, const float*, const float*, const float*, const float*, const float*,
-                       const float*, const float*, const float*, const float*, float*, float*, float*,
-                       float*, float*, float*, float*, int, int, int, int, int, float,
-                       unsigned long long, unsigned long long, const int*);
-long t4r_xlnet_attn_bwd_ws_floats(int, int, int, int);
-// xlnet_fused.hip: token-tile-stationary feed-forward block (one launch forward, one backward)
-int t4r_xlnet_fused_supported(int D);
-long t4r_xlnet_ff_bwd_part_floats(long T, int D);
-long t4r_xlnet_layer_planes_floats(int D);
-int t4r_xlnet_layer_prepare(void*, const float* const*, int, float*);
-int t4r_xlnet_qkv_proj(void*, const float*, const float*, float*, long, int);
-int t4r_xlnet_kr_proj(void*, const float*, const float*, float*, long, int);
-int t4r_xlnet_oproj_ln(void*, const float*, const float*, const float*, const float*, const float*, float*, float*, float*,
-                       float*, long, int, float, float, unsigned long long, unsigned long long);
-long t4r_xlnet_ln1_bwd_part_floats(long, int);
-int t4r_xlnet_ln1_bwd(void*, const float*, const float*, const float*, const float*, const float*, const float*, const float*,
-                      float*, float*, float*, float*, float*, float*, long, int, float, unsigned long long, unsigned long long);
-int t4r_xlnet_dh(void*, const float*, const float*, float*, long, int);
-// include/t4r_hip_rows.h: the row-mapped forms of the three row-wise kernels
-int t4r_xlnet_ff_fwd_rows(void*, const float*, const float*, const float*, const float*, const float*, const float*, float*, float*,
-                          float*, float*, float*, float*, int, int, float, float, unsigned long long, unsigned long long,
-                          unsigned long long, const int*, int);
-int t4r_xlnet_ff_bwd_rows(void*, const float*, const float*, const float*, const float*, const float*, const float*, const float*,
-                          const float*, float*, float*, float*, float*, float*, float*, float*, float*, int, int, float,
-                          unsigned long long, unsigned long long, unsigned long long, const int*, int, float*);
-int t4r_xlnet_ln1_bwd_rows(void*, const float*, const float*, const float*, const float*, const float*, const float*, const float*,
-                           float*, float*, float*, float*, float*, float*, long, int, float, unsigned long long,
-                           unsigned long long, const int*, int);
-// xlnet_attn_block.hip: the attention half as one kernel per direction, exact fp32 matrix instructions
-int t4r_xlnet_attn_block_supported(int L, int D, int n_head);
-int t4r_xlnet_attn_block_fwd(void*, const float*, const float*, const float*, const float*, long, const float*, const float*,
-                             const float*, const float*, float*, float*, float*, float*, float*, float*, float*, int, int, int,
-                             int, float, float, unsigned long long, unsigned long long, unsigned long long, const int*);
-#ifdef T4R_EXPERIMENTAL     /* tools/experimental: the one-kernel backward of the attention half (measured slower, not in the product library) */
-long t4r_xlnet_attn_block_bwd_part_floats(int B, int L, int D, int n_head);
-int t4r_xlnet_attn_block_bwd(void*, const float*, const float*, const float*, const float*, const float*, const float*, const float*,
-                             const float*, const float*, const float*, const float*, const float*, long, const float*, const float*,
-                             const float*, float*, float*, float*, float*, float*, float*, float*, float*, float*, int, int, int, int,
-                             float, unsigned long long, unsigned long long, unsigned long long, const int*);
-#endif
-int t4r_xlnet_ff_fwd(void*, const float*, const float*, const float*, const float*, const float*, const float*,
-                     float*, float*, float*, float*, float*, float*, int, int, float, float,
-                     unsigned long long, unsigned long long, unsigned long long);
-int t4r_xlnet_ff_bwd(void*, const float*, const float*, const float*, const float*, const float*, const float*,
-                     const float*, const float*, float*, float*, float*, float*, float*, float*, float*,
-                     float*, int, int, float, unsigned long long, unsigned long long, unsigned long long);
-}
 // T4R_XLNET_FUSED=0 restores the launch chain (A/B timing); default: fused kernels where they exist (d_model 32/64/128)
 static bool use_fused(int D) {
     static const int on = [] { const char* e = t4r_exp_getenv("T4R_XLNET_FUSED"); return e ? atoi(e) : 1; }();
@@ -303,13 +215,10 @@ static int layer_fwd_impl(void* stream, const float* h, const float* pos_emb,
         }
         if (block) {
             // q | k | v projection, attention core, o-projection + dropout + residual + LayerNorm: ONE launch
-            t4r_xlnet_attn_block_input_dropout(fuse_in, ctr_hi(offset, 255, SITE_INPUT), w.hin);
-            const int rc_ab = t4r_xlnet_attn_block_fwd_impl(stream, h, w.planes, params[P_O], w.kr, drop ? 2L * L * D : 0L, params[P_RWB],
-                                                            params[P_RRB], params[P_LN1W], params[P_LN1B], w.qkv, w.av, w.lse, w.prob,
-                                                            w.ao, w.mean1, w.rstd1, w.h1, B, L, D, n_head, ln_eps, drop_p, seed,
-                                                            C(SITE_PROB), C(SITE_ATTN_OUT), key_len);
-            t4r_xlnet_attn_block_input_dropout(0, 0, nullptr);
-            if (rc_ab) return rc_ab;
+            RUN(t4r_xlnet_attn_block_fwd_impl(stream, h, w.planes, params[P_O], w.kr, drop ? 2L * L * D : 0L, params[P_RWB],
+                                              params[P_RRB], params[P_LN1W], params[P_LN1B], w.qkv, w.av, w.lse, w.prob, w.ao,
+                                              w.mean1, w.rstd1, w.h1, B, L, D, n_head, ln_eps, drop_p, seed, C(SITE_PROB),
+                                              C(SITE_ATTN_OUT), key_len, fuse_in, ctr_hi(offset, 255, SITE_INPUT), w.hin));
         } else {
         RUN(t4r_xlnet_attn_fwd(stream, w.qkv, w.qkv + TD, w.qkv + 2 * TD, w.kr, params[P_RWB], params[P_RRB], w.av, w.lse,
                                B, L, n_head, dh, drop, drop_p, seed, C(SITE_PROB), key_len));
@@ -321,18 +230,13 @@ static int layer_fwd_impl(void* stream, const float* h, const float* pos_emb,
             t4r_set_error("xlnet_layer_fwd_rows: memset failed");
             return -1;
         }
-        t4r_xlnet_ff_amax_buffers(w.amax, w.amax + ns, nullptr, nullptr);
-        t4r_xlnet_ff_final_dropout(fuse_final && drop, ctr_hi(offset, 255, SITE_FINAL));
+        // the launch leaves max |h1|, max |act| per workgroup for the backward's weight gradients, and applies the model's output
+        // dropout when this is the last layer of a stack
+        const FFOpts ff_opt{w.amax, w.amax + ns, fuse_final && drop, ctr_hi(offset, 255, SITE_FINAL)};
         // with a map: ffpre / ffact / ffout in compact order [n, .] inside their full-size slots, mean2 / rstd2 at the token rows
-        const int rc = rows ? t4r_xlnet_ff_fwd_rows(stream, w.h1, w.planes, params[P_B1], params[P_B2], params[P_LN2W], params[P_LN2B],
-                                                    w.ffpre, w.ffact, w.ffout, w.mean2, w.rstd2, h_out, T, D, ln_eps, drop_p, seed,
-                                                    C(SITE_FF_ACT), C(SITE_FF_OUT), rows, n_rows)
-                            : t4r_xlnet_ff_fwd(stream, w.h1, w.planes, params[P_B1], params[P_B2], params[P_LN2W], params[P_LN2B], w.ffpre,
-                                        w.ffact, w.ffout, w.mean2, w.rstd2, h_out, T, D, ln_eps, drop_p, seed, C(SITE_FF_ACT),
-                                        C(SITE_FF_OUT));
-        t4r_xlnet_ff_final_dropout(0, 0);
-        t4r_xlnet_ff_amax_buffers(nullptr, nullptr, nullptr, nullptr);
-        return rc;
+        return t4r_xlnet_ff_fwd_impl(stream, w.h1, w.planes, params[P_B1], params[P_B2], params[P_LN2W], params[P_LN2B], w.ffpre,
+                                     w.ffact, w.ffout, w.mean2, w.rstd2, h_out, T, D, ln_eps, drop_p, seed, C(SITE_FF_ACT),
+                                     C(SITE_FF_OUT), rows, n_rows, ff_opt);
     }
     if (k_w == q_w + DD && v_w == q_w + 2 * DD) {
         RUN(t4r_gemm_launch(st, 0, 0, T, D, D, 1.f, h, D, q_w, D, w.qkv, D, nullptr, EPI_NONE, nullptr, 0,
@@ -571,31 +475,20 @@ static int layer_bwd_impl(void* stream, const float* h, const float* pos_emb,
         const int Tk = rows ? n_rows : T;
         const int na = t4r_xlnet_ff_amax_count(Tk), nb = t4r_xlnet_ff_amax_count_bwd(Tk);
         float* am = w.amax;          // max |h1|, max |act| (forward), max |d pre|, max |d ffout| (now): one float per workgroup
-        t4r_xlnet_ff_amax_buffers(nullptr, nullptr, am + 2 * ns, am + 3 * ns);
-        {
-            t4r_xlnet_ff_final_dropout(fuse_final && drop, ctr_hi(offset, 255, SITE_FINAL));
-            const int rc = rows ? t4r_xlnet_ff_bwd_rows(stream, dh_out, w.ffout, w.h1, w.mean2, w.rstd2, params[P_LN2W], w.ffpre,
-                                                        w.planes, dx, dfo, dff, grads[P_LN2W], grads[P_LN2B], grads[P_B2],
-                                                        grads[P_B1], ff_part, T, D, drop_p, seed, C(SITE_FF_ACT), C(SITE_FF_OUT),
-                                                        rows, n_rows, h1c)
-                                : t4r_xlnet_ff_bwd(stream, dh_out, w.ffout, w.h1, w.mean2, w.rstd2, params[P_LN2W], w.ffpre, w.planes,
-                                            dx, dfo, dff, grads[P_LN2W], grads[P_LN2B], grads[P_B2], grads[P_B1], ff_part,
-                                            T, D, drop_p, seed, C(SITE_FF_ACT), C(SITE_FF_OUT));
-            t4r_xlnet_ff_final_dropout(0, 0);
-            t4r_xlnet_ff_amax_buffers(nullptr, nullptr, nullptr, nullptr);
-            if (rc) return rc;
-        }
+        const FFOpts ff_opt{am + 2 * ns, am + 3 * ns, fuse_final && drop, ctr_hi(offset, 255, SITE_FINAL)};
+        RUN(t4r_xlnet_ff_bwd_impl(stream, dh_out, w.ffout, w.h1, w.mean2, w.rstd2, params[P_LN2W], w.ffpre, w.planes, dx, dfo, dff,
+                                  grads[P_LN2W], grads[P_LN2B], grads[P_B2], grads[P_B1], ff_part, T, D, drop_p, seed,
+                                  C(SITE_FF_ACT), C(SITE_FF_OUT), rows, n_rows, h1c, ff_opt));
         // the two weight gradients in the two-way fp16 form, positioned by the operand maxima the fused kernels left
         const bool hs = t4r_xlnet_body_fp16x2() && drop_p >= 0.f;
-        if (hs) t4r_gemm_operand_amax2(am + 3 * ns, nb, am + ns, na);
+        const GemmAmax amax_w2{am + 3 * ns, nb, am + ns, na}, amax_w1{am + 2 * ns, nb, am, na};
         // (with a map the two products contract over the n_rows compact rows)
         RUN(t4r_gemm_launch(wg(), 1, 0, D, 4 * D, Tk, 1.f, dfo, D, w.ffact, 4 * D, grads[P_W2], 4 * D, nullptr,
-                            EPI_NONE, nullptr, 0, -1, 1, 1, 0, 0, 0, nullptr));
+                            EPI_NONE, nullptr, 0, -1, 1, 1, 0, 0, 0, nullptr, hs ? &amax_w2 : nullptr));
         {
             hipStream_t s1 = wg_again();
-            if (hs) t4r_gemm_operand_amax2(am + 2 * ns, nb, am, na);
             RUN(t4r_gemm_launch(s1, 1, 0, 4 * D, D, Tk, 1.f, dff, 4 * D, rows ? h1c : w.h1, D, grads[P_W1], D, nullptr,
-                                EPI_NONE, nullptr, 0, -1, 1, 1, 0, 0, 0, nullptr));
+                                EPI_NONE, nullptr, 0, -1, 1, 1, 0, 0, 0, nullptr, hs ? &amax_w1 : nullptr));
             // first reduction launch of the call: W2, W1 and the bias / LayerNorm-2 sums of the feed-forward half
             RUN(t4r_splitk_sink_flush(s1));
         }
@@ -676,12 +569,9 @@ static int layer_bwd_impl(void* stream, const float* h, const float* pos_emb,
         }
         // second reduction launch: o, r, q, k, v and the LayerNorm-1 / attention-bias sums (same stream as their products)
         RUN(t4r_splitk_sink_flush(sw));
-        if (!block) {
-            t4r_xlnet_dh_input_dropout(fuse_in, drop_p, seed, ctr_hi(offset, 255, SITE_INPUT));
-            const int rc_dh = t4r_xlnet_dh(stream, dqkv, w.planes, dh_in, T, D);
-            t4r_xlnet_dh_input_dropout(0, 0.f, 0, 0);
-            if (rc_dh) return rc_dh;
-        }
+        if (!block)
+            RUN(t4r_xlnet_dh_impl(stream, dqkv, w.planes, dh_in, T, D,
+                                  make_drop(fuse_in ? drop_p : 0.f, seed, ctr_hi(offset, 255, SITE_INPUT))));
         if (ss && !g_defer_join) {   // join: the caller's stream continues after every weight gradient of this layer
             (void)hipEventRecord(ss->done_all, ss->s);
             (void)hipStreamWaitEvent(st, ss->done_all, 0);
