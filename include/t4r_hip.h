@@ -279,13 +279,16 @@ int t4r_head_split_dx(void* stream, void* ws, const float* logits, long ld, cons
  * labels == NULL: the dominant kernel alone on a workspace a full call has filled (bench.py's roofline timing).
  * t4r_head_split_fdx_supported: 1 when this form takes the width (the widths of t4r_head_split_supported). */
 int t4r_head_split_fdx_supported(int D);
-/* The next t4r_head_split_logits_ce_dx of this thread ON TABLE W takes max |W| from part[0 .. n) -- the per-workgroup maxima
- * t4r_adam_step_amax left over exactly W's elements; the caller promises that nothing has written W since -- instead of a memset
- * + a pass over the table.  Consumed by that call. */
-void t4r_head_split_w_amax_hint(const float* W, const float* part, int n);
 int t4r_head_split_logits_ce_dx(void* stream, void* ws, const float* X, long ldx, const float* W, long ldw, float* C, long ldc,
                                 const long* labels, float* loss_rows, float* lse, float* loss_mean, float* dX, long lddx,
                                 const float* wsum, int N, int V, int D, float alpha, float label_smoothing, void* note);
+/* The same call, taking max |W| from w_amax_part[0 .. w_amax_n) instead of a memset + a pass over the table.  The caller's
+ * contract: the partials are the per-workgroup maxima t4r_adam_step_amax left over exactly W's elements, and nothing has
+ * written W since that optimizer launch.  w_amax_part == NULL or w_amax_n <= 0: as t4r_head_split_logits_ce_dx. */
+int t4r_head_split_logits_ce_dx_amax(void* stream, void* ws, const float* X, long ldx, const float* W, long ldw, float* C, long ldc,
+                                     const long* labels, float* loss_rows, float* lse, float* loss_mean, float* dX, long lddx,
+                                     const float* wsum, int N, int V, int D, float alpha, float label_smoothing, void* note,
+                                     const float* w_amax_part, int w_amax_n);
 /* The RECOMPUTING form of the same head (t4r_head_split_recompute_supported: the widths of t4r_head_split_supported): nothing
  * of size [N, V] is written or read.  _ce: loss rows, lse (and the mean) from per-tile statistics, each row's label logit
  * captured inside the product; _dw_rc / _dx_rc: the two backward products with their score tiles recomputed on the matrix
@@ -515,7 +518,20 @@ int t4r_xlnet_ff_bwd(void* stream, const float* dy, const float* ffout, const fl
  * around the stack (round 6); bit 9 (0x200), with drop_p > 0, d_model 32 / 64 / 128 and t4r_xlnet_attn_block_supported(L, D,
  * n_head): this is the FIRST layer and `h` is the model's UNDROPPED input -- the input dropout (HF :1116, key (offset, 255,
  * site 0)) is applied on load by the attention-block kernel (the dropped rows are kept in `ws` for _bwd, which takes them from
- * there whatever `h` it is given) and _bwd masks the d h it returns. */
+ * there whatever `h` it is given) and _bwd masks the d h it returns; bit 10 (0x400), honoured by _fwd / _fwd_rows only, d_model
+ * 32 / 64 / 128: `ws` already holds this layer's weight planes and k_r (t4r_xlnet_stack_prepare below) and the call skips its
+ * own two launches -- pos_emb_b must be passed when dropout is on; bit 11 (0x800), honoured by _bwd / _bwd_rows only: deferred
+ * join of the weight-gradient streams (csrc/xlnet_layer.hip) -- the call returns without ordering `stream` after its weight
+ * gradients (q, k, v, o, r, W1, W2 and the bias / LayerNorm sums may still be accumulating); the caller keeps every buffer
+ * it passed (h, ws, bws, dh_out, pos_emb_b, the parameter and gradient tensors) alive and unwritten and calls
+ * t4r_xlnet_layer_bwd_join(stream) before the gradients are read or those buffers are reused.  Without the bit every call
+ * joins before it returns (reference semantics: autograd returns finished gradients,
+ * transformers4rec/torch/block/transformer.py:179-199 under torch.autograd).  The options are per call: nothing a call is
+ * given outlives it. */
+#define T4R_LAYER_FUSE_FINAL 0x100
+#define T4R_LAYER_FUSE_INPUT 0x200
+#define T4R_LAYER_STACK_PREPARED 0x400
+#define T4R_LAYER_DEFER_JOIN 0x800
 long t4r_xlnet_layer_ws_floats(int B, int L, int D, int n_head, int dropout);
 long t4r_xlnet_layer_bwd_ws_floats(int B, int L, int D, int n_head, int dropout);
 int t4r_xlnet_layer_fwd(void* stream, const float* h, const float* pos_emb, const float* const* params,
@@ -533,25 +549,21 @@ int t4r_xlnet_layer_bwd(void* stream, const float* h, const float* pos_emb, cons
  * of two launches inside every t4r_xlnet_layer_fwd.  params_all: n_layers x 15 device pointers (order of
  * t4r_xlnet_layer_fwd); planes[l] / kr[l]: inside layer l's workspace at t4r_xlnet_layer_ws_offsets' offsets; pos: the
  * [pos_rows, D] positional encoding the layers would project (pos_emb_b [B 2L, D] with dropout, pos_emb [2L, D] without).
- * After t4r_xlnet_stack_prepared(1) the layer forwards of this thread skip their own two launches (fused widths only;
- * pos_emb_b must be passed to them when dropout is on). */
+ * A layer forward given T4R_LAYER_STACK_PREPARED in layer_idx then skips its own two launches (fused widths only). */
 int t4r_xlnet_layer_ws_offsets(int B, int L, int D, int n_head, int dropout, long* planes_off, long* kr_off);
 int t4r_xlnet_stack_prepare(void* stream, const float* const* params_all, int n_layers, int D, float* const* planes,
                             const float* pos, long pos_rows, float* const* kr);
-/* The next t4r_xlnet_stack_prepare of this thread makes the dropped positional rows of a TRAINING forward itself: it is then
- * given the plain [period, D] encoding as `pos` with pos_rows = B x period, masks row t = pos[t % period] with the pos_emb
- * dropout keyed (seed, ctr) (HF modeling_xlnet.py:1143) inside the projection kernel and writes the dropped rows to out
- * [pos_rows, D] -- the tensor the layers' backward takes as pos_emb_b.  Replaces a t4r_dropout launch in front of the call. */
-void t4r_xlnet_stack_pos_dropout(float p, unsigned long long seed, unsigned long long ctr, long period, float* out);
-void t4r_xlnet_stack_prepared(int on);
+/* t4r_xlnet_stack_prepare that makes the dropped positional rows of a TRAINING forward itself: `pos` is the plain [period, D]
+ * encoding and pos_rows = B x period; row t = pos[t % period] is masked with the pos_emb dropout keyed (seed, ctr) (HF
+ * modeling_xlnet.py:1143) inside the projection kernel and the dropped rows are written to dropped [pos_rows, D] -- the
+ * tensor the layers' backward takes as pos_emb_b.  Replaces a t4r_dropout launch in front of the call.  Needs the fp16 form
+ * of the projection (the default), drop_p > 0, pos_rows % period == 0 and dropped != NULL. */
+int t4r_xlnet_stack_prepare_drop(void* stream, const float* const* params_all, int n_layers, int D, float* const* planes,
+                                 const float* pos, long pos_rows, float* const* kr, float drop_p, unsigned long long seed,
+                                 unsigned long long ctr, long period, float* dropped);
 
-/* Deferred join of the layer backward's weight-gradient streams (csrc/xlnet_layer.hip).  After
- * t4r_xlnet_layer_bwd_defer(1) a t4r_xlnet_layer_bwd call on this thread returns without ordering `stream` after its
- * weight gradients (q, k, v, o, r, W1, W2 and the bias / LayerNorm sums may still be accumulating); the caller keeps
- * every buffer it passed alive and unwritten and calls t4r_xlnet_layer_bwd_join(stream) before the gradients are read
- * or those buffers are reused.  Default 0: every call joins before it returns (reference semantics: autograd returns
- * finished gradients, transformers4rec/torch/block/transformer.py:179-199 under torch.autograd). */
-void t4r_xlnet_layer_bwd_defer(int on);
+/* Orders `stream` after everything queued so far on the weight-gradient streams of the current device: what a caller of
+ * t4r_xlnet_layer_bwd with T4R_LAYER_DEFER_JOIN owes before the gradients are read. */
 int t4r_xlnet_layer_bwd_join(void* stream);
 
 
@@ -700,7 +712,7 @@ int t4r_adam_step(void* stream, float* param, float* grad, float* exp_avg, float
                   int step, float lr, float beta1, float beta2, float eps, float weight_decay,
                   float grad_scale, int zero_grad);
 /* the same step that also leaves amax_part[b] = max |param[i]| AFTER the update over i in [amax_lo, amax_hi) seen by workgroup b;
- * returns the number of workgroups (<= 1024: the capacity amax_part must have) or < 0.  With t4r_head_split_w_amax_hint it
+ * returns the number of workgroups (<= 1024: the capacity amax_part must have) or < 0.  With t4r_head_split_logits_ce_dx_amax it
  * replaces the memset + 21 us pass over the tied item table in front of every step's head (round 6). */
 int t4r_adam_step_amax(void* stream, float* param, float* grad, float* exp_avg, float* exp_avg_sq, long n, int step, float lr,
                        float beta1, float beta2, float eps, float weight_decay, float grad_scale, int zero_grad, long amax_lo,

@@ -63,21 +63,19 @@ def test_missing_library_fails_loudly(monkeypatch, tmp_path):
 # until it is justified here (a process-wide forward->backward ring in head_split.hip is gone --
 # that state now travels in the caller-owned t4r_head_note).  Per-launch options of the XLNet layer (operand maxima of a GEMM,
 # the maxima buffers and the fused model-level dropouts of the token-tile kernels) are ARGUMENTS of internal entries
-# (csrc/t4r_internal.h), not thread-locals armed around a call: none may come back here.
+# (csrc/t4r_internal.h), not thread-locals armed around a call: none may come back here.  The same holds across the C ABI: what
+# the host once armed with a setter before the call it meant (a prepared stack, the deferred join, the stack prologue's positional
+# dropout, the table maximum of the one-pass head) is a flag bit in layer_idx or an argument of a sibling entry (_drop, _amax), so
+# that a call that never reaches the library leaves nothing armed for the next one.
 _ALLOWED_FILE_SCOPE_STATE = {
     "g_err": "thread-local error string (t4r_last_error)",
     "g_prec": "precision switch, set only through t4r_set_precision",
-    "g_defer_join": "thread-local switch, set only through t4r_xlnet_layer_bwd_defer",
-    "g_stack_prepared": "thread-local switch, set only through t4r_xlnet_stack_prepared",
     "g_side": "thread-local per-device side streams of the layer backward (created once, never freed)",
     "g_side_all": "registry of those side streams for t4r_xlnet_layer_bwd_join",
     "g_side_mu": "mutex of that registry",
     "g_sink": "thread-local, set and cleared INSIDE one t4r_xlnet_layer_bwd call (split-K partial sink)",
     "g_cu_budget": "CUs the backward's token-tile kernels may count on, set only through t4r_xlnet_set_cu_budget (documented in "
                    "include/t4r_hip.h; per-row results do not depend on it, batch-reduced gradients are equal up to summation order)",
-    "g_stack_gen": "thread-local, set by t4r_xlnet_stack_pos_dropout and consumed (cleared) by the next t4r_xlnet_stack_prepare",
-    "g_w_amax_part": "thread-local, set by t4r_head_split_w_amax_hint and consumed (cleared) by the next t4r_head_split_logits_ce_dx",
-    "g_w_amax_W": "same", "g_w_amax_n": "same",
     "g_red_side": "thread-local, set and cleared inside one layer call (reduction side stream)",
     "g_red_events": "same", "g_red_n": "same", "g_red_used": "same",
 }

@@ -217,7 +217,6 @@ EXEMPT = {
     "t4r_head_split_fwd_products": "capability query: nothing launches",
     "t4r_head_split_ws_bytes": "size query: nothing launches",
     "t4r_head_split_fdx_supported": "capability query: nothing launches",
-    "t4r_head_split_w_amax_hint": "host-side hint registration: nothing launches",
     "t4r_head_split_recompute_supported": "capability query: nothing launches",
     "t4r_linear_softmax_ce_chunk_floats": "size query: nothing launches",
     "t4r_dropout_ctr_hi": "host arithmetic: nothing launches",
@@ -237,9 +236,6 @@ EXEMPT = {
     "t4r_xlnet_layer_ws_floats": "size query: nothing launches",
     "t4r_xlnet_layer_bwd_ws_floats": "size query: nothing launches",
     "t4r_xlnet_layer_ws_offsets": "offset query into host longs: nothing launches",
-    "t4r_xlnet_stack_pos_dropout": "host-side registration for the next stack_prepare: nothing launches",
-    "t4r_xlnet_stack_prepared": "thread-local switch: nothing launches",
-    "t4r_xlnet_layer_bwd_defer": "thread-local switch: nothing launches",
     "t4r_item_topk_ws_bytes": "size query: nothing launches",
     "t4r_item_table_image_ld": "pitch query: nothing launches",
     "t4r_item_topk_h16_supported": "capability query: nothing launches",

@@ -1195,8 +1195,9 @@ def _head_bwd_ref(lg, lse, y, V, yoff, smooth, gout, N, alpha, W64, x64):
 
 
 def _head_split(N, V, D, smooth, form):
-    """form: "mat" prepare -> logits -> logits_ce -> dw, dx | "fdx" prepare -> logits_ce_dx -> dw | "rc" prepare -> prepare_rc ->
-    ce -> dw_rc, dx_rc | "chunk" prepare -> logits -> dx, dw on the columns [yoff, yoff + Vc)"""
+    """form: "mat" prepare -> logits -> logits_ce -> dw, dx | "fdx" prepare -> logits_ce_dx -> dw | "fdx_amax" the same through
+    logits_ce_dx_amax (the table maximum from the caller's partials) | "rc" prepare -> prepare_rc -> ce -> dw_rc, dx_rc |
+    "chunk" prepare -> logits -> dx, dw on the columns [yoff, yoff + Vc)"""
     def fn(a, key):
         ops = _ops()
         lib = _lib().load()
@@ -1256,12 +1257,20 @@ def _head_split(N, V, D, smooth, form):
             dX64, dW64 = _head_bwd_ref(chunk, lse64.float(), y, V, yoff, smooth, gout, N, alpha, W64, x64)
             tc = "test_kernels_gpu.py::test_head_split_vocabulary_chunk"
             return [Out(DX, dX64, dict(rtol=1e-4, atol=1e-7), tc), Out(DWC, dW64, dict(rtol=1e-4, atol=1e-7), tc)]
-        if form == "fdx":
+        if form in ("fdx", "fdx_amax"):
             C3 = a.new("logits", "out", F32, (N, ldc), 0, V)
             WSUM = a.new("wsum", "in", F32, D).set(W.double().sum(0)) if smooth > 0 else None
             DW = a.new("dW", "inout", F32, (V, ldw), 0, D).set(1.0)
-            call(a, "t4r_head_split_logits_ce_dx", stream(), WS.ptr, X.ptr, ldx, Wb.ptr, ldw, C3.ptr, ldc, Y.ptr, LR.ptr, LS.ptr, LM.ptr,
-                 DX.ptr, ldx, None if WSUM is None else WSUM.ptr, N, V, D, alpha, smooth, nptr)
+            fdx_args = (stream(), WS.ptr, X.ptr, ldx, Wb.ptr, ldw, C3.ptr, ldc, Y.ptr, LR.ptr, LS.ptr, LM.ptr,
+                        DX.ptr, ldx, None if WSUM is None else WSUM.ptr, N, V, D, alpha, smooth, nptr)
+            if form == "fdx_amax":
+                # host-computed per-slot maxima over exactly W's elements (what t4r_adam_step_amax leaves), five slots: max |W| is
+                # exact whichever way it is reduced, so the expected outputs are the fdx case's
+                part = torch.stack([c.abs().max() for c in W.chunk(5)])
+                PART = a.new("w_amax_part", "in", F32, part.numel()).set(part)
+                call(a, "t4r_head_split_logits_ce_dx_amax", *fdx_args, PART.ptr, part.numel())
+            else:
+                call(a, "t4r_head_split_logits_ce_dx", *fdx_args)
             call(a, "t4r_head_split_dw", stream(), WS.ptr, C3.ptr, ldc, LS.ptr, Y.ptr, GO.ptr, smooth, DW.ptr, ldw, N, V, V, 0, D, alpha, 1, nptr)
 
             def mk():
@@ -1299,7 +1308,7 @@ def _head_supported(form, D):
     lib = _lib().load()
     if not lib.t4r_head_split_supported(D):
         return False
-    if form == "fdx":
+    if form in ("fdx", "fdx_amax"):
         return bool(lib.t4r_head_split_fdx_supported(D))
     if form == "rc":
         return bool(lib.t4r_head_split_recompute_supported(D))
@@ -1308,11 +1317,13 @@ def _head_supported(form, D):
 
 _HEAD_FORMS = {"mat": ["t4r_head_split_prepare", "t4r_head_split_logits", "t4r_head_split_logits_ce", "t4r_head_split_dw", "t4r_head_split_dx"],
                "fdx": ["t4r_head_split_prepare", "t4r_head_split_logits_ce_dx", "t4r_head_split_dw"],
+               "fdx_amax": ["t4r_head_split_prepare", "t4r_head_split_logits_ce_dx_amax", "t4r_head_split_dw"],
                "rc": ["t4r_head_split_prepare", "t4r_head_split_prepare_rc", "t4r_head_split_ce", "t4r_head_split_dw_rc", "t4r_head_split_dx_rc"],
                "chunk": ["t4r_head_split_prepare", "t4r_head_split_dw", "t4r_head_split_dx"]}
 # csrc/head_split.hip: 128-row x 128-column tiles; V = 33 / 129 / 257 / 1001 are one tile, one tile + 1, two + 1 and a ragged last tile
 for _N, _V, _D, _sm in ((1, 33, 32, 0.0), (33, 129, 64, 0.1), (77, 257, 96, 0.0), (130, 1001, 128, 0.1), (129, 129, 64, 0.0)):
-    for _form in ("mat", "fdx", "rc") + (("chunk",) if _V >= 129 else ()):
+    # fdx_amax: at the fdx form's two small shapes (the table maximum does not depend on the tiling)
+    for _form in ("mat", "fdx", "rc") + (("chunk",) if _V >= 129 else ()) + (("fdx_amax",) if _V <= 129 and _N <= 33 else ()):
         if _head_supported(_form, _D):        # "the recompute forms ... where *_supported says they exist" (pure host queries)
             case("head", f"head_split_{_form}-{_N}-{_V}-{_D}-e{_sm}", _HEAD_FORMS[_form])(_head_split(_N, _V, _D, _sm, _form))
 
@@ -1732,20 +1743,12 @@ def _xlnet_layer(B, L, D, n, p, defer, stack):
             planes, _k3 = _lib().ptr_array([WS.ptr + 4 * po.value])
             kr, _k4 = _lib().ptr_array([WS.ptr + 4 * ko.value])
             call(a, "t4r_xlnet_stack_prepare", s, parr, 1, D, planes, PE.ptr, 2 * L, kr)
-            lib.t4r_xlnet_stack_prepared(1)
-        try:
-            call(a, "t4r_xlnet_layer_fwd", s, H.ptr, PE.ptr, parr, WS.ptr, HO.ptr, B, L, D, n, eps, p, seed, offset, layer, None, None)
-        finally:
-            if stack:
-                lib.t4r_xlnet_stack_prepared(0)
-        if defer:
-            lib.t4r_xlnet_layer_bwd_defer(1)
-        try:
-            call(a, "t4r_xlnet_layer_bwd", s, H.ptr, PE.ptr, parr, garr, WS.ptr, BWS.ptr, DO.ptr, DHI.ptr, B, L, D, n, eps, p, seed, offset,
-                 layer, None, None)
-        finally:
-            if defer:
-                lib.t4r_xlnet_layer_bwd_defer(0)
+        # the options are bits of layer_idx (include/t4r_hip.h: T4R_LAYER_STACK_PREPARED, T4R_LAYER_DEFER_JOIN), each given to
+        # the one call it is meant for
+        call(a, "t4r_xlnet_layer_fwd", s, H.ptr, PE.ptr, parr, WS.ptr, HO.ptr, B, L, D, n, eps, p, seed, offset,
+             layer | (ops.LAYER_STACK_PREPARED if stack else 0), None, None)
+        call(a, "t4r_xlnet_layer_bwd", s, H.ptr, PE.ptr, parr, garr, WS.ptr, BWS.ptr, DO.ptr, DHI.ptr, B, L, D, n, eps, p, seed, offset,
+             layer | (ops.LAYER_DEFER_JOIN if defer else 0), None, None)
         if defer:
             call(a, "t4r_xlnet_layer_bwd_join", s)          # "calls t4r_xlnet_layer_bwd_join(stream) before the gradients are read"
         t = "test_kernels_gpu.py::test_xlnet_layer_fwd_bwd" if p == 0 else "test_kernels_gpu.py::test_xlnet_layer_dropout_fwd_bwd"
@@ -1763,6 +1766,60 @@ for _B, _L, _D, _n in _XL_SHAPES:
             continue
         case("xlnet", f"xlnet_layer-{_B}-{_L}-{_D}-{_n}-p{_p}" + ("-deferred" if _defer else "") + ("-stack" if _stack else ""), _ents)(
             _xlnet_layer(_B, _L, _D, _n, _p, _defer, _stack))
+
+
+def _stack_prepare_drop(n_layers):
+    """t4r_xlnet_stack_prepare_drop: the stack prologue that makes the dropped positional rows itself.  `dropped` must be, bit
+    for bit, what t4r_dropout gives over the expanded encoding with the same key, and every kr[l], bit for bit, what
+    t4r_xlnet_stack_prepare gives over those dropped rows (the two-call form it replaces).  The prologue projects four layers per
+    launch: n_layers = 5 crosses the group boundary."""
+    B, L, D, n, p = 2, 5, 32, 2, 0.3
+
+    def fn(a, key):
+        import t4r_oracle as Orc
+        ops = _ops()
+        lib = _lib().load()
+        g = gen(1000 + n_layers)
+        prms = [_xl_params(g, D, n) for _ in range(n_layers)]
+        pos = Orc.xlnet_pos_emb(L, D).to(F32)
+        period, rows = 2 * L, B * 2 * L
+        seed, ctr = 99, ops.dropout_ctr_hi(7, 255, ops.SITE_POS)
+        npl = lib.t4r_xlnet_layer_planes_floats(D)
+
+        def mk():       # the two-call form, on plain device tensors
+            flat = [pr[k].to(DEV, F32).contiguous() for pr in prms for k in ORDER]
+            pl = [torch.empty(npl, device=DEV, dtype=F32) for _ in prms]
+            krs = [torch.empty(rows, D, device=DEV, dtype=F32) for _ in prms]
+            src, dropped = pos.to(DEV).contiguous(), torch.empty(rows, D, device=DEV, dtype=F32)
+            parr, _k0 = _lib().ptr_array([t.data_ptr() for t in flat])
+            planes, _k1 = _lib().ptr_array([t.data_ptr() for t in pl])
+            kr, _k2 = _lib().ptr_array([t.data_ptr() for t in krs])
+            _lib().call("t4r_dropout", stream(), src.data_ptr(), dropped.data_ptr(), None, rows * D, period * D, p, seed, ctr)
+            _lib().call("t4r_xlnet_stack_prepare", stream(), parr, n_layers, D, planes, dropped.data_ptr(), rows, kr)
+            torch.cuda.synchronize()
+            return dropped.cpu(), [t.cpu() for t in krs]
+        dropped_ref, kr_ref = memo(key, mk)
+        PB = [b for l, pr in enumerate(prms) for b in _xl_param_bufs(a, pr, tag=str(l))]
+        POS = a.new("pos", "in", F32, (period, D)).set(pos)
+        PL = [a.ws(f"planes{l}", 4 * npl) for l in range(n_layers)]
+        KR = [a.new(f"kr{l}", "out", F32, (rows, D)) for l in range(n_layers)]
+        DR = a.new("dropped", "out", F32, (rows, D))
+        parr, _k0 = _lib().ptr_array([b.ptr for b in PB])
+        planes, _k1 = _lib().ptr_array([b.ptr for b in PL])
+        kr, _k2 = _lib().ptr_array([b.ptr for b in KR])
+        call(a, "t4r_xlnet_stack_prepare_drop", stream(), parr, n_layers, D, planes, POS.ptr, rows, kr, p, seed, ctr, period, DR.ptr)
+        torch.cuda.synchronize()
+        t = "bit for bit the two-call form: t4r_dropout, then t4r_xlnet_stack_prepare over its rows"
+        for b, ref in [(DR, dropped_ref)] + list(zip(KR, kr_ref)):
+            assert _bits_equal(b.win.cpu(), ref), f"{key}: '{b.name}' is not {t}"
+        assert float((dropped_ref == 0).float().mean()) > 0.1, "the dropout mask must drop something for the comparison to mean anything"
+        return [Out(DR, dropped_ref, None, t)] + [Out(b, ref, None, t) for b, ref in zip(KR, kr_ref)]
+    return fn
+
+
+if _lib().load().t4r_xlnet_fused_supported(32):
+    for _nl in (1, 5):
+        case("xlnet", f"stack_prepare_drop-2-5-32-p0.3-layers{_nl}", ["t4r_xlnet_stack_prepare_drop"])(_stack_prepare_drop(_nl))
 
 
 def _attn_block(B, L, D, n, p, use_kl):

@@ -320,10 +320,6 @@ def test_round3_host_queries_of_the_library():
     assert po.value == -1                                                   # no fused kernels (no planes) at this width
     assert planes >= 25 * 3 * 128 * 128 // 2 + 25 * 2 * 128 * 128 // 2      # bf16 planes + fp16 planes (+ scales)
     assert lib.t4r_xlnet_fused_products() in (3, 6) and lib.t4r_head_split_fwd_products() in (3, 6)
-    # deferred join switches are plain host state: callable without a device
-    lib.t4r_xlnet_layer_bwd_defer(1)
-    lib.t4r_xlnet_layer_bwd_defer(0)
-    lib.t4r_xlnet_stack_prepared(0)
     assert lib.t4r_apply_mask_bwd_ws_floats(4, 20, 128) == ((4 * 20 + 31) // 32) * 128
 
 

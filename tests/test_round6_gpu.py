@@ -358,8 +358,8 @@ def test_input_dropout_fused_into_the_first_layer(ops, B, L, D, n):
 
 def test_table_maximum_from_the_optimizer_launch(ops):
     """FusedAdam leaves the per-workgroup maxima of the tied item table in its launch (t4r_adam_step_amax); the next step's head
-    takes max |W| from them (t4r_head_split_w_amax_hint) instead of a memset + a pass over the table: same bits in logits, loss
-    and d X; the hint is dropped as soon as anything else writes the table."""
+    is given them in its own call (t4r_head_split_logits_ce_dx_amax) and takes max |W| from them instead of a memset + a pass over
+    the table: same bits in logits, loss and d X; the host drops the record as soon as anything else writes the table."""
     import transformers4rec_amd as tr
 
     B, L, V, D = 256, 20, 30_000, 128
@@ -509,3 +509,60 @@ def test_stand_alone_entries_are_not_coloured_by_a_layer_call(ops):
     assert len(first) == len(again) == 22
     for i, (a, b) in enumerate(zip(first, again)):
         assert a.data_ptr() != b.data_ptr() and torch.equal(a, b), i
+
+
+def test_layer_options_are_per_call(ops):
+    """T4R_LAYER_STACK_PREPARED and T4R_LAYER_DEFER_JOIN are bits of ONE call's layer_idx: the call after it, on the same thread
+    with nothing in between, is a plain call.  A forward without the bit right after one with it cuts its own weight planes and
+    projects its own k_r (a fresh workspace ends up with the regions the stack prologue wrote, bit for bit, and the same output);
+    a plain backward right after a deferred one (+ join) gives the same d h and the same 15 gradients, bit for bit.  Eval mode
+    (drop_p = 0); B 4, L 20, d_model 32, 2 heads: the token-tile kernels and the one-kernel attention forward."""
+    import ctypes
+
+    import test_kernels_gpu as K
+    from transformers4rec_amd import _lib
+
+    B, L, D, n = 4, 20, 32, 2
+    T = B * L
+    assert ops.xlnet_fused_supported(D) and ops.xlnet_attn_block_supported(L, D, n)
+    g = torch.Generator().manual_seed(80)
+    prm = {k: K.cu(v) for k, v in K._layer_params(g, D, n).items()}
+    params = [prm[k] for k in K.ORDER]
+    h, dy = K.cu(torch.randn(T, D, generator=g)), K.cu(torch.randn(T, D, generator=g))
+    pos = K.cu(O.xlnet_pos_emb(L, D))
+    po, ko = ctypes.c_long(0), ctypes.c_long(0)
+    _lib.call("t4r_xlnet_layer_ws_offsets", B, L, D, n, 0, ctypes.addressof(po), ctypes.addressof(ko))
+    n_planes, n_kr = _lib.load().t4r_xlnet_layer_planes_floats(D), 2 * L * D
+    assert po.value >= 0
+    # both workspaces start as 0xFF bytes (no kernel stores that word: as a float it is a NaN), viewed as int32 for the comparisons
+    fresh = lambda: torch.full((ops.xlnet_layer_ws_floats(B, L, D, n, False),), -1, device=DEV, dtype=torch.int32).view(torch.float32)
+    regions = lambda ws: (ws.view(torch.int32)[po.value:po.value + n_planes], ws.view(torch.int32)[ko.value:ko.value + n_kr])
+    ws1, ws2 = fresh(), fresh()
+    parr, _k0 = _lib.ptr_array([t.data_ptr() for t in params])
+    planes, _k1 = _lib.ptr_array([ws1.data_ptr() + 4 * po.value])
+    kr, _k2 = _lib.ptr_array([ws1.data_ptr() + 4 * ko.value])
+    _lib.call("t4r_xlnet_stack_prepare", torch.cuda.current_stream().cuda_stream, parr, 1, D, planes, pos.data_ptr(), 2 * L, kr)
+    out1, _ = ops.xlnet_layer_fwd(h, pos, params, B, L, n, 0.03, ws=ws1, stack_prepared=True)
+    out2, _ = ops.xlnet_layer_fwd(h, pos, params, B, L, n, 0.03, ws=ws2)
+    torch.cuda.synchronize()
+    (pl1, kr1), (pl2, kr2) = regions(ws1), regions(ws2)
+    assert bool((kr2 != -1).all()) and bool((pl2 != -1).any()), "the plain forward did not write its own planes / k_r"
+    assert torch.equal(pl1, pl2) and torch.equal(kr1, kr2)
+    assert torch.equal(out1.view(torch.int32), out2.view(torch.int32)) and bool(torch.isfinite(out1).all())
+
+    def backward(defer):
+        grads = [torch.full_like(t, 0.5) for t in params]
+        keep = [] if defer else None
+        dh = ops.xlnet_layer_bwd(h, pos, params, grads, ws1, dy, B, L, n, 0.03, defer_join=keep)
+        if defer:
+            ops.xlnet_layer_bwd_join()
+        return [dh] + grads, keep
+
+    deferred, keep = backward(True)
+    plain, _ = backward(False)
+    torch.cuda.synchronize()
+    assert len(deferred) == len(plain) == 16 and len(keep) == 1
+    for i, (a, b) in enumerate(zip(deferred, plain)):
+        assert a.data_ptr() != b.data_ptr() and torch.equal(a.view(torch.int32), b.view(torch.int32)), i
+        assert bool(torch.isfinite(a).all()), i
+    assert all(bool((gr != 0.5).any()) for gr in plain[1:])        # every gradient was accumulated into

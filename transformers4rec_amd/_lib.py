@@ -78,6 +78,7 @@ _SIGS = {
     "t4r_head_split_prepare": ("i", "ppl" + "iii" + "p"),
     "t4r_head_split_fdx_supported": ("i", "i"),
     "t4r_head_split_logits_ce_dx": ("i", "pp" + "plpl" + "pl" + "pppp" + "plp" + "iii" + "ff" + "p"),
+    "t4r_head_split_logits_ce_dx_amax": ("i", "pp" + "plpl" + "pl" + "pppp" + "plp" + "iii" + "ff" + "p" + "pi"),
     "t4r_head_note_dw_form": ("i", "p"),
     "t4r_head_split_logits": ("i", "ppplpl" + "iiif" + "p"),
     "t4r_head_split_logits_ce": ("i", "ppplpl" + "pppp" + "iiiff" + "p"),
@@ -114,11 +115,9 @@ _SIGS = {
     "t4r_experimental_build": ("i", ""),
     "t4r_xlnet_attn_block_supported": ("i", "iii"),
     "t4r_xlnet_attn_block_fwd": ("i", "ppppp" + "l" + "pppp" + "ppppppp" + "iiii" + "ffQQQ" + "p"),
-    "t4r_xlnet_layer_bwd_defer": ("v", "i"),
     "t4r_xlnet_layer_ws_offsets": ("i", "iiiii" + "pp"),
     "t4r_xlnet_stack_prepare": ("i", "ppiip" + "plp"),
-    "t4r_xlnet_stack_pos_dropout": ("v", "fQQlp"),
-    "t4r_xlnet_stack_prepared": ("v", "i"),
+    "t4r_xlnet_stack_prepare_drop": ("i", "ppiip" + "plp" + "fQQlp"),
     "t4r_xlnet_layer_bwd_join": ("i", "p"),
     "t4r_xlnet_ff_planes_floats": ("l", "i"),
     "t4r_xlnet_ff_prepare": ("i", "ppppip"),
@@ -155,7 +154,6 @@ _SIGS = {
     "t4r_seq_sum_cols": ("i", "pp" + "li" + "p" + "ili"),
     "t4r_adam_step": ("i", "ppppp" + "li" + "ffffff" + "i"),
     "t4r_adam_step_amax": ("i", "ppppp" + "li" + "ffffff" + "i" + "llp"),
-    "t4r_head_split_w_amax_hint": ("v", "ppi"),
 }
 
 # the second header, include/t4r_hip_sampling.h (tests/test_sampling_cpu.py checks this table against it)

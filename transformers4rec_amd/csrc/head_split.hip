@@ -1872,20 +1872,13 @@ extern "C" int t4r_head_split_dx_rc(void* stream, void* ws, const float* X, long
 // dX [N, D] = d (mean loss) / d X for grad_out = 1 -- the caller's backward multiplies by its upstream gradient and runs only
 // t4r_head_split_dw (same workspace and note).  X: the rows t4r_head_split_prepare was given.  wsum: column sums of W [D]
 // (needed when label_smoothing > 0, else NULL).
-// The next t4r_head_split_logits_ce_dx of this thread on table W takes max |W| from `part[0 .. n)` (per-workgroup maxima written by
-// t4r_adam_step_amax over exactly W's elements, AFTER which nothing else has written W -- the caller's promise) instead of
-// computing it.  Consumed (cleared) by that call, whatever table it is given.
-static thread_local const float* g_w_amax_part = nullptr;
-static thread_local const float* g_w_amax_W = nullptr;
-static thread_local int g_w_amax_n = 0;
-extern "C" void t4r_head_split_w_amax_hint(const float* W, const float* part, int n) {
-    g_w_amax_W = (part && n > 0) ? W : nullptr; g_w_amax_part = g_w_amax_W ? part : nullptr; g_w_amax_n = g_w_amax_W ? n : 0;
-}
+// _amax: max |W| is taken from `w_amax_part[0 .. w_amax_n)` (per-workgroup maxima written by t4r_adam_step_amax over exactly W's
+// elements, AFTER which nothing else has written W -- the caller's promise) instead of computed; NULL or w_amax_n <= 0: computed.
 extern "C" int t4r_head_split_fdx_supported(int D) { return t4r_head_split_supported(D); }
-extern "C" int t4r_head_split_logits_ce_dx(void* stream, void* ws, const float* X, long ldx, const float* W, long ldw, float* C,
-                                           long ldc, const long* labels, float* loss_rows, float* lse, float* loss_mean,
-                                           float* dX, long lddx, const float* wsum, int N, int V, int D, float alpha,
-                                           float label_smoothing, void* note) {
+extern "C" int t4r_head_split_logits_ce_dx_amax(void* stream, void* ws, const float* X, long ldx, const float* W, long ldw, float* C,
+                                                long ldc, const long* labels, float* loss_rows, float* lse, float* loss_mean,
+                                                float* dX, long lddx, const float* wsum, int N, int V, int D, float alpha,
+                                                float label_smoothing, void* note, const float* w_amax_part, int w_amax_n) {
     hipStream_t st = (hipStream_t)stream;
     if (N <= 0 || V <= 0) return loss_mean ? t4r_mean_launch(st, loss_rows, 0, loss_mean) : 0;
     // labels == NULL: the dominant kernel alone (no table maximum, no image cut, no finalize: the workspace holds them from
@@ -1898,11 +1891,9 @@ extern "C" int t4r_head_split_logits_ce_dx(void* stream, void* ws, const float* 
     T4R_CHECK_ARG(label_smoothing <= 0.f || wsum, "head_split_logits_ce_dx: label smoothing needs the column sums of W");
     const HeadWs w = head_ws(N, V, D);
     unsigned* amax = reinterpret_cast<unsigned*>((char*)ws + w.scales);
-    // the table's maximum: from the optimizer's partials when the caller announced them for THIS table (t4r_head_split_w_amax_hint,
-    // consumed here), else a memset + a pass over the table
-    const float* w_part = g_w_amax_W == W ? g_w_amax_part : nullptr;
-    const int w_npart = g_w_amax_n;
-    g_w_amax_part = nullptr; g_w_amax_W = nullptr; g_w_amax_n = 0;
+    // the table's maximum: from the optimizer's partials when the caller passed them, else a memset + a pass over the table
+    const float* w_part = w_amax_n > 0 ? w_amax_part : nullptr;
+    const int w_npart = w_part ? w_amax_n : 0;
     if (!kernel_only && !w_part && head_w_amax(st, W, ldw, V, D, amax + 1)) return -1;
     u32x4* wa = reinterpret_cast<u32x4*>((char*)ws + w.wa);
     u32x4* wtp = reinterpret_cast<u32x4*>((char*)ws + w.wt);
@@ -1934,4 +1925,11 @@ extern "C" int t4r_head_split_logits_ce_dx(void* stream, void* ws, const float* 
                            labels, wsum, label_smoothing, alpha, amax, loss_rows, lse, dX, lddx);
     T4R_LAUNCH_CHECK();
     return (loss_mean && !kernel_only) ? t4r_mean_launch(st, loss_rows, N, loss_mean) : 0;
+}
+extern "C" int t4r_head_split_logits_ce_dx(void* stream, void* ws, const float* X, long ldx, const float* W, long ldw, float* C,
+                                           long ldc, const long* labels, float* loss_rows, float* lse, float* loss_mean,
+                                           float* dX, long lddx, const float* wsum, int N, int V, int D, float alpha,
+                                           float label_smoothing, void* note) {
+    return t4r_head_split_logits_ce_dx_amax(stream, ws, X, ldx, W, ldw, C, ldc, labels, loss_rows, lse, loss_mean, dX, lddx, wsum, N, V, D,
+                                            alpha, label_smoothing, note, nullptr, 0);
 }

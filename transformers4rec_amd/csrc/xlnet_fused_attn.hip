@@ -831,18 +831,12 @@ extern "C" int t4r_xlnet_kr_proj(void* stream, const float* pos, const float* pl
 // change inside a step) and every layer's positional keys k_r = pos @ r_l (the positional encoding -- with its dropout
 // mask, drawn once per forward -- is the same for all layers, so its tile is read and cut once for up to four layers).
 // planes[l] / kr[l]: the layer's own buffers (inside its t4r_xlnet_layer_fwd workspace: t4r_xlnet_layer_ws_offsets).
-// The next t4r_xlnet_stack_prepare of this thread MAKES the dropped positional rows itself (round 6): `pos` is then the plain
-// [period, D] positional encoding, pos_rows = B x period, and the projection kernel masks row t = pos[t % period] with the
+// gen.out != NULL (t4r_xlnet_stack_prepare_drop): the call MAKES the dropped positional rows itself (round 6): `pos` is then the
+// plain [period, D] positional encoding, pos_rows = B x period, and the projection kernel masks row t = pos[t % period] with the
 // pos_emb dropout of this forward (key (seed, ctr)) and writes the dropped rows to `out` [pos_rows, D] (what the caller used to
-// produce with t4r_dropout before the call, and what the backward's d r contraction reads).  Consumed by that call.
-static thread_local GenRows g_stack_gen = {nullptr, 0, DropCfg(), nullptr};
-extern "C" void t4r_xlnet_stack_pos_dropout(float p, unsigned long long seed, unsigned long long ctr, long period, float* out) {
-    g_stack_gen.base = nullptr; g_stack_gen.period = period; g_stack_gen.drop = make_drop(p, seed, ctr); g_stack_gen.out = out;
-}
-extern "C" int t4r_xlnet_stack_prepare(void* stream, const float* const* params_all, int n_layers, int D,
-                                       float* const* planes, const float* pos, long pos_rows, float* const* kr) {
-    GenRows gen = g_stack_gen;
-    g_stack_gen.out = nullptr;
+// produce with t4r_dropout before the call, and what the backward's d r contraction reads).
+static int stack_prepare_impl(void* stream, const float* const* params_all, int n_layers, int D, float* const* planes,
+                              const float* pos, long pos_rows, float* const* kr, const GenRows& gen) {
     T4R_CHECK_ARG(t4r_xlnet_fused_supported(D) && params_all && planes && n_layers >= 1, "xlnet_stack_prepare: bad arguments");
     hipStream_t st = (hipStream_t)stream;
     for (int l0 = 0; l0 < n_layers; l0 += 4) {
@@ -900,6 +894,17 @@ extern "C" int t4r_xlnet_stack_prepare(void* stream, const float* const* params_
         T4R_LAUNCH_CHECK();
     }
     return 0;
+}
+extern "C" int t4r_xlnet_stack_prepare(void* stream, const float* const* params_all, int n_layers, int D,
+                                       float* const* planes, const float* pos, long pos_rows, float* const* kr) {
+    return stack_prepare_impl(stream, params_all, n_layers, D, planes, pos, pos_rows, kr, GenRows{nullptr, 0, DropCfg(), nullptr});
+}
+extern "C" int t4r_xlnet_stack_prepare_drop(void* stream, const float* const* params_all, int n_layers, int D,
+                                            float* const* planes, const float* pos, long pos_rows, float* const* kr, float drop_p,
+                                            unsigned long long seed, unsigned long long ctr, long period, float* dropped) {
+    T4R_CHECK_ARG(dropped, "xlnet_stack_prepare_drop: null pointer for the dropped rows");
+    return stack_prepare_impl(stream, params_all, n_layers, D, planes, pos, pos_rows, kr,
+                              GenRows{nullptr, period, make_drop(drop_p, seed, ctr), dropped});
 }
 
 // h1 = LayerNorm(dropout(attn_vec @ o^T) + h).  Training: ao [T, D] (pre-dropout projection), mean, rstd [T] saved;

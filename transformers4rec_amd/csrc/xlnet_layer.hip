@@ -20,18 +20,13 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-// layer_idx carries flags above its low byte (the Philox counters use the low byte only, ctr_hi):
-//   T4R_LAYER_FUSE_FINAL  this is the LAST layer of the stack and the model runs in training mode: the model-level output
-//                         dropout (HF modeling_xlnet.py:1177, key (offset, 255, SITE_FINAL)) is applied by this layer's
-//                         feed-forward kernels -- to h_out in the forward, to dh_out on load in the backward -- instead of by
-//                         two element-wise launches over [T, D] around the stack.  Needs the fused kernels (d_model 32/64/128).
-#define T4R_LAYER_FUSE_FINAL 0x100
-//   T4R_LAYER_FUSE_INPUT  this is the FIRST layer of the stack and `h` is the model's UNDROPPED input: the model-level input
-//                         dropout (HF :1116, key (offset, 255, SITE_INPUT)) is applied by the attention-block kernel on load
-//                         (the dropped rows are kept in the layer's workspace for the backward), and the backward masks d h
-//                         in xlnet_dh's final store -- instead of two element-wise launches over [T, D].  Needs the one-kernel
-//                         attention forward (t4r_xlnet_attn_block_supported) and the fused kernels.
-#define T4R_LAYER_FUSE_INPUT 0x200
+// layer_idx carries flags above its low byte (the Philox counters use the low byte only, ctr_hi): the T4R_LAYER_* bits of
+// include/t4r_hip.h, each read once at the top of layer_fwd_impl / layer_bwd_impl.
+//   T4R_LAYER_FUSE_FINAL  the model-level output dropout (key (offset, 255, SITE_FINAL)) is applied by this layer's feed-forward
+//                         kernels -- to h_out in the forward, to dh_out on load in the backward.
+//   T4R_LAYER_FUSE_INPUT  the model-level input dropout (key (offset, 255, SITE_INPUT)) is applied by the attention-block
+//                         kernel on load (the dropped rows are kept in the layer's workspace for the backward), and the
+//                         backward masks d h in xlnet_dh's final store.
 // T4R_XLNET_FUSED=0 restores the launch chain (A/B timing); default: fused kernels where they exist (d_model 32/64/128)
 static bool use_fused(int D) {
     static const int on = [] { const char* e = t4r_exp_getenv("T4R_XLNET_FUSED"); return e ? atoi(e) : 1; }();
@@ -130,10 +125,6 @@ extern "C" int t4r_xlnet_layer_ws_offsets(int B, int L, int D, int n_head, int d
     *kr_off = (long)(w.kr - base);
     return 0;
 }
-// t4r_xlnet_stack_prepared(1): the following t4r_xlnet_layer_fwd calls of this thread find their weight planes and k_r
-// already in their workspace (t4r_xlnet_stack_prepare) and skip both launches (fused path only)
-static thread_local int g_stack_prepared = 0;
-extern "C" void t4r_xlnet_stack_prepared(int on) { g_stack_prepared = on ? 1 : 0; }
 // partial tiles of the layer's split-K weight gradients (gemm_f32.hip: deterministic split-K): the split rule gives at
 // most K / 320 + 1 splits per product (>= 20 k-tiles of 16 each), K = T (2 T for d r with per-session k_r); outputs
 // 2 x 4 D^2 (FF) + 4 D^2 (q, k, v, o) + D^2 (r)
@@ -194,13 +185,15 @@ static int layer_fwd_impl(void* stream, const float* h, const float* pos_emb,
     const bool fuse_in = (layer_idx & T4R_LAYER_FUSE_INPUT) != 0 && drop;
     T4R_CHECK_ARG(!fuse_in || (use_fused(D) && use_attn_block(L, D, n_head)),
                   "xlnet_layer: the fused input dropout needs the one-kernel attention forward (L <= 32, d_model 32 / 64 / 128)");
+    // the weight planes and k_r are already in `ws` (t4r_xlnet_stack_prepare): both launches are skipped (fused path only)
+    const bool stack_prepared = (layer_idx & T4R_LAYER_STACK_PREPARED) != 0;
     if (use_fused(D)) {
         // ONE launch cuts the layer's nine weight matrices into bf16 planes; q, k, v in one token-tile launch; k_r; the
         // attention core; o-projection + dropout + residual + LayerNorm in one launch; the feed-forward block in one
         const bool block = use_attn_block(L, D, n_head);
-        if (!g_stack_prepared) RUN(t4r_xlnet_layer_prepare(stream, params, D, w.planes));
+        if (!stack_prepared) RUN(t4r_xlnet_layer_prepare(stream, params, D, w.planes));
         if (!block) RUN(t4r_xlnet_qkv_proj(stream, h, w.planes, w.qkv, T, D));
-        if (g_stack_prepared) {
+        if (stack_prepared) {
             // k_r of every layer came from one launch of the stack prologue
         } else if (drop) {
             const float* pe_b = pos_emb_b;
@@ -362,16 +355,12 @@ static SideStream* side_stream() {
     return ss.state == 1 ? &ss : nullptr;
 }
 
-// Deferred join (opt-in, t4r_xlnet_layer_bwd_defer(1)): the call returns WITHOUT making the caller's stream wait for its
+// Deferred join (opt-in, T4R_LAYER_DEFER_JOIN in layer_idx): the call returns WITHOUT making the caller's stream wait for its
 // weight-gradient streams.  After the attention core only ~35 us of critical-chain work are left (d h) but ~90 us of
 // weight-gradient work (r, q|k|v and their reduction can only start then): joined inside the call, the caller's stream
 // idled 60-95 us at every layer boundary (rocprofv3 timeline, profiles/r03_g_*).  Deferred, the next layer's backward
-// starts at once and that tail runs under it.  The caller then owes two things: every buffer the call was given
-// (h, ws, bws, dh_out, pos_emb_b, the parameter and gradient tensors) stays alive and unwritten, and
-// t4r_xlnet_layer_bwd_join(stream) is called before anything reads the parameter gradients or reuses those buffers
-// (transformers4rec_amd/transformer.py does both from the autograd engine's end-of-backward callback).
-static thread_local int g_defer_join = 0;
-extern "C" void t4r_xlnet_layer_bwd_defer(int on) { g_defer_join = on ? 1 : 0; }
+// starts at once and that tail runs under it.  What the caller then owes is stated at the bit's definition (include/t4r_hip.h;
+// transformers4rec_amd/transformer.py pays it from the autograd engine's end-of-backward callback).
 
 // grads[] are ACCUMULATED into (zero them / let the optimizer zero them between steps).
 // dh_in [T,D] is overwritten with d loss / d h.
@@ -395,6 +384,7 @@ static int layer_bwd_impl(void* stream, const float* h, const float* pos_emb,
     const bool fuse_in = (layer_idx & T4R_LAYER_FUSE_INPUT) != 0 && drop;
     T4R_CHECK_ARG(!fuse_in || (use_fused(D) && use_attn_block(L, D, n_head)),
                   "xlnet_layer: the fused input dropout needs the one-kernel attention forward (L <= 32, d_model 32 / 64 / 128)");
+    const bool defer_join = (layer_idx & T4R_LAYER_DEFER_JOIN) != 0;
     if (fuse_in) h = w.hin;          // the forward left the DROPPED input rows there: the residual and the weight-gradient operand
     long o = 0;
     auto take = [&](long nfl) { float* p = bws + o; o += align4(nfl); return p; };
@@ -572,7 +562,7 @@ static int layer_bwd_impl(void* stream, const float* h, const float* pos_emb,
         if (!block)
             RUN(t4r_xlnet_dh_impl(stream, dqkv, w.planes, dh_in, T, D,
                                   make_drop(fuse_in ? drop_p : 0.f, seed, ctr_hi(offset, 255, SITE_INPUT))));
-        if (ss && !g_defer_join) {   // join: the caller's stream continues after every weight gradient of this layer
+        if (ss && !defer_join) {   // join: the caller's stream continues after every weight gradient of this layer
             (void)hipEventRecord(ss->done_all, ss->s);
             (void)hipStreamWaitEvent(st, ss->done_all, 0);
             if (used_s2) {

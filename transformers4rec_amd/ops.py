@@ -253,11 +253,13 @@ def head_split_logits_ce_dx(ws, x, W, labels, alpha=1.0, label_smoothing=0.0, ld
     if label_smoothing > 0:
         wsum = torch.zeros(D, device=dev, dtype=torch.float32)
         colsum_(W, wsum)
+    args = (_stream(), ws.data_ptr(), _chk(x, torch.float32), x.stride(0), _chk(W, torch.float32),
+            W.stride(0), buf.data_ptr(), ldc, _chk(labels, torch.int64), loss_rows.data_ptr(), lse.data_ptr(), loss.data_ptr(),
+            dx.data_ptr(), dx.stride(0), _p(wsum), N, V, D, float(alpha), float(label_smoothing), _note(ws))
     if w_amax is not None:      # (partials, n) of ops.w_amax_of(the table's Parameter): max |W| without a pass over W
-        _lib.load().t4r_head_split_w_amax_hint(_chk(W, torch.float32), _chk(w_amax[0], torch.float32), int(w_amax[1]))
-    call("t4r_head_split_logits_ce_dx", _stream(), ws.data_ptr(), _chk(x, torch.float32), x.stride(0), _chk(W, torch.float32),
-         W.stride(0), buf.data_ptr(), ldc, _chk(labels, torch.int64), loss_rows.data_ptr(), lse.data_ptr(), loss.data_ptr(),
-         dx.data_ptr(), dx.stride(0), _p(wsum), N, V, D, float(alpha), float(label_smoothing), _note(ws))
+        call("t4r_head_split_logits_ce_dx_amax", *args, _chk(w_amax[0], torch.float32), int(w_amax[1]))
+    else:
+        call("t4r_head_split_logits_ce_dx", *args)
     return buf[:, :V], loss, loss_rows, lse, dx
 
 
@@ -325,6 +327,8 @@ SITE_INPUT, SITE_POS, SITE_PROB, SITE_ATTN_OUT, SITE_FF_ACT, SITE_FF_OUT, SITE_F
 SITE_GUMBEL = 7              # the Gumbel noise of the sampling heads: ctr_hi = dropout_ctr_hi(offset, 255, SITE_GUMBEL)
 LAYER_FUSE_FINAL = 0x100     # flag in xlnet_layer_fwd / _bwd's layer_idx: this layer also applies the model's output dropout
 LAYER_FUSE_INPUT = 0x200     # ... this (first) layer applies the model's input dropout: h is the undropped input
+LAYER_STACK_PREPARED = 0x400  # ... (_fwd only) the workspace already holds the layer's weight planes and k_r (xlnet_stack_prepare)
+LAYER_DEFER_JOIN = 0x800     # ... (_bwd only) return without joining the weight-gradient streams (xlnet_layer_bwd_join is owed)
 NO_DROP = (0.0, 0, 0)
 
 
@@ -792,20 +796,14 @@ def xlnet_layer_fwd(h, pos_emb, params, B, L, n_head, eps, ws=None, drop_p=0.0, 
                          dtype=torch.float32)
     out = torch.empty_like(h)
     parr, _keep = ptr_array([_chk(p, torch.float32, "xlnet param") for p in params])
-    lib = _lib.load()
-    if stack_prepared:
-        lib.t4r_xlnet_stack_prepared(1)
-    try:
-        args = (_stream(), _chk(h, torch.float32), _chk(pos_emb, torch.float32), parr,
-                ws.data_ptr(), out.data_ptr(), B, L, D, n_head, float(eps), float(drop_p), int(seed),
-                int(offset), int(layer_idx), _p(key_len, torch.int32), _p(pos_emb_b, torch.float32))
-        if rows is None:
-            call("t4r_xlnet_layer_fwd", *args)
-        else:
-            call("t4r_xlnet_layer_fwd_rows", *args, _chk(rows, torch.int32), int(n_rows))
-    finally:
-        if stack_prepared:
-            lib.t4r_xlnet_stack_prepared(0)
+    flags = LAYER_STACK_PREPARED if stack_prepared else 0
+    args = (_stream(), _chk(h, torch.float32), _chk(pos_emb, torch.float32), parr,
+            ws.data_ptr(), out.data_ptr(), B, L, D, n_head, float(eps), float(drop_p), int(seed),
+            int(offset), int(layer_idx) | flags, _p(key_len, torch.int32), _p(pos_emb_b, torch.float32))
+    if rows is None:
+        call("t4r_xlnet_layer_fwd", *args)
+    else:
+        call("t4r_xlnet_layer_fwd_rows", *args, _chk(rows, torch.int32), int(n_rows))
     return out, ws
 
 
@@ -835,9 +833,10 @@ def xlnet_stack_prepare(params_all, B, L, n_head, pos, drop, pos_dropout=None):
         # (p, seed, offset, out): `pos` is the plain [2L, D] encoding; the projection kernel masks it per session with this
         # forward's pos_emb dropout and leaves the dropped rows in out [B * 2L, D] (what xlnet_pos_emb_dropout returned)
         pd, seed, offset, out = pos_dropout
-        _lib.load().t4r_xlnet_stack_pos_dropout(float(pd), int(seed), dropout_ctr_hi(offset, 255, SITE_POS), rows, _chk(out, torch.float32))
-        rows = B * rows
-    call("t4r_xlnet_stack_prepare", _stream(), parr, n, D, planes, _chk(pos2, torch.float32), rows, kr)
+        call("t4r_xlnet_stack_prepare_drop", _stream(), parr, n, D, planes, _chk(pos2, torch.float32), B * rows, kr,
+             float(pd), int(seed), dropout_ctr_hi(offset, 255, SITE_POS), rows, _chk(out, torch.float32))
+    else:
+        call("t4r_xlnet_stack_prepare", _stream(), parr, n, D, planes, _chk(pos2, torch.float32), rows, kr)
     return ws
 
 
@@ -854,20 +853,14 @@ def xlnet_layer_bwd(h, pos_emb, params, grads, ws, dh_out, B, L, n_head, eps, bw
     dh_in = torch.empty_like(h)
     parr, _k1 = ptr_array([_chk(p, torch.float32) for p in params])
     garr, _k2 = ptr_array([_chk(g, torch.float32) for g in grads])
-    lib = _lib.load()
-    if defer_join is not None:
-        lib.t4r_xlnet_layer_bwd_defer(1)
-    try:
-        args = (_stream(), _chk(h), _chk(pos_emb), parr, garr, _chk(ws),
-                bws.data_ptr(), _chk(dh_out), dh_in.data_ptr(), B, L, D, n_head, float(eps), float(drop_p),
-                int(seed), int(offset), int(layer_idx), _p(key_len, torch.int32), _p(pos_emb_b, torch.float32))
-        if rows is None:
-            call("t4r_xlnet_layer_bwd", *args)
-        else:
-            call("t4r_xlnet_layer_bwd_rows", *args, _chk(rows, torch.int32), int(n_rows))
-    finally:
-        if defer_join is not None:
-            lib.t4r_xlnet_layer_bwd_defer(0)
+    flags = LAYER_DEFER_JOIN if defer_join is not None else 0
+    args = (_stream(), _chk(h), _chk(pos_emb), parr, garr, _chk(ws),
+            bws.data_ptr(), _chk(dh_out), dh_in.data_ptr(), B, L, D, n_head, float(eps), float(drop_p),
+            int(seed), int(offset), int(layer_idx) | flags, _p(key_len, torch.int32), _p(pos_emb_b, torch.float32))
+    if rows is None:
+        call("t4r_xlnet_layer_bwd", *args)
+    else:
+        call("t4r_xlnet_layer_bwd_rows", *args, _chk(rows, torch.int32), int(n_rows))
     if defer_join is not None:
         defer_join.append((h, pos_emb, list(params), list(grads), ws, bws, dh_out, key_len, pos_emb_b, rows))
     return dh_in
