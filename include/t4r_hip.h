@@ -189,16 +189,18 @@ int t4r_gemm_f32(void* stream, int transA, int transB, int M, int N, int K, floa
                  const float* bias, int epilogue, float* aux, long ldaux, int splitk, int accumulate,
                  int batch, long strideA, long strideB, long strideC, float drop_p,
                  unsigned long long seed, unsigned long long ctr_hi);
-/* Deterministic split-K for a caller's weight gradients (autograd of torch.nn.Linear's weight, block/mlp.py:133-135): between
- * _begin and _end every ACCUMULATING split-K t4r_gemm_f32 (dense C, epilogue 0) issued by THIS thread stores its partial tiles
- * into ws (cap_floats floats; M * N * splits per launch, up to 20 launches) instead of adding them with atomics, and _flush adds
- * them to C in split order with one launch -- the sum no longer depends on the order the workgroups finish.  A launch that
- * does not fit the workspace falls back to atomics.  The XLNet layer backward uses the same mechanism internally. */
-void t4r_gemm_splitk_sink_begin(float* ws, long cap_floats);
-int t4r_gemm_splitk_sink_flush(void* stream);
-void t4r_gemm_splitk_sink_end(void);
-/* launches since the last _begin (this thread) that were eligible for the sink but found no room and fell back to fp32 atomics */
-int t4r_gemm_splitk_sink_bypassed(void);
+/* Deterministic split-K for a caller's weight gradient (autograd of torch.nn.Linear's weight, block/mlp.py:133-135; the XLNet
+ * layer backward uses the same mechanism internally).
+ * C[M,N] += A[K,lda]^T @ B[K,ldb] over a long K with deterministic split-K: partial tiles into ws, then ONE launch adds
+ * them in split order.  Dense C (ldc == N).  *bypassed (may be null): 1 if the product found no room in ws and used
+ * fp32 atomics (correct, not bit-reproducible), else 0.
+ * ws: ws_floats floats, 16-byte aligned; t4r_gemm_wgrad_ws_floats(M, N, K) of them always suffice.  ws may be null (ws_floats
+ * 0) when that query returns M * N: the product is then not split and nothing is parked.  C must be 16-byte aligned with
+ * M * N a multiple of 4 for the deterministic path; otherwise the product is t4r_gemm_f32(splitk = -1, accumulate = 1).
+ * Nothing is kept between calls. */
+int  t4r_gemm_wgrad_f32(void* stream, int M, int N, int K, const float* A, long lda, const float* B, long ldb,
+                        float* C, float* ws, long ws_floats, int* bypassed);
+long t4r_gemm_wgrad_ws_floats(int M, int N, int K);   /* the launcher's own bound: M * N * min(256, K / 320 + 1) */
 
 /* Precision of every dense contraction launched after the call (process-wide setting; T4R_GEMM_PREC sets
  * the default):

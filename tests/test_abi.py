@@ -66,18 +66,17 @@ def test_missing_library_fails_loudly(monkeypatch, tmp_path):
 # (csrc/t4r_internal.h), not thread-locals armed around a call: none may come back here.  The same holds across the C ABI: what
 # the host once armed with a setter before the call it meant (a prepared stack, the deferred join, the stack prologue's positional
 # dropout, the table maximum of the one-pass head) is a flag bit in layer_idx or an argument of a sibling entry (_drop, _amax), so
-# that a call that never reaches the library leaves nothing armed for the next one.
+# that a call that never reaches the library leaves nothing armed for the next one.  And inside the layer backward: the split-K
+# sink and the side-stream redirect of the column reductions are values on that call's stack, handed to the launches that may use
+# them (GemmOpts, ReduceCtx), and the public deterministic weight gradient is ONE call (t4r_gemm_wgrad_f32), not _begin / _end.
 _ALLOWED_FILE_SCOPE_STATE = {
     "g_err": "thread-local error string (t4r_last_error)",
     "g_prec": "precision switch, set only through t4r_set_precision",
     "g_side": "thread-local per-device side streams of the layer backward (created once, never freed)",
     "g_side_all": "registry of those side streams for t4r_xlnet_layer_bwd_join",
     "g_side_mu": "mutex of that registry",
-    "g_sink": "thread-local, set and cleared INSIDE one t4r_xlnet_layer_bwd call (split-K partial sink)",
     "g_cu_budget": "CUs the backward's token-tile kernels may count on, set only through t4r_xlnet_set_cu_budget (documented in "
                    "include/t4r_hip.h; per-row results do not depend on it, batch-reduced gradients are equal up to summation order)",
-    "g_red_side": "thread-local, set and cleared inside one layer call (reduction side stream)",
-    "g_red_events": "same", "g_red_n": "same", "g_red_used": "same",
 }
 
 

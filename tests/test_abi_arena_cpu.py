@@ -205,9 +205,7 @@ EXEMPT = {
     "t4r_embedding_bwd_sorted_ws_floats": "size query: nothing launches (sizes the workspace of the t4r_embedding_bwd_sorted cases)",
     "t4r_apply_mask_bwd_ws_floats": "size query: nothing launches (sizes the workspace of the t4r_apply_mask_bwd cases)",
     "t4r_soft_embedding_bwd_ws_floats": "size query: nothing launches",
-    "t4r_gemm_splitk_sink_begin": "host-side registration of the caller's sink buffer: nothing launches",
-    "t4r_gemm_splitk_sink_end": "host-side switch: nothing launches",
-    "t4r_gemm_splitk_sink_bypassed": "host counter getter: nothing launches",
+    "t4r_gemm_wgrad_ws_floats": "size query: nothing launches",
     "t4r_set_precision": "setter: nothing launches",
     "t4r_get_precision": "getter: nothing launches",
     "t4r_set_tok_gemm_min_rows": "setter: nothing launches",

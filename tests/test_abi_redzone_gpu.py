@@ -35,7 +35,8 @@ F32, I64, I32, U8 = torch.float32, torch.int64, torch.int32, torch.uint8
 ATOMIC_ENTRIES = {
     "t4r_embedding_bwd": "csrc/embedding.hip:533-544 embedding_bwd kernels, atomicAdd(dtable + id * dim + c, ...)",
     "t4r_add_pos_bwd": "csrc/elementwise.hip:559 add_pos_bwd_kernel, atomicAdd(dpos + l * D + c, acc)",
-    "t4r_gemm_f32 (splitk != 1 outside the deterministic sink)": "csrc/gemm_kernel.h:772 split-K epilogue, atomicAdd(cp, v)",
+    "t4r_gemm_f32 (splitk != 1)": "csrc/gemm_kernel.h:772 split-K epilogue, atomicAdd(cp, v)",
+    "t4r_gemm_wgrad_f32 (*bypassed == 1 only)": "csrc/gemm_kernel.h:772, the same split-K epilogue",
     "t4r_gemm_softmax_grad_f32 (splitk != 1)": "csrc/gemm_kernel.h:772, the same split-K epilogue",
     "t4r_sampled_logits_bwd": "csrc/head.hip:353 sampled_bwd kernel, atomicAdd(dW + yi * D + d, ...)",
 }
@@ -1072,10 +1073,9 @@ for _mode in ("fp32", "fp32_bf16x3", "bf16", "fp16", "auto"):
         case("gemm", f"gemm_epilogues-{_mode}-{_M}-{_N}-{_K}-p{_p}", ["t4r_gemm_f32"])(_gemm_epilogues(_mode, _M, _N, _K, _p))
 
 
-def _gemm_splitk(mode, M, N, K, splitk, sink):
+def _gemm_splitk(mode, M, N, K, splitk):
     def fn(a, key):
         ops = _ops()
-        lib = _lib().load()
         g = gen(M + N + K + splitk)
         A, B = rn(g, K, M), rn(g, K, N)
         Ar, Br = _round_to(A, mode), _round_to(B, mode)
@@ -1083,22 +1083,6 @@ def _gemm_splitk(mode, M, N, K, splitk, sink):
         Ab, Bb = a.new("A", "in", F32, (K, _pitch(M, 4)), 0, M).set(A), a.new("B", "in", F32, (K, _pitch(N, 4)), 0, N).set(B)
         t = "test_kernels_gpu.py::test_gemm_epilogues_splitk_accumulate (rtol 1e-4, atol 2e-3)"
         tol = dict(rtol=1e-4, atol=2e-3)
-        if sink:
-            # the deterministic sink takes dense outputs only (ldc == N); its workspace is M * N * splits floats as ops.gemm_wgrad
-            # sizes it: splits = K // 320 + 1
-            splits = max(1, min(256, K // 320 + 1))
-            C = a.new("C", "inout", F32, (M, N)).set(1.0)
-            WS = a.ws("sink_ws", 4 * M * N * splits)
-            a.seal()
-            with ops.precision(mode):
-                lib.t4r_gemm_splitk_sink_begin(WS.ptr, M * N * splits)
-                try:
-                    ops.gemm(Ab.win, Bb.win, True, False, splitk=-1, accumulate=True, out=C.win)
-                    _lib().call("t4r_gemm_splitk_sink_flush", stream())
-                    assert lib.t4r_gemm_splitk_sink_bypassed() == 0
-                finally:
-                    lib.t4r_gemm_splitk_sink_end()
-            return [Out(C, ref + 1, tol, t)]
         C = a.new("C", "out", F32, (M, _pitch(N, 4)), 0, N)
         ACC = a.new("C_acc", "inout", F32, (M, _pitch(N, 4)), 0, N).set(1.0)
         a.seal()
@@ -1109,11 +1093,40 @@ def _gemm_splitk(mode, M, N, K, splitk, sink):
     return fn
 
 
+def _gemm_wgrad(mode, M, N, K, ws):
+    """t4r_gemm_wgrad_f32: the deterministic split-K weight gradient in one call, dense C (ldc == N).  ws "query": the workspace
+    is what t4r_gemm_wgrad_ws_floats returns; "one_split": M * N floats, room for one split only (at K = 700 the rule gives two:
+    the product must say so in *bypassed and use atomics); "null": none at all (K = 304 is 19 k-tiles: one split, nothing parked)"""
+    def fn(a, key):
+        ops = _ops()
+        g = gen(M + N + K - 1)      # (the operands of the gemm_splitk_sink cases as they always were: seed M + N + K + splitk)
+        A, B = rn(g, K, M), rn(g, K, N)
+        Ar, Br = _round_to(A, mode), _round_to(B, mode)
+        ref = memo(key, lambda: Ar.double().t() @ Br.double())
+        Ab, Bb = a.new("A", "in", F32, (K, _pitch(M, 4)), 0, M).set(A), a.new("B", "in", F32, (K, _pitch(N, 4)), 0, N).set(B)
+        t = "test_kernels_gpu.py::test_gemm_epilogues_splitk_accumulate (rtol 1e-4, atol 2e-3)"
+        tol = dict(rtol=1e-4, atol=2e-3)
+        C = a.new("C", "inout", F32, (M, N)).set(1.0)
+        floats = {"query": _lib().load().t4r_gemm_wgrad_ws_floats(M, N, K), "one_split": M * N, "null": 0}[ws]
+        WS = a.ws("sink_ws", 4 * floats) if floats else None
+        bypassed = ctypes.c_int(-1)
+        with ops.precision(mode):
+            call(a, "t4r_gemm_wgrad_f32", stream(), M, N, K, Ab.ptr, Ab.win.stride(0), Bb.ptr, Bb.win.stride(0), C.ptr,
+                 WS.ptr if WS else None, floats, ctypes.addressof(bypassed))
+        assert bypassed.value == (1 if ws == "one_split" else 0)
+        return [Out(C, ref + 1, tol, t, atomic=ws == "one_split")]
+    return fn
+
+
 for _mode in ("fp32", "auto", "bf16"):
     for _sk in (1, 3, -1):
-        case("gemm", f"gemm_splitk-{_mode}-65-47-700-s{_sk}", ["t4r_gemm_f32"])(_gemm_splitk(_mode, 65, 47, 700, _sk, False))
-    case("gemm", f"gemm_splitk_sink-{_mode}-64-48-700", ["t4r_gemm_f32", "t4r_gemm_splitk_sink_flush"])(
-        _gemm_splitk(_mode, 64, 48, 700, -1, True))
+        case("gemm", f"gemm_splitk-{_mode}-65-47-700-s{_sk}", ["t4r_gemm_f32"])(_gemm_splitk(_mode, 65, 47, 700, _sk))
+    # (t4r_gemm_f32 is named so that, as before, this case is what runs between the two runs of the atomic split-K case above:
+    # after the deterministic product nothing is left armed that a later t4r_gemm_f32(splitk = -1) could find)
+    case("gemm", f"gemm_splitk_sink-{_mode}-64-48-700", ["t4r_gemm_f32", "t4r_gemm_wgrad_f32"])(_gemm_wgrad(_mode, 64, 48, 700, "query"))
+case("gemm", "gemm_wgrad_bypass-fp32-64-48-700", ["t4r_gemm_wgrad_f32"])(_gemm_wgrad("fp32", 64, 48, 700, "one_split"))
+case("gemm", "gemm_wgrad_nosplit-fp32-64-48-304", ["t4r_gemm_wgrad_f32"])(_gemm_wgrad("fp32", 64, 48, 304, "query"))
+case("gemm", "gemm_wgrad_nosplit_nullws-fp32-64-48-304", ["t4r_gemm_wgrad_f32"])(_gemm_wgrad("fp32", 64, 48, 304, "null"))
 
 
 def _gemm_softmax_grad(N, V, D, eps, mode):

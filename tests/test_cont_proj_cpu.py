@@ -32,7 +32,7 @@ def test_contproj_header_library_and_prototypes_agree():
               | set(_lib.rows_header_symbols()) | set(_lib.rowadam_header_symbols()))
     assert not set(syms) & others
     # the other eight tables are as they were
-    for table, names, n in ((_lib._SIGS, _lib.header_symbols(), 127), (_lib._SIGS_SAMPLING, _lib.sampling_header_symbols(), 6),
+    for table, names, n in ((_lib._SIGS, _lib.header_symbols(), 125), (_lib._SIGS_SAMPLING, _lib.sampling_header_symbols(), 6),
                             (_lib._SIGS_FILTER, _lib.filter_header_symbols(), 7), (_lib._SIGS_OPTIM, _lib.optim_header_symbols(), 4),
                             (_lib._SIGS_PRETRAINED, _lib.pretrained_header_symbols(), 4), (_lib._SIGS_ATTN, _lib.attn_header_symbols(), 2),
                             (_lib._SIGS_ROWS, _lib.rows_header_symbols(), 5), (_lib._SIGS_ROWADAM, _lib.rowadam_header_symbols(), 2)):

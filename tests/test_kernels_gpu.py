@@ -667,6 +667,51 @@ def test_xlnet_layer_backward_is_bit_reproducible(ops):
     assert all(float(t.abs().max()) > 0 for t in runs[0])
 
 
+@pytest.mark.parametrize("p_drop", [0.0, 0.3])
+def test_xlnet_layer_unfused_backward_is_bit_reproducible_and_right(ops, p_drop):
+    """The same for the UNFUSED chain (d_model 48 has no token-tile kernels; d_head 16: the one-wave attention kernels): T = 800
+    tokens, so every weight gradient is split at least in two and goes through the layer's split-K sink, and the second stages of
+    the LayerNorm / bias / attention-bias sums go through the same sink or the side stream.  Three calls give the same bits, and
+    one of them is right against the fp64 oracle at the tolerances of test_xlnet_layer_fwd_bwd (p = 0) and
+    test_xlnet_layer_dropout_fwd_bwd (p = 0.3)."""
+    B, L, D, n = 40, 20, 48, 3
+    g = torch.Generator().manual_seed(B + L + D)
+    prm = _layer_params(g, D, n)
+    h, dout = torch.randn(B, L, D, generator=g), torch.randn(B, L, D, generator=g)
+    seed, offset, layer = 99, 7, 2
+    kw = dict(drop_p=p_drop, seed=seed, offset=offset, layer_idx=layer) if p_drop else {}
+    pos = cu(O.xlnet_pos_emb(L, D))
+    params = [cu(prm[k]) for k in ORDER]
+    hd, dd = cu(h).view(B * L, D), cu(dout).view(B * L, D)
+    runs = []
+    for _ in range(3):
+        out, ws = ops.xlnet_layer_fwd(hd, pos, params, B, L, n, 0.03, **kw)
+        grads = [torch.zeros_like(t) for t in params]
+        dh = ops.xlnet_layer_bwd(hd, pos, params, grads, ws, dd, B, L, n, 0.03, **kw)
+        torch.cuda.synchronize()
+        runs.append([dh.clone()] + [gt.clone() for gt in grads])
+    for other in runs[1:]:
+        for name, a, b in zip(("dh",) + ORDER, runs[0], other):
+            assert torch.equal(a, b), f"{name}: gradients differ between identical calls (max |d| {float((a - b).abs().max()):.3e})"
+    pr = {k: v.double().requires_grad_() for k, v in prm.items()}
+    hr = h.double().requires_grad_()
+    if p_drop:
+        C = lambda site: ops.dropout_ctr_hi(offset, layer, site)
+        masks = dict(pos=_mask(ops, (B, 2 * L, D), p_drop, seed, ops.dropout_ctr_hi(offset, 255, ops.SITE_POS)),
+                     prob=_mask(ops, (B, n, L, L), p_drop, seed, C(ops.SITE_PROB)),
+                     attn_out=_mask(ops, (B, L, D), p_drop, seed, C(ops.SITE_ATTN_OUT)),
+                     ff_act=_mask(ops, (B, L, 4 * D), p_drop, seed, C(ops.SITE_FF_ACT)),
+                     ff_out=_mask(ops, (B, L, D), p_drop, seed, C(ops.SITE_FF_OUT)))
+        ref = O.xlnet_layer_dropout(hr, pr, n, 0.03, {k: m.double() for k, m in masks.items()}, p_drop)
+    else:
+        ref = O.xlnet_layer(hr, pr, n, 0.03)
+    ref.backward(dout.double())
+    close(runs[0][0], hr.grad.reshape(B * L, D).float(), rtol=1e-4, atol=3e-4 if p_drop else 2e-4)
+    for k, gt in zip(ORDER, runs[0][1:]):
+        close(gt.reshape(-1), pr[k].grad.reshape(-1).float(), rtol=1e-4, atol=8e-4 if p_drop else 5e-4,
+              msg=lambda m, k=k: f"{k}: {m}")
+
+
 @pytest.mark.parametrize("N,V,D,eps", [(37, 1001, 64, 0.0), (130, 5003, 128, 0.1)])
 def test_gemm_softmax_grad_fused(ops, N, V, D, eps):
     """dX / dW of the head with the CE backward fused into the A operand == autograd."""

@@ -24,7 +24,7 @@ def test_fourth_header_library_and_prototypes_agree():
         assert getattr(lib, s).argtypes is not None                            # bound by load()
     others = set(_lib.header_symbols()) | set(_lib.sampling_header_symbols()) | set(_lib.filter_header_symbols())
     assert not set(syms) & others
-    assert set(_lib.header_symbols()) == set(_lib._SIGS) and len(_lib._SIGS) == 127          # the first header is as it was
+    assert set(_lib.header_symbols()) == set(_lib._SIGS) and len(_lib._SIGS) == 125          # the first header is as it was
     assert sorted(_lib.sampling_header_symbols()) == sorted(_lib._SIGS_SAMPLING) and len(_lib._SIGS_SAMPLING) == 6
     assert sorted(_lib.filter_header_symbols()) == sorted(_lib._SIGS_FILTER) and len(_lib._SIGS_FILTER) == 7
     text = open(_lib.OPTIM_HEADER_PATH).read()
@@ -221,7 +221,7 @@ def test_fused_adam_state_dict_round_trip():
 
 def test_documents_name_the_new_surface():
     readme = open(os.path.join(ROOT, "README.md")).read()
-    assert "127 entry points" in readme and "t4r_hip_optim.h" in readme and re.search(r"\b4 (optimizer )?entry points", readme)
+    assert "125 entry points" in readme and "t4r_hip_optim.h" in readme and re.search(r"\b4 (optimizer )?entry points", readme)
     integ = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     assert "t4r_hip_optim.h" in integ and "decoupled_weight_decay=True" in integ and "max_grad_norm=1.0" in integ
     assert "warmup_schedule" in integ

@@ -27,7 +27,7 @@ def test_rowadam_header_library_and_prototypes_agree():
               | set(_lib.rows_header_symbols()))
     assert not set(syms) & others
     # the other headers are as they were
-    assert set(_lib.header_symbols()) == set(_lib._SIGS) and len(_lib._SIGS) == 127
+    assert set(_lib.header_symbols()) == set(_lib._SIGS) and len(_lib._SIGS) == 125
     assert sorted(_lib.sampling_header_symbols()) == sorted(_lib._SIGS_SAMPLING) and len(_lib._SIGS_SAMPLING) == 6
     assert sorted(_lib.filter_header_symbols()) == sorted(_lib._SIGS_FILTER) and len(_lib._SIGS_FILTER) == 7
     assert sorted(_lib.optim_header_symbols()) == sorted(_lib._SIGS_OPTIM) and len(_lib._SIGS_OPTIM) == 4

@@ -603,13 +603,14 @@ extern "C" long t4r_xlnet_attn_block_bwd_part_floats(int B, int L, int D, int n_
 // Backward of t4r_xlnet_attn_block_fwd (same planes / weights / k_r / Philox keys).  wq, wk, wv: the layer's q, k, v weights
 // [D][n_head d_head] as stored.  Overwrites dh, dao, dqkv and dkr ([B][2L][D] when kr_bstride > 0, else [2L][D]);
 // ACCUMULATES d_rw, d_rr, d_gamma, d_beta.  part: t4r_xlnet_attn_block_bwd_part_floats(B, L, D, n_head) floats.
-extern "C" int t4r_xlnet_attn_block_bwd(void* stream, const float* dy, const float* ao, const float* h, const float* mean,
-                                        const float* rstd, const float* gamma, const float* planes, const float* wq,
-                                        const float* wk, const float* wv, const float* qkv, const float* kr, long kr_bstride,
-                                        const float* r_w_bias, const float* r_r_bias, const float* lse, float* dh, float* dao,
-                                        float* dqkv, float* dkr, float* d_rw, float* d_rr, float* d_gamma, float* d_beta,
-                                        float* part, int B, int L, int D, int n_head, float drop_p, unsigned long long seed,
-                                        unsigned long long ctr_prob, unsigned long long ctr_out, const int* key_len) {
+// red: where the second stages of those sums go (t4r_internal.h: ReduceCtx; null from the extern "C" entry below)
+int t4r_xlnet_attn_block_bwd_impl(void* stream, const float* dy, const float* ao, const float* h, const float* mean,
+                                  const float* rstd, const float* gamma, const float* planes, const float* wq,
+                                  const float* wk, const float* wv, const float* qkv, const float* kr, long kr_bstride,
+                                  const float* r_w_bias, const float* r_r_bias, const float* lse, float* dh, float* dao,
+                                  float* dqkv, float* dkr, float* d_rw, float* d_rr, float* d_gamma, float* d_beta,
+                                  float* part, int B, int L, int D, int n_head, float drop_p, unsigned long long seed,
+                                  unsigned long long ctr_prob, unsigned long long ctr_out, const int* key_len, ReduceCtx* red) {
     if (B <= 0) return 0;
     T4R_CHECK_ARG(t4r_xlnet_attn_block_supported(L, D, n_head), "xlnet_attn_block_bwd: unsupported shape (L <= 32, d_head 16 / 32, d_model 32 / 64 / 128)");
     T4R_CHECK_ARG(dy && ao && h && mean && rstd && gamma && planes && wq && wk && wv && qkv && kr && r_w_bias && r_r_bias && lse &&
@@ -650,10 +651,21 @@ extern "C" int t4r_xlnet_attn_block_bwd(void* stream, const float* dy, const flo
     }
 #undef T4R_AB_BWD
     T4R_LAUNCH_CHECK();
-    int rc = t4r_reduce_partials_launch(st, p.part_ln, grid_n, d_gamma, D, 1, d_beta, D, 1, nullptr, 0, 0);
+    int rc = t4r_reduce_partials_launch(st, p.part_ln, grid_n, d_gamma, D, 1, d_beta, D, 1, nullptr, 0, 0, red);
     if (rc) return rc;
     return t4r_reduce_partials_launch(st, p.part_at, grid_n * (dhd / 16), kr_bstride > 0 ? nullptr : dkr, 2 * L * D, 0, d_rw, D, 1,
-                                      d_rr, D, 1);
+                                      d_rr, D, 1, red);
+}
+extern "C" int t4r_xlnet_attn_block_bwd(void* stream, const float* dy, const float* ao, const float* h, const float* mean,
+                                        const float* rstd, const float* gamma, const float* planes, const float* wq,
+                                        const float* wk, const float* wv, const float* qkv, const float* kr, long kr_bstride,
+                                        const float* r_w_bias, const float* r_r_bias, const float* lse, float* dh, float* dao,
+                                        float* dqkv, float* dkr, float* d_rw, float* d_rr, float* d_gamma, float* d_beta,
+                                        float* part, int B, int L, int D, int n_head, float drop_p, unsigned long long seed,
+                                        unsigned long long ctr_prob, unsigned long long ctr_out, const int* key_len) {
+    return t4r_xlnet_attn_block_bwd_impl(stream, dy, ao, h, mean, rstd, gamma, planes, wq, wk, wv, qkv, kr, kr_bstride, r_w_bias,
+                                         r_r_bias, lse, dh, dao, dqkv, dkr, d_rw, d_rr, d_gamma, d_beta, part, B, L, D, n_head,
+                                         drop_p, seed, ctr_prob, ctr_out, key_len, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------ the core alone
@@ -669,7 +681,7 @@ int t4r_xlnet_attn_core16_ok(int L, int D, int n_head) {
 int t4r_xlnet_attn_core16_bwd(hipStream_t st, const float* qkv, const float* kr, const float* rw, const float* rr,
                               const float* lse, const float* dout, float* dqkv, float* part, float* dkr, float* d_rw,
                               float* d_rr, int B, int L, int n_head, int d_head, float scale, long kr_bstride, DropCfg drop,
-                              const int* key_len) {
+                              const int* key_len, ReduceCtx* red) {
     const int D = n_head * d_head;
     const int S = (B + T4R_CORE_SLOTS - 1) / T4R_CORE_SLOTS, grid_n = (B + S - 1) / S;
     AttnBlockBwd p = {};
@@ -701,5 +713,5 @@ int t4r_xlnet_attn_core16_bwd(hipStream_t st, const float* qkv, const float* kr,
     }
 #undef T4R_AB_CORE
     T4R_LAUNCH_CHECK();
-    return t4r_reduce_partials_launch(st, part, grid_n, kr_bstride > 0 ? nullptr : dkr, 2 * L * D, 0, d_rw, D, 1, d_rr, D, 1);
+    return t4r_reduce_partials_launch(st, part, grid_n, kr_bstride > 0 ? nullptr : dkr, 2 * L * D, 0, d_rw, D, 1, d_rr, D, 1, red);
 }

@@ -162,32 +162,26 @@ __global__ __launch_bounds__(512) void reduce_partials_kernel(const float* __res
     }
 }
 
-// Second-stage redirect (installed by the XLNet layer backward for the duration of one call): the
-// second stages feed parameter gradients only, so they can leave the critical chain and run on the
-// weight-gradient stream.  Each redirected launch is ordered after the first stage by its own event;
-// the installer owns the partial buffers (one per site) and joins the streams before they are reused.
-static thread_local hipStream_t g_red_side = nullptr;
-static thread_local hipEvent_t* g_red_events = nullptr;
-static thread_local int g_red_n = 0, g_red_used = 0;
-void t4r_reduce_redirect(hipStream_t side, hipEvent_t* events, int n_events) {
-    g_red_side = side; g_red_events = events; g_red_n = side ? n_events : 0; g_red_used = 0;
-}
-
+// red (t4r_internal.h: ReduceCtx; the XLNet layer backward passes its own, everyone else null): the second stages
+// feed parameter gradients only, so they can leave the critical chain.  First choice: the sums join the layer's one
+// reduction launch (gemm_f32.hip: split-K sink).  Second: this kernel on the weight-gradient stream, ordered after the
+// first stage by its own event; the owner of `red` owns the partial buffers (one per site) and joins the streams before
+// they are reused.  Null, or neither: this kernel on `st`, at once.
 int t4r_reduce_partials_launch(hipStream_t st, const float* part, int nblocks, float* o0, int n0, int a0,
-                               float* o1, int n1, int a1, float* o2, int n2, int a2) {
+                               float* o1, int n1, int a1, float* o2, int n2, int a2, ReduceCtx* red) {
     const int n = n0 + n1 + n2;
     if (n <= 0 || nblocks <= 0) return 0;
-    {   // inside a layer backward the sums join the layer's one reduction launch (gemm_f32.hip: split-K sink)
+    if (red && red->sink) {
         float* const outs[3] = {o0, o1, o2};
         const int lens[3] = {n0, n1, n2}, accs[3] = {a0, a1, a2};
-        if (t4r_splitk_sink_add_reduce(part, nblocks, n, outs, lens, accs, 3)) return 0;
+        if (t4r_splitk_sink_add_reduce(*red->sink, part, nblocks, n, outs, lens, accs, 3)) return 0;
     }
     ReduceSeg s0{o0, n0, a0}, s1{o1, n1, a1}, s2{o2, n2, a2};
-    if (g_red_side && g_red_used < g_red_n) {
-        hipEvent_t ev = g_red_events[g_red_used++];
+    if (red && red->side && red->used < red->n_events) {
+        hipEvent_t ev = red->events[red->used++];
         (void)hipEventRecord(ev, st);
-        (void)hipStreamWaitEvent(g_red_side, ev, 0);
-        st = g_red_side;
+        (void)hipStreamWaitEvent(red->side, ev, 0);
+        st = red->side;
     }
     hipLaunchKernelGGL(reduce_partials_kernel, dim3((n + 15) / 16), dim3(512), 0, st, part, nblocks, n,
                        s0, s1, s2);
@@ -382,11 +376,11 @@ __global__ __launch_bounds__(256) void add_layernorm_bwd_kernel(
 
 // ws: t4r_colreduce_ws_floats(rows, 2*D) floats.  With dropout (x = drop(a) + b): dx = d loss/d b
 // (the residual operand) and dxa = d loss/d a = dx * mask/(1-p); dxa may be NULL when p == 0.
-extern "C" int t4r_add_layernorm_bwd(void* stream, const float* a, const float* b,
-                                     const float* gamma, const float* mean, const float* rstd,
-                                     const float* dy, float* dx, float* dxa, float* dgamma,
-                                     float* dbeta, float* ws, int rows, int D, int accumulate_dx,
-                                     float drop_p, unsigned long long seed, unsigned long long ctr_hi) {
+// red (here and in t4r_colred_launch below): t4r_reduce_partials_launch above
+int t4r_add_layernorm_bwd_impl(void* stream, const float* a, const float* b, const float* gamma, const float* mean,
+                               const float* rstd, const float* dy, float* dx, float* dxa, float* dgamma, float* dbeta,
+                               float* ws, int rows, int D, int accumulate_dx, float drop_p, unsigned long long seed,
+                               unsigned long long ctr_hi, ReduceCtx* red) {
     if (rows <= 0) return 0;
     int vec, nc;
     T4R_CHECK_ARG(D > 0 && ln_pick(D, &vec, &nc), "layernorm: D out of range");
@@ -409,7 +403,15 @@ extern "C" int t4r_add_layernorm_bwd(void* stream, const float* a, const float* 
     else LN_BWD(1, 8);
 #undef LN_BWD
     T4R_LAUNCH_CHECK();
-    return t4r_reduce_partials_launch(st, ws, nblocks, dgamma, D, 1, dbeta, D, 1, nullptr, 0, 0);
+    return t4r_reduce_partials_launch(st, ws, nblocks, dgamma, D, 1, dbeta, D, 1, nullptr, 0, 0, red);
+}
+extern "C" int t4r_add_layernorm_bwd(void* stream, const float* a, const float* b,
+                                     const float* gamma, const float* mean, const float* rstd,
+                                     const float* dy, float* dx, float* dxa, float* dgamma,
+                                     float* dbeta, float* ws, int rows, int D, int accumulate_dx,
+                                     float drop_p, unsigned long long seed, unsigned long long ctr_hi) {
+    return t4r_add_layernorm_bwd_impl(stream, a, b, gamma, mean, rstd, dy, dx, dxa, dgamma, dbeta, ws, rows, D, accumulate_dx,
+                                      drop_p, seed, ctr_hi, nullptr);
 }
 
 // ---------------------------------------------------------------- activation backward + bias grad
@@ -467,8 +469,8 @@ __global__ __launch_bounds__(256) void act_bwd_bias_kernel(
     }
 }
 
-static int colred_launch(hipStream_t st, const float* dact, const float* pre, float* dpre, float* dbias,
-                         float* ws, long rows, int N, long ld, int mode, DropCfg drop) {
+int t4r_colred_launch(hipStream_t st, const float* dact, const float* pre, float* dpre, float* dbias,
+                      float* ws, long rows, int N, long ld, int mode, DropCfg drop, ReduceCtx* red) {
     if (rows <= 0) return 0;
     T4R_CHECK_ARG(N % 4 == 0 && ld % 4 == 0, "act_bwd_bias/colsum: N and ld must be multiples of 4");
     T4R_CHECK_ARG(!dbias || ws, "act_bwd_bias/colsum: workspace required");
@@ -478,7 +480,7 @@ static int colred_launch(hipStream_t st, const float* dact, const float* pre, fl
     hipLaunchKernelGGL(act_bwd_bias_kernel, dim3(nblocks), dim3(256), 0, st, dact, pre, dpre,
                        dbias ? ws : nullptr, rows, N, ld, mode, cqp, drop);
     T4R_LAUNCH_CHECK();
-    if (dbias) return t4r_reduce_partials_launch(st, ws, nblocks, dbias, N, 1, nullptr, 0, 0, nullptr, 0, 0);
+    if (dbias) return t4r_reduce_partials_launch(st, ws, nblocks, dbias, N, 1, nullptr, 0, 0, nullptr, 0, 0, red);
     return 0;
 }
 
@@ -487,13 +489,13 @@ extern "C" int t4r_act_bwd_bias(void* stream, const float* dact, const float* pr
                                 float* dbias, float* ws, long rows, int N, int mode, float drop_p,
                                 unsigned long long seed, unsigned long long ctr_hi) {
     T4R_CHECK_ARG(mode == 0 || mode == 1, "act_bwd_bias: mode 0 (gelu) or 1 (relu)");
-    return colred_launch((hipStream_t)stream, dact, pre, dpre, dbias, ws, rows, N, N, mode,
-                         make_drop(drop_p, seed, ctr_hi));
+    return t4r_colred_launch((hipStream_t)stream, dact, pre, dpre, dbias, ws, rows, N, N, mode,
+                             make_drop(drop_p, seed, ctr_hi), nullptr);
 }
 
 // out[N] += sum_rows x[rows, N]   (bias gradients).  ws: t4r_colreduce_ws_floats(rows, N)
 extern "C" int t4r_colsum(void* stream, const float* x, float* out, float* ws, long rows, int N, long ld) {
-    return colred_launch((hipStream_t)stream, x, nullptr, nullptr, out, ws, rows, N, ld, 2, make_drop(0.f, 0, 0));
+    return t4r_colred_launch((hipStream_t)stream, x, nullptr, nullptr, out, ws, rows, N, ld, 2, make_drop(0.f, 0, 0), nullptr);
 }
 
 // ---------------------------------------------------------------- element-wise dropout

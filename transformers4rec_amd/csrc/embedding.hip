@@ -485,7 +485,7 @@ extern "C" int t4r_apply_mask_bwd(void* stream, float* dy, const unsigned char* 
     const int nblk = (int)((ntok + T4R_MASK_BWD_TOK - 1) / T4R_MASK_BWD_TOK);
     apply_mask_bwd_launch((hipStream_t)stream, dy, dy, mask, ws, ntok, L, H, mode, nblk);
     T4R_LAUNCH_CHECK();
-    return t4r_reduce_partials_launch((hipStream_t)stream, ws, nblk, d_memb, H, 1, nullptr, 0, 0, nullptr, 0, 0);
+    return t4r_reduce_partials_launch((hipStream_t)stream, ws, nblk, d_memb, H, 1, nullptr, 0, 0, nullptr, 0, 0, nullptr);
 }
 // the same out of place: dx = the masked gradient, dy untouched (an autograd backward must not write its incoming gradient:
 // the module path cloned dy first -- a 10 MB device copy per step at BASELINE configs[1] -- and masked the clone in place)
@@ -501,7 +501,7 @@ extern "C" int t4r_apply_mask_bwd_to(void* stream, const float* dy, float* dx, c
     const int nblk = (int)((ntok + T4R_MASK_BWD_TOK - 1) / T4R_MASK_BWD_TOK);
     apply_mask_bwd_launch((hipStream_t)stream, dy, dx, mask, ws, ntok, L, H, mode, nblk);
     T4R_LAUNCH_CHECK();
-    return t4r_reduce_partials_launch((hipStream_t)stream, ws, nblk, d_memb, H, 1, nullptr, 0, 0, nullptr, 0, 0);
+    return t4r_reduce_partials_launch((hipStream_t)stream, ws, nblk, d_memb, H, 1, nullptr, 0, 0, nullptr, 0, 0, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -815,9 +815,9 @@ extern "C" int t4r_soft_embedding_bwd(void* stream, const float* dout, const flo
                            proj_b, table, ln_w, partA, partB, ntok, W, col, K, D, eps);
     T4R_LAUNCH_CHECK();
     // fixed-order sums over the workgroups, accumulated into the gradients
-    int rc = t4r_reduce_partials_launch(st, partA, nblocks, d_table, K * D, 1, d_proj_w, K, 1, d_proj_b, K, 1);
+    int rc = t4r_reduce_partials_launch(st, partA, nblocks, d_table, K * D, 1, d_proj_w, K, 1, d_proj_b, K, 1, nullptr);
     if (rc != 0) return rc;
-    if (ln_w) rc = t4r_reduce_partials_launch(st, partB, nblocks, d_ln_w, D, 1, d_ln_b, D, 1, nullptr, 0, 0);
+    if (ln_w) rc = t4r_reduce_partials_launch(st, partB, nblocks, d_ln_w, D, 1, d_ln_b, D, 1, nullptr, 0, 0, nullptr);
     return rc;
 }
 

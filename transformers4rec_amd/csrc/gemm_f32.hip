@@ -84,20 +84,17 @@ static bool auto_split(const GemmParams& p) { return gemm_flop(p) >= kAutoSplitM
 // ---------------------------------------------------------------- deterministic split-K (two stages)
 // Split-K launches normally add their partial tiles into C with fp32 atomics: run-to-run non-deterministic, and every
 // split of a tile finishes at the same time and hits the same addresses (same-address atomics serialise at the memory
-// side: a 128 x 128-tile experiment, tools/wgrad_planes_experiment.hip, lost 10-20 of 33-43 us to them).  While a SINK
-// is installed (t4r_splitk_sink_begin: the XLNet layer backward does, with a slice of its scratch), accumulating
-// split-K launches store their partial tiles into the sink instead and register a job; ONE launch
+// side: a 128 x 128-tile experiment, tools/wgrad_planes_experiment.hip, lost 10-20 of 33-43 us to them).  A launch that
+// is handed a SINK (t4r_internal.h: SplitKSink in GemmOpts; the XLNet layer backward keeps one on its stack over a slice
+// of its scratch and passes it to its weight-gradient products, t4r_gemm_wgrad_f32 below over the caller's workspace)
+// stores its partial tiles there instead and registers a job, if it accumulates; ONE launch
 // (t4r_splitk_sink_flush) then adds the partials of every job in split order:  C += ((p0 + p1) + p2) + ...
 // The second stages of the layer's column reductions (bias / LayerNorm / attention-bias gradients) ride in the same
-// launch (t4r_splitk_sink_add_reduce): one reduction launch per layer backward instead of four small ones + atomics.
+// launch (t4r_splitk_sink_add_reduce, through the layer's ReduceCtx): one reduction launch per layer backward instead of
+// four small ones + atomics.  The sink is an argument everywhere: a launch that was not given one never finds one.
 // Measured in the step at BASELINE configs[1] (single stream, rocprofv3): FF weight gradients 33.8 -> 32.3 us, the
 // D x D ones 24.2 -> 20.5 us, the reduction 11 us per layer: 560 -> 549 us per step.  The point is the fixed order:
 // the body's parameter gradients are now bit-reproducible run to run (tests/test_kernels_gpu.py).
-struct SplitKJob { const float* part; float* out; int n4; int splits; long stride4; int accumulate; };
-constexpr int kMaxSplitKJobs = 20;
-struct SplitKJobs { SplitKJob j[kMaxSplitKJobs]; int n; int blk_end[kMaxSplitKJobs]; };
-struct SplitKSink { float* ws = nullptr; long cap = 0, used = 0; SplitKJobs jobs; bool on = false; int bypassed = 0; };
-static thread_local SplitKSink g_sink;
 
 // workgroup = 16 float4 columns x 16 split groups; group g adds splits g, g + 16, ... in order (four loads in flight per
 // thread: a job with 256 partial rows and 32 columns is ONE workgroup, its time is its dependent load chain), then the
@@ -133,38 +130,23 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(SplitKJobs jobs) {
     }
 }
 
-void t4r_splitk_sink_begin(float* ws, long cap_floats) {
-    g_sink.ws = ws; g_sink.cap = cap_floats; g_sink.used = 0; g_sink.jobs.n = 0; g_sink.on = ws && cap_floats > 0;
-    g_sink.bypassed = 0;
-}
-int t4r_splitk_sink_flush(hipStream_t st) {
-    SplitKJobs& J = g_sink.jobs;
-    if (g_sink.on && J.n > 0) {
+int t4r_splitk_sink_flush(SplitKSink& sink, hipStream_t st) {
+    SplitKJobs& J = sink.jobs;
+    if (J.n > 0) {
         int blocks = 0;
         for (int i = 0; i < J.n; ++i) { blocks += (J.j[i].n4 + 15) / 16; J.blk_end[i] = blocks; }
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, J);
         T4R_LAUNCH_CHECK();
     }
-    J.n = 0;       // the partial buffers stay allocated until the sink ends: a later flush may run on another stream
+    J.n = 0;       // the partial buffers stay taken for the life of the sink: a later flush may run on another stream
     return 0;
 }
-void t4r_splitk_sink_end() { g_sink.on = false; g_sink.ws = nullptr; g_sink.cap = 0; g_sink.jobs.n = 0; }
-// The same mechanism for a caller outside the layer (C ABI, include/t4r_hip.h): between _begin and _end every ACCUMULATING
-// split-K t4r_gemm_f32 of this thread stores its partial tiles into `ws` instead of adding them with atomics; _flush adds
-// them in split order (one launch).  The input block's projection weight gradient uses it (features.py): it was the one
-// order-dependent sum of a BASELINE configs[2] training step.
-extern "C" void t4r_gemm_splitk_sink_begin(float* ws, long cap_floats) { t4r_splitk_sink_begin(ws, cap_floats); }
-extern "C" int t4r_gemm_splitk_sink_flush(void* stream) { return t4r_splitk_sink_flush((hipStream_t)stream); }
-extern "C" void t4r_gemm_splitk_sink_end(void) { t4r_splitk_sink_end(); }
-// split-K launches since the last _begin of this thread that were ELIGIBLE for the sink but did not get room in it (too small
-// a workspace, too many jobs) and therefore added their partial tiles with fp32 atomics: correct, but not bit-reproducible.
-// A caller that sized the workspace itself asks here instead of trusting its copy of the launcher's split rule.
-extern "C" int t4r_gemm_splitk_sink_bypassed(void) { return g_sink.bypassed; }
 
-// a split-K launch asks for room: returns the partial buffer (and registers the jobs) or null (-> atomics)
-static float* splitk_sink_take(const GemmParams& p, int batch) {
-    SplitKSink& k = g_sink;
-    if (!k.on || !p.accumulate || p.epilogue != EPI_NONE || p.sg_lse || p.rk_thr || p.tk_thr) return nullptr;
+// a split-K launch asks for room: returns the partial buffer (and registers the jobs) or null (-> atomics).  sink->bypassed
+// counts the ELIGIBLE launches that got none (buffer too small, too many jobs): correct, but not bit-reproducible
+static float* splitk_sink_take(SplitKSink* sink, const GemmParams& p, int batch) {
+    if (!sink || !p.accumulate || p.epilogue != EPI_NONE || p.sg_lse || p.rk_thr || p.tk_thr) return nullptr;
+    SplitKSink& k = *sink;
     const long n = (long)p.M * p.ldc;                       // one partial = C's [M][ldc] image (dense outputs: ldc == N)
     if (p.ldc != p.N || n % 4 || ((uintptr_t)p.C & 15) || (p.sC % 4)) return nullptr;        // not a shape the sink takes
     if (k.jobs.n + batch > kMaxSplitKJobs) { ++k.bypassed; return nullptr; }
@@ -177,11 +159,10 @@ static float* splitk_sink_take(const GemmParams& p, int batch) {
     return part;
 }
 // the second stage of a column reduction (elementwise.hip: t4r_reduce_partials_launch, out_s[i] (+)= sum_b part[b * n + off_s + i])
-// joins the same launch while a sink is installed: false -> the caller launches its own kernel
-bool t4r_splitk_sink_add_reduce(const float* part, int nblocks, int n, float* const* outs, const int* lens, const int* accs,
-                                int n_seg) {
-    SplitKSink& k = g_sink;
-    if (!k.on || nblocks <= 0 || (n & 3) || ((uintptr_t)part & 15)) return false;
+// joins the sink's launch: false -> the caller launches its own kernel
+bool t4r_splitk_sink_add_reduce(SplitKSink& k, const float* part, int nblocks, int n, float* const* outs, const int* lens,
+                                const int* accs, int n_seg) {
+    if (nblocks <= 0 || (n & 3) || ((uintptr_t)part & 15)) return false;
     int live = 0;
     for (int s = 0; s < n_seg; ++s) {
         if (lens[s] & 3) return false;
@@ -198,33 +179,46 @@ bool t4r_splitk_sink_add_reduce(const float* part, int nblocks, int n, float* co
     return true;
 }
 
-// amax (null: none): the operand maxima of this launch (t4r_internal.h: GemmAmax)
+// Split-K.  Enough workgroups to fill 256 CUs x 8 (the k-loop of one workgroup hides latency only
+// through other resident workgroups), but at least ~20 k-tiles each so that the atomics of
+// the epilogue stay a small part.  Measured (tools/gemm_bench.py): head dX 2765x128x100001
+// 1076 us at 1024 workgroups, 786 us at 4096; wgrad 128x512x20480 best at 64 splits.
+constexpr long kSplitTargetBlocks = 4096, kSplitMinTiles = 20;
+constexpr int kSplitMax = 256;
+// what ONE product with splitk = -1 can need in a sink: never more splits than this (the k-tile is at least kBkF32 deep)
+extern "C" long t4r_gemm_wgrad_ws_floats(int M, int N, int K) {
+    if (M <= 0 || N <= 0 || K <= 0) return 0;
+    return (long)M * N * min((long)kSplitMax, K / (kSplitMinTiles * kBkF32) + 1);
+}
+
+// opt (t4r_internal.h: GemmOpts): the operand maxima of this launch and the sink of its split-K partial tiles (null: none)
 // force_fp32 (the fused top-k head only: t4r_gemm_fp32_nt_launch / t4r_gemm_topk_collect_launch): this launch runs form 0
 // whatever the process-wide mode says, so that its outputs carry the bits of the materialised fp32 scores
 template <bool TA, bool TB>
-static int launch_layout(GemmParams& p, int batch, int splitk_req, hipStream_t stream, const GemmAmax* amax, bool force_fp32) {
+static int launch_layout(GemmParams& p, int batch, int splitk_req, hipStream_t stream, const GemmOpts& opt, bool force_fp32) {
     auto launch_precision = [&]() { return force_fp32 ? 0 : t4r_get_precision(); };
+    const GemmAmax* amax = opt.amax;
     const float* amax_a = amax ? amax->a : nullptr;
     const float* amax_b = amax ? amax->b : nullptr;
     const int amax_n = amax ? amax->na : 0, amax_nb = amax ? amax->nb : 0;
     p.amaxA = p.amaxB = nullptr; p.n_amax = p.n_amax_b = 0;
 #ifdef T4R_EXPERIMENTAL
-    // long-K weight gradients with a split-K sink installed (the XLNet layer backward): the K-streaming kernel (wgrad_stream.hip)
-    if (TA && !TB && splitk_req < 0 && g_sink.on && t4r_wgrad_stream_ok(p)) {
+    // long-K weight gradients that were handed a split-K sink (the XLNet layer backward): the K-streaming kernel (wgrad_stream.hip)
+    if (TA && !TB && splitk_req < 0 && opt.sink && t4r_wgrad_stream_ok(p)) {
         int splits = 1, kper = 0;
         t4r_wgrad_stream_plan(p.K, &splits, &kper);
         p.splitk = splits;
-        float* part = splitk_sink_take(p, batch);
+        float* part = splitk_sink_take(opt.sink, p, batch);
         if (part) return t4r_wgrad_stream_launch(p, batch, kper, part, stream);
         p.splitk = 1;
     }
-    if (TA && !TB && splitk_req < 0 && g_sink.on && amax_a && amax_b) {
+    if (TA && !TB && splitk_req < 0 && opt.sink && amax_a && amax_b) {
         p.amaxA = amax_a; p.amaxB = amax_b; p.n_amax = amax_n; p.n_amax_b = amax_nb;
         if (t4r_wgrad_units_ok(p)) {
             int splits = 1, kper = 0;
             t4r_wgrad_units_plan(p.K, &splits, &kper);
             p.splitk = splits;
-            float* part = splitk_sink_take(p, batch);
+            float* part = splitk_sink_take(opt.sink, p, batch);
             if (part) return t4r_wgrad_units_launch(p, batch, kper, part, stream);
             p.splitk = 1;
         }
@@ -265,11 +259,7 @@ static int launch_layout(GemmParams& p, int batch, int splitk_req, hipStream_t s
     } else if (logits_shape) {          // fp32 and the one-plane precisions
         bm = bn = 128;
     }
-    // Split-K.  Enough workgroups to fill 256 CUs x 8 (the k-loop of one workgroup hides latency only
-    // through other resident workgroups), but at least ~20 k-tiles each so that the atomics of
-    // the epilogue stay a small part.  Measured (tools/gemm_bench.py): head dX 2765x128x100001
-    // 1076 us at 1024 workgroups, 786 us at 4096; wgrad 128x512x20480 best at 64 splits.
-    constexpr long kSplitTargetBlocks = 4096, kSplitMinTiles = 20;
+    // Split-K (the rule's constants: above launch_layout)
     const int kt = (p.K + (prec ? kBkHalf : kBkF32) - 1) / (prec ? kBkHalf : kBkF32);
     int splitk = splitk_req;
     if (splitk_req == 0) {  // auto: only when the caller allows atomics (accumulating outputs)
@@ -277,7 +267,7 @@ static int launch_layout(GemmParams& p, int batch, int splitk_req, hipStream_t s
     } else if (splitk_req < 0) {
         const long blocks = (long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn) * batch;
         splitk = (int)max(1L, min((long)kt / kSplitMinTiles, kSplitTargetBlocks / max(1L, blocks)));
-        splitk = min(splitk, 256);
+        splitk = min(splitk, kSplitMax);
     }
     p.splitk = max(1, splitk);
     p.part = nullptr;
@@ -285,7 +275,7 @@ static int launch_layout(GemmParams& p, int batch, int splitk_req, hipStream_t s
         // every split owns at least one k-tile (a partial tile must be written by its split)
         const int kt_per = (kt + p.splitk - 1) / p.splitk;
         p.splitk = (kt + kt_per - 1) / kt_per;
-        if (p.splitk > 1) p.part = splitk_sink_take(p, batch);
+        if (p.splitk > 1) p.part = splitk_sink_take(opt.sink, p, batch);
     }
     p.xcd_order = 1;        // XCD-aware tile order (gemm_kernel.h); the kernel keeps the test of it
     if (p.splitk > 1) {
@@ -313,7 +303,7 @@ static int gemm_launch_impl(hipStream_t stream, int transA, int transB, int M, i
                             const float* bias, int epilogue, float* aux, long ldaux, int splitk,
                             int accumulate, int batch, long sA, long sB, long sC, const DropCfg* drop,
                             const SoftmaxGradA* sg, const RankEpi* rank, const TopkEpi* topk, bool force_fp32,
-                            const GemmAmax* amax = nullptr) {
+                            const GemmOpts& opt = GemmOpts()) {
     if (M <= 0 || N <= 0) return 0;
     T4R_CHECK_ARG(K > 0 && A && B && C && batch >= 1, "gemm: bad arguments");
     GemmParams p;
@@ -343,20 +333,20 @@ static int gemm_launch_impl(hipStream_t stream, int transA, int transB, int M, i
         p.sg_rows = sg->rows; p.sg_V = sg->V; p.sg_smooth = sg->smooth; p.sg_yoff = sg->yoff;
     }
     if (transA) {
-        if (transB) return launch_layout<true, true>(p, batch, splitk, stream, amax, force_fp32);
-        return launch_layout<true, false>(p, batch, splitk, stream, amax, force_fp32);
+        if (transB) return launch_layout<true, true>(p, batch, splitk, stream, opt, force_fp32);
+        return launch_layout<true, false>(p, batch, splitk, stream, opt, force_fp32);
     }
-    if (transB) return launch_layout<false, true>(p, batch, splitk, stream, amax, force_fp32);
-    return launch_layout<false, false>(p, batch, splitk, stream, amax, force_fp32);
+    if (transB) return launch_layout<false, true>(p, batch, splitk, stream, opt, force_fp32);
+    return launch_layout<false, false>(p, batch, splitk, stream, opt, force_fp32);
 }
 
 // Internal C++ entry used by the composite (layer / head) launchers.
 int t4r_gemm_launch(hipStream_t stream, int transA, int transB, int M, int N, int K, float alpha,
                     const float* A, long lda, const float* B, long ldb, float* C, long ldc,
                     const float* bias, int epilogue, float* aux, long ldaux, int splitk,
-                    int accumulate, int batch, long sA, long sB, long sC, const DropCfg* drop, const GemmAmax* amax) {
+                    int accumulate, int batch, long sA, long sB, long sC, const DropCfg* drop, GemmOpts opt) {
     return gemm_launch_impl(stream, transA, transB, M, N, K, alpha, A, lda, B, ldb, C, ldc, bias, epilogue, aux, ldaux, splitk,
-                            accumulate, batch, sA, sB, sC, drop, nullptr, nullptr, nullptr, false, amax);
+                            accumulate, batch, sA, sB, sC, drop, nullptr, nullptr, nullptr, false, opt);
 }
 
 extern "C" int t4r_gemm_f32(void* stream, int transA, int transB, int M, int N, int K, float alpha,
@@ -369,6 +359,20 @@ extern "C" int t4r_gemm_f32(void* stream, int transA, int transB, int M, int N, 
     return t4r_gemm_launch((hipStream_t)stream, transA, transB, M, N, K, alpha, A, lda, B, ldb, C,
                            ldc, bias, epilogue, aux, ldaux, splitk, accumulate, batch, strideA,
                            strideB, strideC, drop_p > 0.f ? &dc : nullptr);
+}
+
+// include/t4r_hip.h.  A weight gradient outside the layer (the input block's projection, features.py: once the one
+// order-dependent sum of a BASELINE configs[2] step): the sink lives on this stack for one product and its reduction.
+// ws may be null where the size query returns M * N (one split: nothing is parked).
+extern "C" int t4r_gemm_wgrad_f32(void* stream, int M, int N, int K, const float* A, long lda, const float* B, long ldb,
+                                  float* C, float* ws, long ws_floats, int* bypassed) {
+    if (bypassed) *bypassed = 0;
+    SplitKSink sink(ws, ws_floats);
+    const int rc = t4r_gemm_launch((hipStream_t)stream, 1, 0, M, N, K, 1.f, A, lda, B, ldb, C, N, nullptr, EPI_NONE, nullptr, 0,
+                                   -1, 1, 1, 0, 0, 0, nullptr, GemmOpts{nullptr, &sink});
+    if (rc != 0) return rc;
+    if (bypassed) *bypassed = sink.bypassed != 0;
+    return t4r_splitk_sink_flush(sink, (hipStream_t)stream);
 }
 
 // Head backward contractions with CrossEntropyLoss' backward fused into the A operand:

@@ -588,7 +588,7 @@ static int attn_bwd_launch(hipStream_t st, const float* q, const float* k, const
                            const float* kr, const float* rw, const float* rr, const float* out,
                            const float* lse, const float* dout, float* dq, float* dk, float* dv,
                            float* part, float* dkr, float* d_rw, float* d_rr, int B, int L, int n_head,
-                           float scale, long kr_bstride, DropCfg drop, const int* key_len) {
+                           float scale, long kr_bstride, DropCfg drop, const int* key_len, ReduceCtx* red) {
     const int D = n_head * DH;
     if (L <= 32 && (DH == 16 || DH == 32 || DH == 8) && 2 * L * (DH / 4) <= 64 * PAIRS_NKR) {
         const size_t sm2 = ((size_t)6 * L * (DH + 4) + 2 * L * (L + 1) + 2 * L) * sizeof(float);
@@ -598,7 +598,7 @@ static int attn_bwd_launch(hipStream_t st, const float* q, const float* k, const
                            kr_bstride, drop, key_len);
         T4R_LAUNCH_CHECK();
         return t4r_reduce_partials_launch(st, part, gx, kr_bstride > 0 ? nullptr : dkr, 2 * L * D, 0, d_rw, D, 1,
-                                          d_rr, D, 1);
+                                          d_rr, D, 1, red);
     }
     const size_t smem = attn_bwd_smem(L, D, n_head, kr_bstride > 0);
     static T4rLdsAttr attr;
@@ -613,19 +613,20 @@ static int attn_bwd_launch(hipStream_t st, const float* q, const float* k, const
     T4R_LAUNCH_CHECK();
     // d k_r overwritten (shared k_r: summed over sessions here), bias gradients accumulated
     return t4r_reduce_partials_launch(st, part, nblocks * hg, kr_bstride > 0 ? nullptr : dkr, 2 * L * D, 0,
-                                      d_rw, D, 1, d_rr, D, 1);
+                                      d_rw, D, 1, d_rr, D, 1, red);
 }
 
 // d_rw / d_rr are ACCUMULATED into (parameter gradients); dq/dk/dv/dk_r are overwritten.
 // prob: null, or the probabilities before dropout [B][n_head][L][L] that t4r_xlnet_attn_block_fwd_prob left (the one-wave
 // matrix-core kernel then reads them instead of recomputing the scores; lse is not read and may be null).  An internal entry:
-// the layer (xlnet_layer.hip) and the two public ones below call it.
+// the layer (xlnet_layer.hip) and the two public ones below call it.  red (t4r_internal.h: ReduceCtx; null from the public
+// entries): where the second stage of the d k_r / bias-gradient sums goes.
 int t4r_xlnet_attn_bwd_impl(void* stream, const float* q, const float* k, const float* v, const float* k_r,
                             const float* r_w_bias, const float* r_r_bias, const float* out, const float* lse,
                             const float* prob, const float* dout, float* dq, float* dk, float* dv, float* dk_r,
                             float* d_r_w_bias, float* d_r_r_bias, float* workspace, int B, int L, int n_head, int d_head,
                             int kr_per_batch, float drop_p, unsigned long long seed, unsigned long long ctr_hi,
-                            const int* key_len) {
+                            const int* key_len, ReduceCtx* red) {
     if (B == 0) return 0;
     T4R_CHECK_ARG(!prob || (n_head > 0 && t4r_xlnet_attn_mfma_ok(L, d_head)),
                   "xlnet_attn_bwd: stored probabilities are read by the one-wave kernels only (L <= 32, d_head 16 / 32)");
@@ -641,25 +642,25 @@ int t4r_xlnet_attn_bwd_impl(void* stream, const float* q, const float* k, const 
         T4R_CHECK_ARG(out != nullptr, "xlnet_attn_bwd: the forward output is needed by the general kernels (L > 64 or d_head not 8 / 16 / 32)");
         return t4r_xlnet_attn_long_bwd(st, q, k, v, k_r, r_w_bias, r_r_bias, out, lse, dout, dq, dk, dv, workspace,
                                        workspace + attn_bwd_part_floats(B, L, D, n_head), dk_r, d_r_w_bias, d_r_r_bias, B, L,
-                                       n_head, d_head, scale, bs, dc, key_len);
+                                       n_head, d_head, scale, bs, dc, key_len, red);
     }
 #ifdef T4R_EXPERIMENTAL
     {
         const long TD = (long)B * L * D;
         if (k == q + TD && v == q + 2 * TD && dk == dq + TD && dv == dq + 2 * TD && t4r_xlnet_attn_core16_ok(L, D, n_head))
             return t4r_xlnet_attn_core16_bwd(st, q, k_r, r_w_bias, r_r_bias, lse, dout, dq, workspace, dk_r, d_r_w_bias,
-                                             d_r_r_bias, B, L, n_head, d_head, scale, bs, dc, key_len);
+                                             d_r_r_bias, B, L, n_head, d_head, scale, bs, dc, key_len, red);
     }
 #endif
     if (use_mfma(L, d_head))
         return t4r_xlnet_attn_mfma_bwd(st, q, k, v, k_r, r_w_bias, r_r_bias, lse, prob, dout, dq, dk, dv, workspace, dk_r,
-                                       d_r_w_bias, d_r_r_bias, B, L, n_head, d_head, scale, bs, dc, key_len);
+                                       d_r_w_bias, d_r_r_bias, B, L, n_head, d_head, scale, bs, dc, key_len, red);
     T4R_CHECK_ARG(!prob, "xlnet_attn_bwd: stored probabilities are read by the one-wave matrix-core kernels only");
     T4R_CHECK_ARG(attn_bwd_smem(L, D, n_head) <= 160 * 1024, "xlnet_attn_bwd: L*d_model too large for LDS");
     switch (d_head) {
-        case 8: return attn_bwd_launch<8>(st, q, k, v, k_r, r_w_bias, r_r_bias, out, lse, dout, dq, dk, dv, workspace, dk_r, d_r_w_bias, d_r_r_bias, B, L, n_head, scale, bs, dc, key_len);
-        case 16: return attn_bwd_launch<16>(st, q, k, v, k_r, r_w_bias, r_r_bias, out, lse, dout, dq, dk, dv, workspace, dk_r, d_r_w_bias, d_r_r_bias, B, L, n_head, scale, bs, dc, key_len);
-        case 32: return attn_bwd_launch<32>(st, q, k, v, k_r, r_w_bias, r_r_bias, out, lse, dout, dq, dk, dv, workspace, dk_r, d_r_w_bias, d_r_r_bias, B, L, n_head, scale, bs, dc, key_len);
+        case 8: return attn_bwd_launch<8>(st, q, k, v, k_r, r_w_bias, r_r_bias, out, lse, dout, dq, dk, dv, workspace, dk_r, d_r_w_bias, d_r_r_bias, B, L, n_head, scale, bs, dc, key_len, red);
+        case 16: return attn_bwd_launch<16>(st, q, k, v, k_r, r_w_bias, r_r_bias, out, lse, dout, dq, dk, dv, workspace, dk_r, d_r_w_bias, d_r_r_bias, B, L, n_head, scale, bs, dc, key_len, red);
+        case 32: return attn_bwd_launch<32>(st, q, k, v, k_r, r_w_bias, r_r_bias, out, lse, dout, dq, dk, dv, workspace, dk_r, d_r_w_bias, d_r_r_bias, B, L, n_head, scale, bs, dc, key_len, red);
     }
     t4r_set_error("xlnet_attn_bwd: d_head must be 8, 16 or 32");
     return -1;
@@ -674,7 +675,7 @@ extern "C" int t4r_xlnet_attn_bwd(void* stream, const float* q, const float* k, 
                                   unsigned long long ctr_hi, const int* key_len) {
     return t4r_xlnet_attn_bwd_impl(stream, q, k, v, k_r, r_w_bias, r_r_bias, out, lse, nullptr, dout, dq, dk, dv, dk_r,
                                    d_r_w_bias, d_r_r_bias, workspace, B, L, n_head, d_head, kr_per_batch, drop_p, seed, ctr_hi,
-                                   key_len);
+                                   key_len, nullptr);
 }
 // include/t4r_hip_attn.h
 extern "C" int t4r_xlnet_attn_bwd_prob(void* stream, const float* q, const float* k, const float* v, const float* k_r,
@@ -685,5 +686,5 @@ extern "C" int t4r_xlnet_attn_bwd_prob(void* stream, const float* q, const float
     T4R_CHECK_ARG(prob != nullptr, "xlnet_attn_bwd_prob: null pointer");
     return t4r_xlnet_attn_bwd_impl(stream, q, k, v, k_r, r_w_bias, r_r_bias, nullptr, nullptr, prob, dout, dq, dk, dv, dk_r,
                                    d_r_w_bias, d_r_r_bias, workspace, B, L, n_head, d_head, kr_per_batch, drop_p, seed, ctr_hi,
-                                   nullptr);
+                                   nullptr, nullptr);
 }

@@ -500,7 +500,7 @@ int t4r_xlnet_attn_long_fwd(hipStream_t st, const float* q, const float* k, cons
 int t4r_xlnet_attn_long_bwd(hipStream_t st, const float* q, const float* k, const float* v, const float* kr, const float* rw,
                             const float* rr, const float* out, const float* lse, const float* dout, float* dq, float* dk,
                             float* dv, float* part, float* delta, float* dkr, float* d_rw, float* d_rr, int B, int L, int n_head,
-                            int d_head, float scale, long kr_bstride, DropCfg drop, const int* key_len) {
+                            int d_head, float scale, long kr_bstride, DropCfg drop, const int* key_len, ReduceCtx* red) {
     const int D = n_head * d_head, nblocks = t4r_xlnet_attn_bwd_blocks(B);
     LongArgs a{};
     a.q = q; a.k = k; a.v = v; a.kr = kr; a.rw = rw; a.rr = rr; a.out = out; a.lse = lse; a.dout = dout;
@@ -526,7 +526,7 @@ int t4r_xlnet_attn_long_bwd(hipStream_t st, const float* q, const float* k, cons
 #undef T4R_LONG_BWD
     T4R_LAUNCH_CHECK();
     // d k_r overwritten (shared k_r: summed over the workgroups here), bias gradients accumulated
-    return t4r_reduce_partials_launch(st, part, nblocks, shared ? dkr : nullptr, 2 * L * D, 0, d_rw, D, 1, d_rr, D, 1);
+    return t4r_reduce_partials_launch(st, part, nblocks, shared ? dkr : nullptr, 2 * L * D, 0, d_rw, D, 1, d_rr, D, 1, red);
 }
 
 // ---- scaled-dot-product core (GPT-2 / BERT): any L, d_head a multiple of 4 up to 128

@@ -503,7 +503,8 @@ int t4r_xlnet_attn_mfma_fwd(hipStream_t st, const float* q, const float* k, cons
 int t4r_xlnet_attn_mfma_bwd(hipStream_t st, const float* q, const float* k, const float* v, const float* kr,
                             const float* rw, const float* rr, const float* lse, const float* prob, const float* dout,
                             float* dq, float* dk, float* dv, float* part, float* dkr, float* d_rw, float* d_rr, int B,
-                            int L, int n_head, int d_head, float scale, long kr_bstride, DropCfg drop, const int* key_len) {
+                            int L, int n_head, int d_head, float scale, long kr_bstride, DropCfg drop, const int* key_len,
+                            ReduceCtx* red) {
     const int D = n_head * d_head;
     // (one (session, head) unit per wave and 1024 x n_head waves: at four heads exactly one residency of 256 CUs.  Shrinking the
     //  grid to the CU budget was tried (round 5) and is worse: the unit is a whole session, so 1024 sessions on 960 workgroups
@@ -529,5 +530,5 @@ int t4r_xlnet_attn_mfma_bwd(hipStream_t st, const float* q, const float* k, cons
 #undef T4R_BWD
     T4R_LAUNCH_CHECK();
     return t4r_reduce_partials_launch(st, part, gx, kr_bstride > 0 ? nullptr : dkr, 2 * L * D, 0, d_rw, D, 1, d_rr,
-                                      D, 1);
+                                      D, 1, red);
 }

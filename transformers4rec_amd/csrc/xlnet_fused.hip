@@ -822,9 +822,9 @@ int t4r_xlnet_ff_bwd_impl(void* stream, const float* dy, const float* ffout, con
     };
     const int rc = launch();
     if (rc != 0) return rc;
-    int rc2 = t4r_reduce_partials_launch(st, partA, nwg, d_gamma, D, 1, d_beta, D, 1, d_b2, D, 1);
+    int rc2 = t4r_reduce_partials_launch(st, partA, nwg, d_gamma, D, 1, d_beta, D, 1, d_b2, D, 1, opt.red);
     if (rc2 != 0) return rc2;
-    return t4r_reduce_partials_launch(st, partB, nwg, d_b1, 4 * D, 1, nullptr, 0, 0, nullptr, 0, 0);
+    return t4r_reduce_partials_launch(st, partB, nwg, d_b1, 4 * D, 1, nullptr, 0, 0, nullptr, 0, 0, opt.red);
 }
 extern "C" int t4r_xlnet_ff_bwd(void* stream, const float* dy, const float* ffout, const float* h1, const float* mean,
                                 const float* rstd, const float* gamma, const float* ffpre, const float* planes,

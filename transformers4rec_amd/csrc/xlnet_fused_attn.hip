@@ -947,10 +947,11 @@ extern "C" long t4r_xlnet_ln1_bwd_part_floats(long T, int D) { return ((T + 15) 
 // the o-projection output: rows of the o weight gradient d o += dao^T @ attn_vec) and dav (d loss / d attn_vec);
 // d_gamma, d_beta ACCUMULATED.  part: t4r_xlnet_ln1_bwd_part_floats(T, D) floats.
 // include/t4r_hip_rows.h: the same on n mapped rows; dh, dao, dav are zeroed first (three fills on the caller's stream)
-extern "C" int t4r_xlnet_ln1_bwd_rows(void* stream, const float* dy, const float* ao, const float* h, const float* mean,
-                                      const float* rstd, const float* gamma, const float* planes, float* dh, float* dao,
-                                      float* dav, float* d_gamma, float* d_beta, float* part, long T, int D, float drop_p,
-                                      unsigned long long seed, unsigned long long ctr_hi, const int* rows, int n) {
+// red (both forms; null from the public entries): where the second stage of d gamma / d beta goes (t4r_internal.h: ReduceCtx)
+int t4r_xlnet_ln1_bwd_rows_impl(void* stream, const float* dy, const float* ao, const float* h, const float* mean,
+                                const float* rstd, const float* gamma, const float* planes, float* dh, float* dao, float* dav,
+                                float* d_gamma, float* d_beta, float* part, long T, int D, float drop_p, unsigned long long seed,
+                                unsigned long long ctr_hi, const int* rows, int n, ReduceCtx* red) {
     T4R_CHECK_ARG(rows != nullptr, "xlnet_ln1_bwd_rows: null row map");
     T4R_CHECK_ARG(T >= 1 && n >= 1 && n <= T, "xlnet_ln1_bwd_rows: the number of mapped rows must be in [1, T]");
     T4R_CHECK_ARG(t4r_xlnet_fused_supported(D) && dy && ao && h && mean && rstd && gamma && planes && dh && dao && dav && part,
@@ -979,13 +980,20 @@ extern "C" int t4r_xlnet_ln1_bwd_rows(void* stream, const float* dy, const float
     ATTN_DISPATCH(CALL, D, R)
 #undef CALL
     T4R_LAUNCH_CHECK();
-    return t4r_reduce_partials_launch(st, part, nwg, d_gamma, D, 1, d_beta, D, 1, nullptr, 0, 0);
+    return t4r_reduce_partials_launch(st, part, nwg, d_gamma, D, 1, d_beta, D, 1, nullptr, 0, 0, red);
+}
+extern "C" int t4r_xlnet_ln1_bwd_rows(void* stream, const float* dy, const float* ao, const float* h, const float* mean,
+                                      const float* rstd, const float* gamma, const float* planes, float* dh, float* dao,
+                                      float* dav, float* d_gamma, float* d_beta, float* part, long T, int D, float drop_p,
+                                      unsigned long long seed, unsigned long long ctr_hi, const int* rows, int n) {
+    return t4r_xlnet_ln1_bwd_rows_impl(stream, dy, ao, h, mean, rstd, gamma, planes, dh, dao, dav, d_gamma, d_beta, part, T, D,
+                                       drop_p, seed, ctr_hi, rows, n, nullptr);
 }
 
-extern "C" int t4r_xlnet_ln1_bwd(void* stream, const float* dy, const float* ao, const float* h, const float* mean,
-                                 const float* rstd, const float* gamma, const float* planes, float* dh, float* dao, float* dav,
-                                 float* d_gamma, float* d_beta, float* part, long T, int D, float drop_p,
-                                 unsigned long long seed, unsigned long long ctr_hi) {
+int t4r_xlnet_ln1_bwd_impl(void* stream, const float* dy, const float* ao, const float* h, const float* mean, const float* rstd,
+                           const float* gamma, const float* planes, float* dh, float* dao, float* dav, float* d_gamma,
+                           float* d_beta, float* part, long T, int D, float drop_p, unsigned long long seed,
+                           unsigned long long ctr_hi, ReduceCtx* red) {
     if (T <= 0) return 0;
     T4R_CHECK_ARG(t4r_xlnet_fused_supported(D) && dy && ao && h && mean && rstd && gamma && planes && dh && dao && dav && part,
                   "xlnet_ln1_bwd: bad arguments");
@@ -1010,7 +1018,14 @@ extern "C" int t4r_xlnet_ln1_bwd(void* stream, const float* dy, const float* ao,
     ATTN_DISPATCH(CALL, D, R)
 #undef CALL
     T4R_LAUNCH_CHECK();
-    return t4r_reduce_partials_launch(st, part, nwg, d_gamma, D, 1, d_beta, D, 1, nullptr, 0, 0);
+    return t4r_reduce_partials_launch(st, part, nwg, d_gamma, D, 1, d_beta, D, 1, nullptr, 0, 0, red);
+}
+extern "C" int t4r_xlnet_ln1_bwd(void* stream, const float* dy, const float* ao, const float* h, const float* mean,
+                                 const float* rstd, const float* gamma, const float* planes, float* dh, float* dao, float* dav,
+                                 float* d_gamma, float* d_beta, float* part, long T, int D, float drop_p,
+                                 unsigned long long seed, unsigned long long ctr_hi) {
+    return t4r_xlnet_ln1_bwd_impl(stream, dy, ao, h, mean, rstd, gamma, planes, dh, dao, dav, d_gamma, d_beta, part, T, D, drop_p,
+                                  seed, ctr_hi, nullptr);
 }
 
 // dh [T, D] += d q @ W_q^T + d k @ W_k^T + d v @ W_v^T   (dqkv [3][T][D])

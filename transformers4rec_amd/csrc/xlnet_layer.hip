@@ -410,22 +410,18 @@ static int layer_bwd_impl(void* stream, const float* h, const float* pos_emb,
     float* block_part = take(attn_block_bwd_part(B, L, D, n_head));
 #endif
     const bool fused = use_fused(D);
-    // the split-K weight gradients of this call leave their partial tiles here; one launch adds them at the end
-    struct SinkGuard {
-        SinkGuard(float* ws, long cap) { t4r_splitk_sink_begin(ws, cap); }
-        ~SinkGuard() { t4r_splitk_sink_end(); }
-    } sink_guard(take(splitk_sink_floats(T, D)), splitk_sink_floats(T, D));
+    // the split-K weight gradients of this call (the products that are passed `wgrad`) leave their partial tiles here; one
+    // launch per half layer adds them
+    SplitKSink sink(take(splitk_sink_floats(T, D)), splitk_sink_floats(T, D));
+    const GemmOpts wgrad{nullptr, &sink};
     float* h1c = take(TD);                      // row-mapped backward: the mapped rows of h1 in compact order (W1 gradient operand)
 
     SideStream* ss = side_stream();
-    struct RedirectGuard {      // second stages of the column reductions -> side stream, for this call only
-        bool on;
-        RedirectGuard(SideStream* s) : on(false) {
-            static const int enabled = [] { const char* e = t4r_exp_getenv("T4R_LAYER_SIDE_REDUCE"); return e ? atoi(e) : 1; }();
-            if (s && enabled) { t4r_reduce_redirect(s->s, s->red, 8); on = true; }
-        }
-        ~RedirectGuard() { if (on) t4r_reduce_redirect(nullptr, nullptr, 0); }
-    } redirect(ss);
+    // second stages of the column reductions (the entries below that are passed `red`): into the sink, else the side stream
+    static const int side_reduce = [] { const char* e = t4r_exp_getenv("T4R_LAYER_SIDE_REDUCE"); return e ? atoi(e) : 1; }();
+    ReduceCtx red_ctx{&sink};
+    if (ss && side_reduce) { red_ctx.side = ss->s; red_ctx.events = ss->red; red_ctx.n_events = 8; }
+    ReduceCtx* const red = &red_ctx;
     int n_fork = 0;
     // wg(): the stream a weight-gradient GEMM goes to; it first waits for everything issued on `st` so far
     auto wg = [&]() -> hipStream_t {
@@ -465,7 +461,7 @@ static int layer_bwd_impl(void* stream, const float* h, const float* pos_emb,
         const int Tk = rows ? n_rows : T;
         const int na = t4r_xlnet_ff_amax_count(Tk), nb = t4r_xlnet_ff_amax_count_bwd(Tk);
         float* am = w.amax;          // max |h1|, max |act| (forward), max |d pre|, max |d ffout| (now): one float per workgroup
-        const FFOpts ff_opt{am + 2 * ns, am + 3 * ns, fuse_final && drop, ctr_hi(offset, 255, SITE_FINAL)};
+        const FFOpts ff_opt{am + 2 * ns, am + 3 * ns, fuse_final && drop, ctr_hi(offset, 255, SITE_FINAL), red};
         RUN(t4r_xlnet_ff_bwd_impl(stream, dh_out, w.ffout, w.h1, w.mean2, w.rstd2, params[P_LN2W], w.ffpre, w.planes, dx, dfo, dff,
                                   grads[P_LN2W], grads[P_LN2B], grads[P_B2], grads[P_B1], ff_part, T, D, drop_p, seed,
                                   C(SITE_FF_ACT), C(SITE_FF_OUT), rows, n_rows, h1c, ff_opt));
@@ -474,45 +470,45 @@ static int layer_bwd_impl(void* stream, const float* h, const float* pos_emb,
         const GemmAmax amax_w2{am + 3 * ns, nb, am + ns, na}, amax_w1{am + 2 * ns, nb, am, na};
         // (with a map the two products contract over the n_rows compact rows)
         RUN(t4r_gemm_launch(wg(), 1, 0, D, 4 * D, Tk, 1.f, dfo, D, w.ffact, 4 * D, grads[P_W2], 4 * D, nullptr,
-                            EPI_NONE, nullptr, 0, -1, 1, 1, 0, 0, 0, nullptr, hs ? &amax_w2 : nullptr));
+                            EPI_NONE, nullptr, 0, -1, 1, 1, 0, 0, 0, nullptr, GemmOpts{hs ? &amax_w2 : nullptr, &sink}));
         {
             hipStream_t s1 = wg_again();
             RUN(t4r_gemm_launch(s1, 1, 0, 4 * D, D, Tk, 1.f, dff, 4 * D, rows ? h1c : w.h1, D, grads[P_W1], D, nullptr,
-                                EPI_NONE, nullptr, 0, -1, 1, 1, 0, 0, 0, nullptr, hs ? &amax_w1 : nullptr));
+                                EPI_NONE, nullptr, 0, -1, 1, 1, 0, 0, 0, nullptr, GemmOpts{hs ? &amax_w1 : nullptr, &sink}));
             // first reduction launch of the call: W2, W1 and the bias / LayerNorm-2 sums of the feed-forward half
-            RUN(t4r_splitk_sink_flush(s1));
+            RUN(t4r_splitk_sink_flush(sink, s1));
         }
     } else {
     // LN2: y = LN(drop(ffout) + h1): dx = d h1 (residual part), d ffout = dxa (or dx when p = 0)
-    RUN(t4r_add_layernorm_bwd(stream, w.ffout, w.h1, params[P_LN2W], w.mean2, w.rstd2, dh_out, dx, dxa,
-                              grads[P_LN2W], grads[P_LN2B], red_ln2, T, D, 0, drop_p, seed, C(SITE_FF_OUT)));
+    RUN(t4r_add_layernorm_bwd_impl(stream, w.ffout, w.h1, params[P_LN2W], w.mean2, w.rstd2, dh_out, dx, dxa,
+                                   grads[P_LN2W], grads[P_LN2B], red_ln2, T, D, 0, drop_p, seed, C(SITE_FF_OUT), red));
     const float* dffout = drop ? dxa : dx;
     // FF2: ffout = ffact @ w2^T + b2
     RUN(t4r_gemm_launch(st, 0, 0, T, 4 * D, D, 1.f, dffout, D, params[P_W2], 4 * D, dff, 4 * D, nullptr,
                         EPI_NONE, nullptr, 0, 1, 0, 1, 0, 0, 0, nullptr));
-    RUN(t4r_colsum(stream, dffout, grads[P_B2], red_b2, T, D, D));
+    RUN(t4r_colred_launch(st, dffout, nullptr, nullptr, grads[P_B2], red_b2, T, D, D, 2, make_drop(0.f, 0, 0), red));
     RUN(t4r_gemm_launch(wg(), 1, 0, D, 4 * D, T, 1.f, dffout, D, w.ffact, 4 * D, grads[P_W2], 4 * D, nullptr,
-                        EPI_NONE, nullptr, 0, -1, 1, 1, 0, 0, 0, nullptr));
+                        EPI_NONE, nullptr, 0, -1, 1, 1, 0, 0, 0, nullptr, wgrad));
     if (ss) (void)hipEventRecord(ss->done_ff2, ss->s);
     // ffact = drop(gelu(ffpre)) ; GELU' + bias1
-    RUN(t4r_act_bwd_bias(stream, dff, w.ffpre, dff, grads[P_B1], red_act, T, 4 * D, 0, drop_p, seed,
-                         C(SITE_FF_ACT)));
+    RUN(t4r_colred_launch(st, dff, w.ffpre, dff, grads[P_B1], red_act, T, 4 * D, 4 * D, 0,
+                          make_drop(drop_p, seed, C(SITE_FF_ACT)), red));
     // FF1: ffpre = h1 @ w1^T + b1 ;  d h1 = dx (residual) + dff @ w1
     if (ss && !drop) (void)hipStreamWaitEvent(st, ss->done_ff2, 0);   // p = 0: the FF2 wgrad reads dx, written next
     RUN(t4r_gemm_launch(st, 0, 0, T, D, 4 * D, 1.f, dff, 4 * D, params[P_W1], D, dx, D, nullptr,
                         EPI_NONE, nullptr, 0, 1, 1, 1, 0, 0, 0, nullptr));
     RUN(t4r_gemm_launch(wg(), 1, 0, 4 * D, D, T, 1.f, dff, 4 * D, w.h1, D, grads[P_W1], D, nullptr,
-                        EPI_NONE, nullptr, 0, -1, 1, 1, 0, 0, 0, nullptr));
+                        EPI_NONE, nullptr, 0, -1, 1, 1, 0, 0, 0, nullptr, wgrad));
     }
     if (fused) {
 #ifdef T4R_EXPERIMENTAL
         const bool block = use_attn_block_bwd(L, D, n_head);
         if (block) {
             // LayerNorm-1 backward, d attn_vec, the attention core backward and d h: ONE launch (tools/experimental)
-            RUN(t4r_xlnet_attn_block_bwd(stream, dx, w.ao, h, w.mean1, w.rstd1, params[P_LN1W], w.planes, params[P_Q], params[P_K],
+            RUN(t4r_xlnet_attn_block_bwd_impl(stream, dx, w.ao, h, w.mean1, w.rstd1, params[P_LN1W], w.planes, params[P_Q], params[P_K],
                                          params[P_V], w.qkv, w.kr, drop ? 2L * L * D : 0L, params[P_RWB], params[P_RRB], w.lse,
                                          dh_in, dao_buf, dqkv, dkr, grads[P_RWB], grads[P_RRB], grads[P_LN1W], grads[P_LN1B],
-                                         block_part, B, L, D, n_head, drop_p, seed, C(SITE_PROB), C(SITE_ATTN_OUT), key_len));
+                                         block_part, B, L, D, n_head, drop_p, seed, C(SITE_PROB), C(SITE_ATTN_OUT), key_len, red));
         } else
 #else
         constexpr bool block = false;
@@ -522,25 +518,26 @@ static int layer_bwd_impl(void* stream, const float* h, const float* pos_emb,
         // (with a map: dx holds the mapped rows in compact order; dh_in, dao_buf, dav are zeroed and written at the token rows, so
         // the attention core, d h and the o product -- K = T on the zero-filled d attn_out -- run as ever)
         if (rows)
-            RUN(t4r_xlnet_ln1_bwd_rows(stream, dx, w.ao, h, w.mean1, w.rstd1, params[P_LN1W], w.planes, dh_in, dao_buf, dav,
-                                       grads[P_LN1W], grads[P_LN1B], ln1_part, T, D, drop_p, seed, C(SITE_ATTN_OUT), rows, n_rows));
+            RUN(t4r_xlnet_ln1_bwd_rows_impl(stream, dx, w.ao, h, w.mean1, w.rstd1, params[P_LN1W], w.planes, dh_in, dao_buf, dav,
+                                            grads[P_LN1W], grads[P_LN1B], ln1_part, T, D, drop_p, seed, C(SITE_ATTN_OUT), rows,
+                                            n_rows, red));
         else
-        RUN(t4r_xlnet_ln1_bwd(stream, dx, w.ao, h, w.mean1, w.rstd1, params[P_LN1W], w.planes, dh_in, dao_buf, dav,
-                              grads[P_LN1W], grads[P_LN1B], ln1_part, T, D, drop_p, seed, C(SITE_ATTN_OUT)));
+        RUN(t4r_xlnet_ln1_bwd_impl(stream, dx, w.ao, h, w.mean1, w.rstd1, params[P_LN1W], w.planes, dh_in, dao_buf, dav,
+                                   grads[P_LN1W], grads[P_LN1B], ln1_part, T, D, drop_p, seed, C(SITE_ATTN_OUT), red));
         // (the one-kernel forward left the probabilities in the workspace: the core reads them instead of recomputing the scores)
         RUN(t4r_xlnet_attn_bwd_impl(stream, w.qkv, w.qkv + TD, w.qkv + 2 * TD, w.kr, params[P_RWB],
                                     params[P_RRB], w.av, w.lse, use_attn_block(L, D, n_head) ? w.prob : nullptr, dav, dqkv,
                                     dqkv + TD, dqkv + 2 * TD, dkr, grads[P_RWB], grads[P_RRB], attn_ws, B, L, n_head, dh, drop,
-                                    drop_p, seed, C(SITE_PROB), key_len));
+                                    drop_p, seed, C(SITE_PROB), key_len, red));
         }
         // ONE event for the o, r and q|k|v products (their operands are all complete here; with the join deferred nothing
         // is gained by starting the o product before the attention core)
         hipStream_t sw = wg2();
         RUN(t4r_gemm_launch(sw, 1, 0, D, D, T, 1.f, dao_buf, D, w.av, D, grads[P_O], D, nullptr, EPI_NONE,
-                            nullptr, 0, -1, 1, 1, 0, 0, 0, nullptr));
+                            nullptr, 0, -1, 1, 1, 0, 0, 0, nullptr, wgrad));
         if (drop) {
             RUN(t4r_gemm_launch(sw, 1, 0, D, D, B * 2 * L, 1.f, pos_emb_b ? pos_emb_b : w.pe_b, D, dkr, D, grads[P_R], D,
-                                nullptr, EPI_NONE, nullptr, 0, -1, 1, 1, 0, 0, 0, nullptr));
+                                nullptr, EPI_NONE, nullptr, 0, -1, 1, 1, 0, 0, 0, nullptr, wgrad));
         } else {
             // shared k_r: d k_r is finished by a reduction that was redirected to the FIRST side stream -- its consumer follows it there
             RUN(t4r_gemm_launch(wg(), 1, 0, D, D, 2 * L, 1.f, pos_emb, D, dkr, D, grads[P_R], D, nullptr,
@@ -550,15 +547,15 @@ static int layer_bwd_impl(void* stream, const float* h, const float* pos_emb,
             float* gz[3] = {grads[P_Q], grads[P_K], grads[P_V]};
             if (gz[1] == gz[0] + DD && gz[2] == gz[0] + 2 * DD) {
                 RUN(t4r_gemm_launch(sw, 1, 0, D, D, T, 1.f, h, D, dqkv, D, gz[0], D, nullptr, EPI_NONE, nullptr,
-                                    0, -1, 1, 3, 0, TD, DD, nullptr));
+                                    0, -1, 1, 3, 0, TD, DD, nullptr, wgrad));
             } else {
                 for (int z = 0; z < 3; ++z)
                     RUN(t4r_gemm_launch(sw, 1, 0, D, D, T, 1.f, h, D, dqkv + z * TD, D, gz[z], D, nullptr,
-                                        EPI_NONE, nullptr, 0, -1, 1, 1, 0, 0, 0, nullptr));
+                                        EPI_NONE, nullptr, 0, -1, 1, 1, 0, 0, 0, nullptr, wgrad));
             }
         }
         // second reduction launch: o, r, q, k, v and the LayerNorm-1 / attention-bias sums (same stream as their products)
-        RUN(t4r_splitk_sink_flush(sw));
+        RUN(t4r_splitk_sink_flush(sink, sw));
         if (!block)
             RUN(t4r_xlnet_dh_impl(stream, dqkv, w.planes, dh_in, T, D,
                                   make_drop(fuse_in ? drop_p : 0.f, seed, ctr_hi(offset, 255, SITE_INPUT))));
@@ -574,24 +571,24 @@ static int layer_bwd_impl(void* stream, const float* h, const float* pos_emb,
     }
     // LN1: h1 = LN(drop(ao) + h): dh_in = d h (residual part), d ao = dxa (or dh_in when p = 0)
     if (ss && drop) (void)hipStreamWaitEvent(st, ss->done_ff2, 0);    // the FF2 wgrad reads dxa, overwritten here
-    RUN(t4r_add_layernorm_bwd(stream, w.ao, h, params[P_LN1W], w.mean1, w.rstd1, dx, dh_in, dxa,
-                              grads[P_LN1W], grads[P_LN1B], red_ln1, T, D, 0, drop_p, seed, C(SITE_ATTN_OUT)));
+    RUN(t4r_add_layernorm_bwd_impl(stream, w.ao, h, params[P_LN1W], w.mean1, w.rstd1, dx, dh_in, dxa,
+                                   grads[P_LN1W], grads[P_LN1B], red_ln1, T, D, 0, drop_p, seed, C(SITE_ATTN_OUT), red));
     const float* dao = drop ? dxa : dh_in;
     // O projection: ao = av @ o^T
     RUN(t4r_gemm_launch(st, 0, 0, T, D, D, 1.f, dao, D, params[P_O], D, dav, D, nullptr, EPI_NONE,
                         nullptr, 0, 1, 0, 1, 0, 0, 0, nullptr));
     RUN(t4r_gemm_launch(wg(), 1, 0, D, D, T, 1.f, dao, D, w.av, D, grads[P_O], D, nullptr, EPI_NONE,
-                        nullptr, 0, -1, 1, 1, 0, 0, 0, nullptr));
+                        nullptr, 0, -1, 1, 1, 0, 0, 0, nullptr, wgrad));
     if (ss) (void)hipEventRecord(ss->done_o, ss->s);
     // attention core
-    RUN(t4r_xlnet_attn_bwd(stream, w.qkv, w.qkv + TD, w.qkv + 2 * TD, w.kr, params[P_RWB],
-                           params[P_RRB], w.av, w.lse, dav, dqkv, dqkv + TD, dqkv + 2 * TD, dkr,
-                           grads[P_RWB], grads[P_RRB], attn_ws, B, L, n_head, dh, drop, drop_p, seed,
-                           C(SITE_PROB), key_len));
+    RUN(t4r_xlnet_attn_bwd_impl(stream, w.qkv, w.qkv + TD, w.qkv + 2 * TD, w.kr, params[P_RWB],
+                                params[P_RRB], w.av, w.lse, nullptr, dav, dqkv, dqkv + TD, dqkv + 2 * TD, dkr,
+                                grads[P_RWB], grads[P_RRB], attn_ws, B, L, n_head, dh, drop, drop_p, seed,
+                                C(SITE_PROB), key_len, red));
     // k_r = pos_emb(_b) @ r  ->  d r += pos_emb(_b)^T @ d k_r
     if (drop) {
         RUN(t4r_gemm_launch(wg(), 1, 0, D, D, B * 2 * L, 1.f, pos_emb_b ? pos_emb_b : w.pe_b, D, dkr, D, grads[P_R], D, nullptr,
-                            EPI_NONE, nullptr, 0, -1, 1, 1, 0, 0, 0, nullptr));
+                            EPI_NONE, nullptr, 0, -1, 1, 1, 0, 0, 0, nullptr, wgrad));
     } else {
         RUN(t4r_gemm_launch(wg(), 1, 0, D, D, 2 * L, 1.f, pos_emb, D, dkr, D, grads[P_R], D, nullptr,
                             EPI_NONE, nullptr, 0, 1, 1, 1, 0, 0, 0, nullptr));
@@ -603,18 +600,18 @@ static int layer_bwd_impl(void* stream, const float* h, const float* pos_emb,
         hipStream_t sw = wg();
         if (gz[1] == gz[0] + DD && gz[2] == gz[0] + 2 * DD) {
             RUN(t4r_gemm_launch(sw, 1, 0, D, D, T, 1.f, h, D, dqkv, D, gz[0], D, nullptr, EPI_NONE, nullptr,
-                                0, -1, 1, 3, 0, TD, DD, nullptr));
+                                0, -1, 1, 3, 0, TD, DD, nullptr, wgrad));
         } else {
             for (int z = 0; z < 3; ++z)
                 RUN(t4r_gemm_launch(sw, 1, 0, D, D, T, 1.f, h, D, dqkv + z * TD, D, gz[z], D, nullptr,
-                                    EPI_NONE, nullptr, 0, -1, 1, 1, 0, 0, 0, nullptr));
+                                    EPI_NONE, nullptr, 0, -1, 1, 1, 0, 0, 0, nullptr, wgrad));
         }
     }
     if (ss && !drop) (void)hipStreamWaitEvent(st, ss->done_o, 0);     // p = 0: the O wgrad reads dh_in, accumulated into next
     for (int z = 0; z < 3; ++z)
         RUN(t4r_gemm_launch(st, 0, 1, T, D, D, 1.f, dqkv + z * TD, D, wz[z], D, dh_in, D, nullptr,
                             EPI_NONE, nullptr, 0, 1, 1, 1, 0, 0, 0, nullptr));
-    RUN(t4r_splitk_sink_flush(wg()));      // after every producer of a partial on the caller's stream
+    RUN(t4r_splitk_sink_flush(sink, wg()));      // after every producer of a partial on the caller's stream
     if (ss) {   // join: the caller's stream continues after every weight gradient of this layer
         (void)hipEventRecord(ss->done_all, ss->s);
         (void)hipStreamWaitEvent(st, ss->done_all, 0);

@@ -117,27 +117,31 @@ def gemm(a, b, trans_a=False, trans_b=False, alpha=1.0, bias=None, epilogue=EPI_
 
 def gemm_wgrad(a, b, out):
     """out[M, N] += a[K, M]^T @ b[K, N] over a long K (a weight gradient: K = tokens) with DETERMINISTIC split-K: the partial
-    tiles go to a scratch buffer and one more launch adds them in split order (csrc/gemm_f32.hip: the split-K sink) instead
-    of fp32 atomics in arrival order.  Needs a dense `out`; otherwise (or if the partials do not fit) plain gemm(splitk=-1)."""
+    tiles go to a scratch buffer and one more launch adds them in split order (include/t4r_hip.h: t4r_gemm_wgrad_f32, one
+    call that keeps nothing armed) instead of fp32 atomics in arrival order.  Needs a dense `out`; otherwise plain
+    gemm(splitk=-1).  The scratch is sized by the launcher's own query; if the product still finds no room there, it uses
+    atomics and this function warns."""
     M, N, K = a.shape[1], b.shape[1], a.shape[0]
     if not (out.is_contiguous() and (M * N) % 4 == 0 and out.data_ptr() % 16 == 0):
         return gemm(a, b, True, False, splitk=-1, accumulate=True, out=out)
-    lib = _lib.load()
-    splits = max(1, min(256, K // 320 + 1))      # the launcher's rule: >= 20 k-tiles of 16 per split, <= 256 splits
-    ws = torch.empty(M * N * splits, device=a.device, dtype=torch.float32)
-    lib.t4r_gemm_splitk_sink_begin(ws.data_ptr(), ws.numel())
-    try:
-        gemm(a, b, True, False, splitk=-1, accumulate=True, out=out)
-        call("t4r_gemm_splitk_sink_flush", _stream())
-        bypassed = lib.t4r_gemm_splitk_sink_bypassed()
-    finally:
-        lib.t4r_gemm_splitk_sink_end()
-    if bypassed:       # the sizing above is a copy of the launcher's rule: if they ever part, say so instead of silently losing
-        import warnings   # the bit-reproducibility this function exists for (the sum itself is still correct)
+    if not (a.is_cuda and b.is_cuda and out.is_cuda):
+        raise _lib.T4RHipError("gemm_wgrad: a, b and out must be HIP device tensors; there is no CPU path")
+    if b.shape[0] != K or a.stride(1) != 1 or b.stride(1) != 1:
+        raise ValueError(f"gemm_wgrad: operands must be row-major [K, M] and [K, N] with unit inner stride (K {K} vs {b.shape[0]})")
+    ws = torch.empty(_gemm_wgrad_ws_floats(M, N, K), device=a.device, dtype=torch.float32)
+    bypassed = ctypes.c_int(0)
+    call("t4r_gemm_wgrad_f32", _stream(), M, N, K, a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), out.data_ptr(),
+         ws.data_ptr(), ws.numel(), ctypes.addressof(bypassed))
+    if bypassed.value:  # say so instead of silently losing the bit-reproducibility this function exists for (the sum is still correct)
+        import warnings
 
-        warnings.warn(f"gemm_wgrad: {bypassed} split-K launch(es) found no room in the deterministic sink ({splits} splits "
-                      f"planned for M={M} N={N} K={K}) and used fp32 atomics: this gradient is not bit-reproducible", RuntimeWarning)
+        warnings.warn(f"gemm_wgrad: the product found no room in its {ws.numel()}-float split-K workspace (M={M} N={N} K={K}) "
+                      "and used fp32 atomics: this gradient is not bit-reproducible", RuntimeWarning)
     return out
+
+
+def _gemm_wgrad_ws_floats(M, N, K):
+    return _lib.load().t4r_gemm_wgrad_ws_floats(M, N, K)
 
 
 def gemm_softmax_grad(logits, lse, labels, grad_out, V, b, trans_a, alpha=1.0, label_smoothing=0.0,
