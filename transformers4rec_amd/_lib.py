@@ -20,6 +20,7 @@ ROWS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_rows
 ROWADAM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_rowadam.h")
 CONTPROJ_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_contproj.h")
 ROWCLIP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_rowclip.h")
+SEQTASK_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_seqtask.h")
 
 _P, _I, _L, _F, _Q = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_ulonglong
 _C = {"p": _P, "i": _I, "l": _L, "f": _F, "Q": _Q}
@@ -241,6 +242,16 @@ _SIGS_ROWCLIP = {
     "t4r_row_adam_apply": ("i", "pppp" + "li" + "li" + "fffff" + "if" + "p" + "pl"),
 }
 
+# the eleventh header, include/t4r_hip_seqtask.h (tests/test_session_task_cpu.py checks this table against it): the session-level
+# prediction tasks.  fwd: stream, x, len, B, L, D, summary, w, b, act, loss_kind, target, s, pred, loss, ws; bwd: stream, g, pred,
+# target, s, len, B, L, D, summary, w, act, loss_kind, dx, d_w, d_b, ws
+_SIGS_SEQTASK = {
+    "t4r_seq_task_supported": ("i", "ii"),
+    "t4r_seq_task_ws_floats": ("l", "li"),
+    "t4r_seq_task_fwd": ("i", "p" + "pp" + "lii" + "i" + "pp" + "ii" + "p" + "pppp"),
+    "t4r_seq_task_bwd": ("i", "p" + "ppppp" + "lii" + "i" + "p" + "ii" + "pppp"),
+}
+
 _lib = None
 
 
@@ -304,6 +315,11 @@ def rowclip_header_symbols():
     return _declared(ROWCLIP_HEADER_PATH)
 
 
+def seqtask_header_symbols():
+    """Function names declared in include/t4r_hip_seqtask.h."""
+    return _declared(SEQTASK_HEADER_PATH)
+
+
 def load():
     """Loads the library and sets ctypes prototypes.  Raises if it is not built."""
     global _lib
@@ -316,7 +332,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (ret, args) in (list(_SIGS.items()) + list(_SIGS_SAMPLING.items()) + list(_SIGS_FILTER.items()) + list(_SIGS_OPTIM.items())
                               + list(_SIGS_PRETRAINED.items()) + list(_SIGS_ATTN.items()) + list(_SIGS_ROWS.items()) + list(_SIGS_ROWADAM.items())
-                              + list(_SIGS_CONTPROJ.items()) + list(_SIGS_ROWCLIP.items())):
+                              + list(_SIGS_CONTPROJ.items()) + list(_SIGS_ROWCLIP.items()) + list(_SIGS_SEQTASK.items())):
         fn = getattr(lib, name)
         fn.restype = ctypes.c_char_p if ret == "s" else (None if ret == "v" else _C[ret])
         fn.argtypes = [_C[a] for a in args]

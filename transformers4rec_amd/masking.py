@@ -84,11 +84,13 @@ def hip_parameters(model):
     and the drop-in subclasses of the reference's"""
     from .features import TabularSequenceFeatures
     from .prediction_task import NextItemPredictionTask
+    from .session_task import BinaryClassificationTask, RegressionTask
     from .transformer import TransformerBlock
 
+    hot = (TabularSequenceFeatures, TransformerBlock, NextItemPredictionTask, BinaryClassificationTask, RegressionTask)
     seen, out = set(), []
     for m in model.modules():
-        if isinstance(m, (TabularSequenceFeatures, TransformerBlock, NextItemPredictionTask)) or getattr(m, "_t4r_hip", False):
+        if isinstance(m, hot) or getattr(m, "_t4r_hip", False):
             for p in m.parameters():
                 if p.requires_grad and id(p) not in seen:
                     seen.add(id(p))

@@ -1,8 +1,10 @@
 """Thin caller of the hot path: the reference's Model -> Head -> SequentialBlock composition
-(transformers4rec/torch/model/base.py:371-425, 544-598; block/base.py:236-262) reduced to the
-single-head next-item case, with the reference's module tree names so state_dicts interchange:
+(transformers4rec/torch/model/base.py:235-425, 544-598; block/base.py:236-262) reduced to one head
+-- with one or several prediction tasks, task_weights and loss_reduction --, with the reference's module tree names so
+state_dicts interchange:
   heads.0.body.0 (TabularSequenceFeatures), heads.0.body.1 (TransformerBlock),
-  heads.0.prediction_task_dict.next-item (NextItemPredictionTask).
+  heads.0.prediction_task_dict.next-item (NextItemPredictionTask),
+  heads.0.prediction_task_dict.<target>/binary_classification_task, .<target>/regression_task (session_task.py).
 Rewriting Model/Head/Trainer is out of scope; this exists so the path can
 be driven stand-alone (tests, bench) where the reference package is not installed.
 """
@@ -50,7 +52,8 @@ def last_rows_gate(model, training, B, L, n_labels=None):
         from .prediction_task import NextItemPredictionTask
 
         block, task, body = model.transformer_block, model.prediction_task, model.heads[0].body
-        kinds = (type(block) is tfm.TransformerBlock and type(block.transformer) is tfm.XLNetModel
+        # a session-level task reads every row of the body's output: the one task of the head must be the next-item task
+        kinds = (len(model.heads[0].prediction_task_dict) == 1 and type(block) is tfm.TransformerBlock and type(block.transformer) is tfm.XLNetModel
                  and type(task) is NextItemPredictionTask and task.masking is not None and task.masking is body[0].masking
                  and type(task.masking) in (MaskedLanguageModeling, CausalLanguageModeling))
         parts = model.__dict__["_last_rows_parts"] = (block, block.transformer, task, body, kinds, {})
@@ -73,20 +76,43 @@ def last_rows_gate(model, training, B, L, n_labels=None):
 
 
 class Head(nn.Module):
-    def __init__(self, body: _Body, task):
+    """one body, one or several prediction tasks (reference Head, model/base.py:235-425): `prediction_task_dict` keyed by
+    task_name in list order, `task_weights` zipped with the tasks (default 1.0), the step's loss
+    getattr(torch.stack([loss_i * w_i]), loss_reduction)()"""
+
+    def __init__(self, body: _Body, tasks, task_weights=None, loss_reduction: str = "mean"):
         super().__init__()
         self.body = body
-        self.prediction_task_dict = nn.ModuleDict({task.task_name: task})
+        self.loss_reduction = loss_reduction
+        tasks = list(tasks) if isinstance(tasks, (list, tuple)) else [tasks]
+        if not tasks:
+            raise ValueError("Head needs at least one prediction task")
+        self.prediction_task_dict = nn.ModuleDict()
+        for task in tasks:
+            if task.task_name in self.prediction_task_dict:
+                raise ValueError(f"two prediction tasks are named '{task.task_name}': give them a target_name or a task_name")
+            self.prediction_task_dict[task.task_name] = task
+        self._task_weights = {}
+        if task_weights:
+            for task, val in zip(tasks, task_weights):
+                self._task_weights[task.task_name] = val
+
+    def task_weight(self, name):
+        return self._task_weights.get(name, 1.0)
 
 
 class Model(nn.Module):
     def __init__(self, input_features, transformer_block, prediction_task, max_sequence_length: Optional[int] = None,
-                 top_k: Optional[int] = None, exclude_seen: bool = False):
+                 top_k: Optional[int] = None, exclude_seen: bool = False, task_weights=None, loss_reduction: str = "mean"):
+        """prediction_task: one task or a list of them (NextItemPredictionTask, BinaryClassificationTask, RegressionTask), all
+        over the one body"""
         super().__init__()
         body = _Body([input_features, transformer_block])
         hidden = transformer_block.transformer.config.hidden_size
-        prediction_task.build(body=body, input_size=(-1, -1, hidden), inputs=input_features)
-        self.heads = nn.ModuleList([Head(body, prediction_task)])
+        tasks = list(prediction_task) if isinstance(prediction_task, (list, tuple)) else [prediction_task]
+        for task in tasks:
+            task.build(body=body, input_size=(-1, -1, hidden), inputs=input_features)
+        self.heads = nn.ModuleList([Head(body, tasks, task_weights=task_weights, loss_reduction=loss_reduction)])
         self.max_sequence_length = max_sequence_length or getattr(input_features, "max_sequence_length", None)
         self.top_k = top_k
         self.exclude_seen = exclude_seen      # inference: drop the session's own items (NextItemPredictionTask.forward)
@@ -131,17 +157,75 @@ class Model(nn.Module):
             n = last_rows_gate(self, training, B, L)
             return None if n is None else (self.prediction_task.masking.compact_labels()[1], n)
 
+        if not self._single_next_item():
+            return self._forward_tasks(head, inputs, targets, training, testing)
         h = head.body(inputs, training=training, testing=testing, out_rows=out_rows if training else None)
         task = self.prediction_task
         if training or testing:
             return task(h, targets=targets, training=training, testing=testing)
         return task(h, training=False, testing=False, top_k=self.top_k, exclude_seen=self.exclude_seen)
 
+    def _single_next_item(self):
+        """the head holds exactly one task and it is a next-item task: the path this model took before heads had several"""
+        single = self.__dict__.get("_single_next_item_cached")      # asked on every forward: looked up once
+        if single is None:
+            from .prediction_task import NextItemPredictionTask
+
+            tasks = self.heads[0].prediction_task_dict
+            single = self.__dict__["_single_next_item_cached"] = (len(tasks) == 1
+                                                                  and isinstance(self.prediction_task, NextItemPredictionTask))
+        return single
+
+    def _forward_tasks(self, head, inputs, targets, training, testing):
+        """reference Head.forward + Model.forward (model/base.py:371-425, 544-598) over the head's tasks: the body runs once,
+        every row of its output is computed (a session-level task reads them all)"""
+        from .prediction_task import NextItemPredictionTask
+
+        if isinstance(targets, dict) and len(targets) == 0:
+            targets = None
+        h = head.body(inputs, training=training, testing=testing)
+        if training or testing:
+            losses, labels, predictions = [], {}, {}
+            for name, task in head.prediction_task_dict.items():
+                if isinstance(task, NextItemPredictionTask):
+                    out = task(h, targets=None, training=training, testing=testing)     # its labels come from the masking
+                else:
+                    label = targets.get(task.target_name, None) if isinstance(targets, dict) else targets
+                    out = task(h, targets=None if label is None else label.float(), training=training, testing=testing)
+                labels[name], predictions[name] = out["labels"], out["predictions"]
+                losses.append(out["loss"].reshape(()) * head.task_weight(name))
+            loss = getattr(torch.stack(losses), head.loss_reduction)()
+            if len(labels) == 1:
+                labels, predictions = next(iter(labels.values())), next(iter(predictions.values()))
+            return {"loss": loss, "labels": labels, "predictions": predictions}
+        outputs = {}
+        for name, task in head.prediction_task_dict.items():
+            if isinstance(task, NextItemPredictionTask):
+                outputs[name] = task(h, training=False, testing=False, top_k=self.top_k, exclude_seen=self.exclude_seen)
+            else:
+                outputs[name] = task(h, training=False, testing=False)
+        return next(iter(outputs.values())) if len(outputs) == 1 else outputs
+
+    @property
+    def prediction_tasks(self):
+        return list(self.heads[0].prediction_task_dict.values())
+
     def calculate_metrics(self, predictions, targets):
-        return self.prediction_task.calculate_metrics(predictions, targets)
+        if len(self.heads[0].prediction_task_dict) == 1:
+            return self.prediction_task.calculate_metrics(predictions, targets)
+        out = {}
+        for name, task in self.heads[0].prediction_task_dict.items():
+            out.update(task.calculate_metrics(predictions[name], targets[name]))
+        return out
 
     def compute_metrics(self, mode=None):
-        return self.prediction_task.compute_metrics(mode)
+        if len(self.heads[0].prediction_task_dict) == 1:
+            return self.prediction_task.compute_metrics(mode)
+        out = {}
+        for task in self.prediction_tasks:
+            out.update(task.compute_metrics(mode))
+        return out
 
     def reset_metrics(self):
-        self.prediction_task.reset_metrics()
+        for task in self.prediction_tasks:
+            task.reset_metrics()

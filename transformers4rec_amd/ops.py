@@ -1799,3 +1799,87 @@ def cont_proj_bwd_(dout2d, col, xs, per_session, weight, bias, d_w, d_b, want_dp
          weight.data_ptr(), bias.data_ptr(), _chk(d_w, torch.float32, "d_w"), _chk(d_b, torch.float32, "d_b"), _p(dpre),
          ws.data_ptr())
     return dpre
+
+
+# ------------------------------------------------------------------------------------------------ session-level tasks
+# (include/t4r_hip_seqtask.h, csrc/seq_task.hip): summary over the sequence + Linear(D, 1) + sigmoid / identity + BCE / MSE
+SUMMARY = {"first": 0, "last": 1, "mean": 2}
+ACT_NONE, ACT_SIGMOID = 0, 1
+LOSS_MSE, LOSS_BCE = 0, 1
+
+
+def seq_task_supported(L, D):
+    return bool(_lib.load().t4r_seq_task_supported(int(L), int(D)))
+
+
+def _seq_task_args(what, x, lengths, weight, bias, target, summary, act, loss_kind):
+    if not x.is_cuda:
+        raise _lib.T4RHipError(f"{what}: x must live on the GPU (got {x.device}); there is no CPU path")
+    if x.dim() != 3:
+        raise ValueError(f"{what}: x must be [B, L, D], got {tuple(x.shape)}")
+    B, L, D = x.shape
+    if B and not seq_task_supported(L, D):
+        raise ValueError(f"{what}: 1 <= L <= 1023 and 1 <= D <= 1024 (got L = {L}, D = {D})")
+    if weight.numel() != D:
+        raise ValueError(f"{what}: weight must hold D = {D} values, got {tuple(weight.shape)}")
+    if bias is not None and bias.numel() != 1:
+        raise ValueError(f"{what}: bias must hold one value, got {tuple(bias.shape)}")
+    if lengths is not None and tuple(lengths.shape) != (B,):
+        raise ValueError(f"{what}: lengths must be int32 [{B}], got {tuple(lengths.shape)}")
+    if target is not None and tuple(target.shape) != (B,):
+        raise ValueError(f"{what}: target must be [{B}], got {tuple(target.shape)}")
+    if summary not in (0, 1, 2) or act not in (0, 1) or loss_kind not in (0, 1) or (loss_kind == LOSS_BCE and act == ACT_NONE):
+        raise ValueError(f"{what}: summary in 0..2, act in 0..1, loss_kind in 0..1, BCE over act 1 only "
+                         f"(got {summary}, {act}, {loss_kind})")
+    return B, L, D
+
+
+def _seq_task_ws(B, D, device):
+    return torch.empty(max(1, _lib.load().t4r_seq_task_ws_floats(B, D)), device=device, dtype=torch.float32)
+
+
+def seq_task_fwd(x, lengths, weight, bias, target, summary, act, loss_kind):
+    """x [B, L, D] -> (s [B, D], pred [B], loss [1]): the summary of every session (summary 0 first, 1 last, 2 mean; lengths
+    int32 [B] or None = all L positions), pred = act(bias + weight . s) (act 1 sigmoid, 0 identity) and, with a target [B], the
+    mean row loss (loss_kind 0 MSE, 1 BCE).  target None: inference, loss is an empty tensor.  Two launches (one)."""
+    B, L, D = _seq_task_args("seq_task_fwd", x, lengths, weight, bias, target, summary, act, loss_kind)
+    s = torch.empty((B, D), device=x.device, dtype=torch.float32)
+    pred = torch.empty((B,), device=x.device, dtype=torch.float32)
+    loss = torch.empty((1 if target is not None else 0,), device=x.device, dtype=torch.float32)
+    if target is not None and B == 0:
+        loss.fill_(float("nan"))                # the mean of no rows, as torch's losses
+    ws = _seq_task_ws(B, D, x.device) if target is not None else None
+    call("t4r_seq_task_fwd", _stream(), _chk(x, torch.float32, "x"), _p(lengths, torch.int32, "lengths"), B, L, D, int(summary),
+         _chk(weight, torch.float32, "weight"), _p(bias, torch.float32, "bias"), int(act), int(loss_kind),
+         _p(target, torch.float32, "target"), s.data_ptr(), pred.data_ptr(), loss.data_ptr() if target is not None else None,
+         _p(ws))
+    return s, pred, loss
+
+
+def seq_task_bwd_(g, pred, target, s, lengths, L, weight, summary, act, loss_kind, d_w=None, d_b=None):
+    """the backward of seq_task_fwd from its notes (s, pred): -> dx [B, L, D], every element written; the parameter gradients are
+    ACCUMULATED into d_w (weight's shape) and d_b ([1]), either may be None.  g: device tensor of one value, the gradient of
+    the loss.  Bit-reproducible (no float atomics).  Two launches (one without d_w and d_b)."""
+    if not s.is_cuda:
+        raise _lib.T4RHipError(f"seq_task_bwd_: s must live on the GPU (got {s.device}); there is no CPU path")
+    if s.dim() != 2:
+        raise ValueError(f"seq_task_bwd_: s must be [B, D], got {tuple(s.shape)}")
+    B, D = s.shape
+    if B and not seq_task_supported(L, D):
+        raise ValueError(f"seq_task_bwd_: 1 <= L <= 1023 and 1 <= D <= 1024 (got L = {L}, D = {D})")
+    if weight.numel() != D or tuple(pred.shape) != (B,) or tuple(target.shape) != (B,) or g.numel() != 1:
+        raise ValueError("seq_task_bwd_: weight must hold D values, pred and target must be [B], g one value")
+    if lengths is not None and tuple(lengths.shape) != (B,):
+        raise ValueError(f"seq_task_bwd_: lengths must be int32 [{B}], got {tuple(lengths.shape)}")
+    if (d_w is not None and d_w.numel() != D) or (d_b is not None and d_b.numel() != 1):
+        raise ValueError("seq_task_bwd_: d_w must hold D values and d_b one")
+    if summary not in (0, 1, 2) or act not in (0, 1) or loss_kind not in (0, 1) or (loss_kind == LOSS_BCE and act == ACT_NONE):
+        raise ValueError(f"seq_task_bwd_: summary in 0..2, act in 0..1, loss_kind in 0..1, BCE over act 1 only "
+                         f"(got {summary}, {act}, {loss_kind})")
+    dx = torch.empty((B, int(L), D), device=s.device, dtype=torch.float32)
+    ws = _seq_task_ws(B, D, s.device)
+    call("t4r_seq_task_bwd", _stream(), _chk(g, torch.float32, "g"), _chk(pred, torch.float32, "pred"),
+         _chk(target, torch.float32, "target"), _chk(s, torch.float32, "s"), _p(lengths, torch.int32, "lengths"), B, int(L), D,
+         int(summary), _chk(weight, torch.float32, "weight"), int(act), int(loss_kind), dx.data_ptr(),
+         _p(d_w, torch.float32, "d_w"), _p(d_b, torch.float32, "d_b"), ws.data_ptr())
+    return dx

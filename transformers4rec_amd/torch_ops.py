@@ -792,10 +792,46 @@ def _am_backward(ctx, dy):
 apply_mask.register_autograd(_am_backward, setup_context=_am_setup)
 
 
+# ------------------------------------------------------------------------------------------------ session-level tasks
+@torch.library.custom_op(f"{NS}::seq_task_fwd", mutates_args=())
+def seq_task_fwd(x: torch.Tensor, lengths: Optional[torch.Tensor], weight: torch.Tensor, bias: Optional[torch.Tensor],
+                 target: Optional[torch.Tensor], summary: int, act: int, loss_kind: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """-> (s [B, D], pred [B], loss [1] or [0] without a target): sequence summary (0 first, 1 last, 2 mean; lengths int32 [B] or
+    None) + Linear(D, 1) + sigmoid (act 1) / identity (act 0) + mean BCE (loss_kind 1) / MSE (0) of x [B, L, D]
+    (prediction_task.py:66-303; include/t4r_hip_seqtask.h, csrc/seq_task.hip)"""
+    s, pred, loss = ops.seq_task_fwd(x.contiguous(), lengths, weight.contiguous(), bias, target, summary, act, loss_kind)
+    return s, pred, loss
+
+
+@seq_task_fwd.register_fake
+def _(x, lengths, weight, bias, target, summary, act, loss_kind):
+    B, _L, D = x.shape
+    return x.new_empty((B, D)), x.new_empty((B,)), x.new_empty((1 if target is not None else 0,))
+
+
+@torch.library.custom_op(f"{NS}::seq_task_bwd", mutates_args=())
+def seq_task_bwd(g: torch.Tensor, pred: torch.Tensor, target: torch.Tensor, s: torch.Tensor, lengths: Optional[torch.Tensor],
+                 L: int, weight: torch.Tensor, has_bias: bool, summary: int, act: int,
+                 loss_kind: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """-> (d x [B, L, D], d weight (weight's shape), d bias [1] or [0] without a bias) of seq_task_fwd from its notes (s, pred)
+    and the gradient g [1] of the loss"""
+    d_w = torch.zeros_like(weight, memory_format=torch.contiguous_format)
+    d_b = torch.zeros((1 if has_bias else 0,), device=s.device, dtype=torch.float32)
+    dx = ops.seq_task_bwd_(g.contiguous().view(-1), pred, target, s, lengths, L, weight.contiguous(), summary, act, loss_kind,
+                           d_w, d_b if has_bias else None)
+    return dx, d_w, d_b
+
+
+@seq_task_bwd.register_fake
+def _(g, pred, target, s, lengths, L, weight, has_bias, summary, act, loss_kind):
+    B, D = s.shape
+    return s.new_empty((B, L, D)), weight.new_empty(weight.shape), s.new_empty((1 if has_bias else 0,))
+
+
 OPERATORS = ("gemm", "item_scores", "topk", "item_topk", "item_sample", "gumbel_argmax", "item_eval", "pack_item_table",
              "pack_item_filter", "item_mask_", "item_topk_filtered", "item_sample_filtered", "rank_of_target", "embedding_gather", "embedding_bag", "ragged_to_padded",
              "xlnet_layer_infer", "xlnet_layer_fwd", "xlnet_layer_bwd", "mlm_targets", "seq_item_embedding",
              "seq_item_embedding_bwd", "xlnet_layer_grad", "gather_label_rows", "scatter_label_rows", "linear_softmax_ce",
              "linear_softmax_ce_bwd", "dropout", "pos_emb_dropout", "next_item_head", "next_item_head_bwd",
              "soft_embedding", "soft_embedding_grad", "seq_concat", "seq_concat_grad", "linear_relu", "linear_relu_grad", "apply_mask",
-             "apply_mask_grad")
+             "apply_mask_grad", "seq_task_fwd", "seq_task_bwd")

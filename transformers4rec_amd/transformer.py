@@ -72,10 +72,14 @@ class XLNetConfig:
         """config/transformer.py:71-131: SequentialBlock(inputs, TransformerBlock) -> Head -> Model."""
         from .model import Model
 
-        if len(prediction_task) != 1:
-            raise NotImplementedError("one NextItemPredictionTask per model on the hot path")
+        if not prediction_task:
+            raise ValueError("to_torch_model needs at least one prediction task")
+        if task_blocks is not None:
+            raise NotImplementedError("to_torch_model(task_blocks=...) is not on the HIP path: pass task_blocks=None")
         block = TransformerBlock(self, masking=input_features.masking)
-        return Model(input_features, block, prediction_task[0])
+        if len(prediction_task) == 1:
+            return Model(input_features, block, prediction_task[0], task_weights=task_weights, loss_reduction=loss_reduction)
+        return Model(input_features, block, list(prediction_task), task_weights=task_weights, loss_reduction=loss_reduction)
 
 
 class _LN(nn.Module):
