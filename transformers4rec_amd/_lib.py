@@ -21,6 +21,7 @@ ROWADAM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_r
 CONTPROJ_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_contproj.h")
 ROWCLIP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_rowclip.h")
 SEQTASK_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_seqtask.h")
+RTD_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "t4r_hip_rtd.h")
 
 _P, _I, _L, _F, _Q = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_ulonglong
 _C = {"p": _P, "i": _I, "l": _L, "f": _F, "Q": _Q}
@@ -252,6 +253,16 @@ _SIGS_SEQTASK = {
     "t4r_seq_task_bwd": ("i", "p" + "ppppp" + "lii" + "i" + "p" + "ii" + "pppp"),
 }
 
+# the twelfth header, include/t4r_hip_rtd.h (tests/test_rtd_cpu.py checks this table against it): the replaced-token-detection
+# head.  fwd: stream, x, active, label, T, D, W1, b1, w2, b2, act, z, n_active, loss, ws; bwd: stream, g, x, active, label, z,
+# n_active, T, D, W1, b1, w2, act, dx, d_W1, d_b1, d_w2, d_b2, ws
+_SIGS_RTD = {
+    "t4r_rtd_head_supported": ("i", "i"),
+    "t4r_rtd_head_ws_floats": ("l", "li"),
+    "t4r_rtd_head_fwd": ("i", "p" + "ppp" + "li" + "pppp" + "i" + "pppp"),
+    "t4r_rtd_head_bwd": ("i", "p" + "pppppp" + "li" + "ppp" + "i" + "pppppp"),
+}
+
 _lib = None
 
 
@@ -320,6 +331,11 @@ def seqtask_header_symbols():
     return _declared(SEQTASK_HEADER_PATH)
 
 
+def rtd_header_symbols():
+    """Function names declared in include/t4r_hip_rtd.h."""
+    return _declared(RTD_HEADER_PATH)
+
+
 def load():
     """Loads the library and sets ctypes prototypes.  Raises if it is not built."""
     global _lib
@@ -332,7 +348,8 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (ret, args) in (list(_SIGS.items()) + list(_SIGS_SAMPLING.items()) + list(_SIGS_FILTER.items()) + list(_SIGS_OPTIM.items())
                               + list(_SIGS_PRETRAINED.items()) + list(_SIGS_ATTN.items()) + list(_SIGS_ROWS.items()) + list(_SIGS_ROWADAM.items())
-                              + list(_SIGS_CONTPROJ.items()) + list(_SIGS_ROWCLIP.items()) + list(_SIGS_SEQTASK.items())):
+                              + list(_SIGS_CONTPROJ.items()) + list(_SIGS_ROWCLIP.items()) + list(_SIGS_SEQTASK.items())
+                              + list(_SIGS_RTD.items())):
         fn = getattr(lib, name)
         fn.restype = ctypes.c_char_p if ret == "s" else (None if ret == "v" else _C[ret])
         fn.argtypes = [_C[a] for a in args]

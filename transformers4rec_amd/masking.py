@@ -5,7 +5,9 @@ Same constructor arguments, attributes (`mask_schema`, `masked_targets`, `paddin
 `masked_item_embedding`) and state_dict names; the integer work runs in
 csrc/masking.hip, the embedding replacement in csrc/embedding.hip, the replacement draw of RTD in
 csrc/item_sample.hip and the sampling heads (csrc/gumbel_noise.h).
-PLM is out of scope; so are RTD's discriminator and its loss, which the reference library does not hold either.
+RTD's discriminator head, its loss and the two-pass training model are in rtd.py (csrc/rtd_head.hip; HuggingFace ELECTRA's
+arithmetic -- the reference library stops at the replacement draw).  PLM is out of scope, and so is RTD's
+tied-generator variant.
 """
 from collections import namedtuple
 from typing import Optional
@@ -84,10 +86,12 @@ def hip_parameters(model):
     and the drop-in subclasses of the reference's"""
     from .features import TabularSequenceFeatures
     from .prediction_task import NextItemPredictionTask
+    from .rtd import ReplacedTokenDetectionHead
     from .session_task import BinaryClassificationTask, RegressionTask
     from .transformer import TransformerBlock
 
-    hot = (TabularSequenceFeatures, TransformerBlock, NextItemPredictionTask, BinaryClassificationTask, RegressionTask)
+    hot = (TabularSequenceFeatures, TransformerBlock, NextItemPredictionTask, BinaryClassificationTask, RegressionTask,
+           ReplacedTokenDetectionHead)
     seen, out = set(), []
     for m in model.modules():
         if isinstance(m, hot) or getattr(m, "_t4r_hip", False):
@@ -284,7 +288,7 @@ class MaskedLanguageModeling(MaskSequence):
 
 class ReplacementLanguageModeling(MaskedLanguageModeling):
     """reference masking.py:753-870: MLM selects the positions, the generator's scores at those positions draw replacement
-    items, a discriminator (outside the library, as in the reference) learns to tell them from the originals.
+    items, a discriminator (rtd.RTDModel / rtd.ReplacedTokenDetectionHead) learns to tell them from the originals.
 
     The draw (`sample_from_softmax`) is one Gumbel-argmax per label row on the device: from materialised logits in one pass
     (ops.gumbel_argmax), from the non-materialising head's LazyPredictions through the fused sampling head (ops.item_sample) --

@@ -1883,3 +1883,87 @@ def seq_task_bwd_(g, pred, target, s, lengths, L, weight, summary, act, loss_kin
          int(summary), _chk(weight, torch.float32, "weight"), int(act), int(loss_kind), dx.data_ptr(),
          _p(d_w, torch.float32, "d_w"), _p(d_b, torch.float32, "d_b"), ws.data_ptr())
     return dx
+
+
+# ------------------------------------------------------------------------------------------------ replaced-token detection
+# (include/t4r_hip_rtd.h, csrc/rtd_head.hip): Linear(D, D) + erf-GELU / ReLU + Linear(D, 1) + BCE-with-logits over the active tokens
+RTD_ACT = {"gelu": 0, "relu": 1}
+
+
+def rtd_head_supported(D):
+    return bool(_lib.load().t4r_rtd_head_supported(int(D)))
+
+
+def _rtd_head_args(what, x, active, labels, W1, b1, w2, act):
+    if not x.is_cuda:
+        raise _lib.T4RHipError(f"{what}: x must live on the GPU (got {x.device}); there is no CPU path")
+    if x.dim() != 2:
+        raise ValueError(f"{what}: x must be [T, D], got {tuple(x.shape)}")
+    T, D = x.shape
+    if not rtd_head_supported(D):
+        raise ValueError(f"{what}: D must be a multiple of 16 with 16 <= D <= 512 (got D = {D})")
+    if tuple(W1.shape) != (D, D) or b1.numel() != D or w2.numel() != D:
+        raise ValueError(f"{what}: W1 must be [{D}, {D}], b1 and w2 must hold D = {D} values "
+                         f"(got {tuple(W1.shape)}, {tuple(b1.shape)}, {tuple(w2.shape)})")
+    for name, m in (("active", active), ("labels", labels)):
+        if m is not None and (tuple(m.shape) != (T,) or m.dtype not in (torch.bool, torch.uint8)):
+            raise ValueError(f"{what}: {name} must be bool / uint8 [{T}], got {m.dtype} {tuple(m.shape)}")
+    if act not in (0, 1):
+        raise ValueError(f"{what}: act must be 0 (erf-GELU) or 1 (ReLU), got {act}")
+    return T, D
+
+
+def _rtd_u8(m):
+    if m is None:
+        return None
+    m = m.contiguous()
+    return m.view(torch.uint8) if m.dtype == torch.bool else m
+
+
+def _rtd_head_ws(T, D, device):
+    return torch.empty(max(1, _lib.load().t4r_rtd_head_ws_floats(T, D)), device=device, dtype=torch.float32)
+
+
+def rtd_head_fwd(x, active, labels, W1, b1, w2, b2, act):
+    """x [T, D] -> (z [T], n_active int32 [1], loss [1]): z = b2 + w2 . act(b1 + W1 x) for every token (act 0 erf-GELU, 1 ReLU)
+    and, with labels (bool / uint8 [T]), the mean of binary_cross_entropy_with_logits(z, labels) over the tokens where active
+    (bool / uint8 [T]; None = all) is set, and their count n; n = 0 gives loss 0.  labels None: inference, n_active and loss
+    are empty tensors.  Two launches (one)."""
+    T, D = _rtd_head_args("rtd_head_fwd", x, active, labels, W1, b1, w2, act)
+    if b2.numel() != 1:
+        raise ValueError(f"rtd_head_fwd: b2 must hold one value, got {tuple(b2.shape)}")
+    train = labels is not None
+    z = torch.empty((T,), device=x.device, dtype=torch.float32)
+    n_active = torch.zeros((1 if train else 0,), device=x.device, dtype=torch.int32)
+    loss = torch.zeros((1 if train else 0,), device=x.device, dtype=torch.float32)
+    ws = _rtd_head_ws(T, D, x.device) if train else None
+    act_u8, lab_u8 = _rtd_u8(active), _rtd_u8(labels)
+    call("t4r_rtd_head_fwd", _stream(), _chk(x, torch.float32, "x"), _p(act_u8, torch.uint8, "active"),
+         _p(lab_u8, torch.uint8, "labels"), T, D, _chk(W1, torch.float32, "W1"), _chk(b1, torch.float32, "b1"),
+         _chk(w2, torch.float32, "w2"), _chk(b2, torch.float32, "b2"), int(act), z.data_ptr(),
+         n_active.data_ptr() if train else None, loss.data_ptr() if train else None, _p(ws))
+    return z, n_active, loss
+
+
+def rtd_head_bwd_(g, x, active, labels, z, n_active, W1, b1, w2, act, d_W1=None, d_b1=None, d_w2=None, d_b2=None):
+    """the backward of rtd_head_fwd from what it wrote (z, n_active): -> dx [T, D], every element written; the parameter
+    gradients are ACCUMULATED into d_W1 [D, D], d_b1 [D], d_w2 (D values), d_b2 [1], each of which may be None.  g: device
+    tensor of one value, the gradient of the loss.  Bit-reproducible (no float atomics).  Three launches (two without d_W1,
+    one without any parameter gradient)."""
+    T, D = _rtd_head_args("rtd_head_bwd_", x, active, labels, W1, b1, w2, act)
+    if labels is None:
+        raise ValueError("rtd_head_bwd_: labels are needed")
+    if tuple(z.shape) != (T,) or n_active.numel() != 1 or g.numel() != 1:
+        raise ValueError(f"rtd_head_bwd_: z must be [{T}], n_active and g one value each")
+    if ((d_W1 is not None and tuple(d_W1.shape) != (D, D)) or (d_b1 is not None and d_b1.numel() != D)
+            or (d_w2 is not None and d_w2.numel() != D) or (d_b2 is not None and d_b2.numel() != 1)):
+        raise ValueError("rtd_head_bwd_: d_W1 must be [D, D], d_b1 and d_w2 must hold D values and d_b2 one")
+    dx = torch.empty((T, D), device=x.device, dtype=torch.float32)
+    ws = _rtd_head_ws(T, D, x.device)
+    act_u8, lab_u8 = _rtd_u8(active), _rtd_u8(labels)
+    call("t4r_rtd_head_bwd", _stream(), _chk(g, torch.float32, "g"), _chk(x, torch.float32, "x"),
+         _p(act_u8, torch.uint8, "active"), _chk(lab_u8, torch.uint8, "labels"), _chk(z, torch.float32, "z"),
+         _chk(n_active, torch.int32, "n_active"), T, D, _chk(W1, torch.float32, "W1"), _chk(b1, torch.float32, "b1"),
+         _chk(w2, torch.float32, "w2"), int(act), dx.data_ptr(), _p(d_W1, torch.float32, "d_W1"),
+         _p(d_b1, torch.float32, "d_b1"), _p(d_w2, torch.float32, "d_w2"), _p(d_b2, torch.float32, "d_b2"), ws.data_ptr())
+    return dx

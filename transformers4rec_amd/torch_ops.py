@@ -828,10 +828,47 @@ def _(g, pred, target, s, lengths, L, weight, has_bias, summary, act, loss_kind)
     return s.new_empty((B, L, D)), weight.new_empty(weight.shape), s.new_empty((1 if has_bias else 0,))
 
 
+# ------------------------------------------------------------------------------------------------ replaced-token detection
+@torch.library.custom_op(f"{NS}::rtd_head_fwd", mutates_args=())
+def rtd_head_fwd(x: torch.Tensor, active: Optional[torch.Tensor], labels: Optional[torch.Tensor], W1: torch.Tensor,
+                 b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, act: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """-> (z [T], n_active int32 [1], loss [1]; the last two [0] without labels): Linear(D, D) + erf-GELU (act 0) / ReLU (1) +
+    Linear(D, 1) of x [T, D] and the mean BCE-with-logits over the active tokens (HF ElectraDiscriminatorPredictions +
+    BCEWithLogitsLoss; include/t4r_hip_rtd.h, csrc/rtd_head.hip)"""
+    z, n_active, loss = ops.rtd_head_fwd(x.contiguous(), active, labels, W1.contiguous(), b1.contiguous(), w2.contiguous(), b2, act)
+    return z, n_active, loss
+
+
+@rtd_head_fwd.register_fake
+def _(x, active, labels, W1, b1, w2, b2, act):
+    T, n = x.shape[0], 1 if labels is not None else 0
+    return x.new_empty((T,)), x.new_empty((n,), dtype=torch.int32), x.new_empty((n,))
+
+
+@torch.library.custom_op(f"{NS}::rtd_head_bwd", mutates_args=())
+def rtd_head_bwd(g: torch.Tensor, x: torch.Tensor, active: Optional[torch.Tensor], labels: torch.Tensor, z: torch.Tensor,
+                 n_active: torch.Tensor, W1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor,
+                 act: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """-> (d x [T, D], d W1 [D, D], d b1 [D], d w2 (w2's shape), d b2 [1]) of rtd_head_fwd from what it wrote (z, n_active) and
+    the gradient g [1] of the loss"""
+    d_W1 = torch.zeros_like(W1, memory_format=torch.contiguous_format)
+    d_b1 = torch.zeros_like(b1, memory_format=torch.contiguous_format)
+    d_w2 = torch.zeros_like(w2, memory_format=torch.contiguous_format)
+    d_b2 = torch.zeros((1,), device=x.device, dtype=torch.float32)
+    dx = ops.rtd_head_bwd_(g.contiguous().view(-1), x.contiguous(), active, labels, z, n_active, W1.contiguous(), b1.contiguous(),
+                           w2.contiguous(), act, d_W1, d_b1, d_w2, d_b2)
+    return dx, d_W1, d_b1, d_w2, d_b2
+
+
+@rtd_head_bwd.register_fake
+def _(g, x, active, labels, z, n_active, W1, b1, w2, act):
+    return x.new_empty(x.shape), W1.new_empty(W1.shape), b1.new_empty(b1.shape), w2.new_empty(w2.shape), x.new_empty((1,))
+
+
 OPERATORS = ("gemm", "item_scores", "topk", "item_topk", "item_sample", "gumbel_argmax", "item_eval", "pack_item_table",
              "pack_item_filter", "item_mask_", "item_topk_filtered", "item_sample_filtered", "rank_of_target", "embedding_gather", "embedding_bag", "ragged_to_padded",
              "xlnet_layer_infer", "xlnet_layer_fwd", "xlnet_layer_bwd", "mlm_targets", "seq_item_embedding",
              "seq_item_embedding_bwd", "xlnet_layer_grad", "gather_label_rows", "scatter_label_rows", "linear_softmax_ce",
              "linear_softmax_ce_bwd", "dropout", "pos_emb_dropout", "next_item_head", "next_item_head_bwd",
              "soft_embedding", "soft_embedding_grad", "seq_concat", "seq_concat_grad", "linear_relu", "linear_relu_grad", "apply_mask",
-             "apply_mask_grad", "seq_task_fwd", "seq_task_bwd")
+             "apply_mask_grad", "seq_task_fwd", "seq_task_bwd", "rtd_head_fwd", "rtd_head_bwd")
