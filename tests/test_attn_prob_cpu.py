@@ -1,5 +1,5 @@
 """Host half of the attention probabilities' hand-over: the sixth C-ABI header (include/t4r_hip_attn.h) against the library and
-the ctypes table, and the layer workspace that carries the probabilities.  Nothing here needs a GPU."""
+the derived prototypes, and the layer workspace that carries the probabilities.  Nothing here needs a GPU."""
 import ctypes
 import re
 
@@ -8,25 +8,12 @@ from transformers4rec_amd import _lib
 
 def test_sixth_header_library_and_prototypes_agree():
     lib = _lib.load()
-    syms = _lib.attn_header_symbols()
-    assert sorted(syms) == sorted(_lib._SIGS_ATTN) == ["t4r_xlnet_attn_block_fwd_prob", "t4r_xlnet_attn_bwd_prob"]
+    syms = _lib.header_symbols("t4r_hip_attn.h")
+    assert syms == ["t4r_xlnet_attn_block_fwd_prob", "t4r_xlnet_attn_bwd_prob"]
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in include/t4r_hip_attn.h but not exported"
-        assert getattr(lib, s).argtypes is not None                            # bound by load()
-    others = (set(_lib.header_symbols()) | set(_lib.sampling_header_symbols()) | set(_lib.filter_header_symbols())
-              | set(_lib.optim_header_symbols()) | set(_lib.pretrained_header_symbols()))
-    assert not set(syms) & others
-    assert set(_lib.header_symbols()) == set(_lib._SIGS)                       # the first header is as it was
-    # the two entries are their t4r_hip.h counterparts plus / minus the documented pointers
-    fwd, fwd_p = _lib._SIGS["t4r_xlnet_attn_block_fwd"][1], _lib._SIGS_ATTN["t4r_xlnet_attn_block_fwd_prob"][1]
-    assert len(fwd_p) == len(fwd) + 1 and fwd_p.replace("p", "") == fwd.replace("p", "")
-    bwd, bwd_p = _lib._SIGS["t4r_xlnet_attn_bwd"][1], _lib._SIGS_ATTN["t4r_xlnet_attn_bwd_prob"][1]
-    assert len(bwd_p) == len(bwd) - 2 and bwd_p.replace("p", "") == bwd.replace("p", "")       # out, lse -> prob; no key_len
-    # argument counts of the table and of the header's declarations agree
-    text = re.sub(r"/\*.*?\*/", "", open(_lib.ATTN_HEADER_PATH).read(), flags=re.S)
-    for name, (_, args) in _lib._SIGS_ATTN.items():
-        decl = re.search(name + r"\s*\((.*?)\)\s*;", text, flags=re.S).group(1)
-        assert len(decl.split(",")) == len(args), name
+    # the two entries are their t4r_hip.h counterparts plus / minus the documented pointers: tests/test_abi_headers_cpu.py
+    text = re.sub(r"/\*.*?\*/", "", open(_lib.header_path("t4r_hip_attn.h")).read(), flags=re.S)
     for word in ("at::", "torch", "Tensor", "std::", "c10"):
         assert word not in text, f"{word} leaked into the C ABI"
 

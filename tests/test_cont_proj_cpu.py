@@ -1,4 +1,4 @@
-"""Host half of `continuous_projection`: the ninth C-ABI header (include/t4r_hip_contproj.h) against its ctypes table, the size
+"""Host half of `continuous_projection`: the ninth C-ABI header (include/t4r_hip_contproj.h) against the library, the size
 query and the argument limits (refused before any launch), the module mirror's construction, state-dict names against the
 reference classes built live (oracle/ref_standins.py), the refusals, the drop-in conversion and the documents.  Nothing here
 needs a GPU."""
@@ -22,22 +22,11 @@ FOUR = ["t4r_cont_proj_bwd", "t4r_cont_proj_bwd_ws_floats", "t4r_cont_proj_fwd",
 # ---------------------------------------------------------------------------------------------------------- header and ABI
 def test_contproj_header_library_and_prototypes_agree():
     lib = _lib.load()
-    syms = _lib.contproj_header_symbols()
-    assert sorted(syms) == sorted(_lib._SIGS_CONTPROJ) == FOUR
+    syms = _lib.header_symbols("t4r_hip_contproj.h")
+    assert syms == FOUR
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in include/t4r_hip_contproj.h but not exported"
-        assert len(getattr(lib, s).argtypes) == len(_lib._SIGS_CONTPROJ[s][1])
-    others = (set(_lib.header_symbols()) | set(_lib.sampling_header_symbols()) | set(_lib.filter_header_symbols())
-              | set(_lib.optim_header_symbols()) | set(_lib.pretrained_header_symbols()) | set(_lib.attn_header_symbols())
-              | set(_lib.rows_header_symbols()) | set(_lib.rowadam_header_symbols()))
-    assert not set(syms) & others
-    # the other eight tables are as they were
-    for table, names, n in ((_lib._SIGS, _lib.header_symbols(), 125), (_lib._SIGS_SAMPLING, _lib.sampling_header_symbols(), 6),
-                            (_lib._SIGS_FILTER, _lib.filter_header_symbols(), 7), (_lib._SIGS_OPTIM, _lib.optim_header_symbols(), 4),
-                            (_lib._SIGS_PRETRAINED, _lib.pretrained_header_symbols(), 4), (_lib._SIGS_ATTN, _lib.attn_header_symbols(), 2),
-                            (_lib._SIGS_ROWS, _lib.rows_header_symbols(), 5), (_lib._SIGS_ROWADAM, _lib.rowadam_header_symbols(), 2)):
-        assert sorted(names) == sorted(table) and len(table) == n
-    text = open(_lib.CONTPROJ_HEADER_PATH).read()
+    text = open(_lib.header_path("t4r_hip_contproj.h")).read()
     for entry in ("int t4r_cont_proj_fwd(void* stream", "int t4r_cont_proj_bwd(void* stream"):
         decl = text[: text.index(entry)]
         comment = decl[decl.rindex("/*"):]
@@ -45,12 +34,6 @@ def test_contproj_header_library_and_prototypes_agree():
     decls = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     for word in ("at::", "torch", "Tensor", "std::", "c10"):
         assert word not in decls, f"{word} leaked into the C ABI"
-    # the signatures the binding states are the header's
-    for name in ("t4r_cont_proj_fwd", "t4r_cont_proj_bwd"):
-        at = decls.index(name + "(")
-        args = decls[at + len(name) + 1: decls.index(");", at)].split(",")
-        kinds = "".join("p" if "*" in a else ("l" if "long" in a else ("f" if "float" in a else "i")) for a in args)
-        assert kinds == _lib._SIGS_CONTPROJ[name][1], name
 
 
 def test_ws_floats_is_pure_and_monotone():
@@ -306,7 +289,7 @@ def test_documents_name_the_new_surface():
     assert "t4r_hip_contproj.h" in readme and re.search(r"\b4 continuous-projection entry points", readme)
     assert "cont_proj.hip" in readme
     integ = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    for word in FOUR + ["_SIGS_CONTPROJ", "continuous_module.1.<i>.0.weight", "continuous_projection"]:
+    for word in FOUR + ["t4r_hip_contproj.h", "continuous_module.1.<i>.0.weight", "continuous_projection"]:
         assert word in integ, word
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     assert "### 4.9" in design and "cont_proj.hip" in design and "T·(4C + 4P)" in design

@@ -54,30 +54,21 @@ def test_restated_ranking_and_tail_rule():
 
 # ---------------------------------------------------------------------------------------------------------- header and ABI
 def _decls():
-    return re.sub(r"/\*.*?\*/", "", open(_lib.FILTER_HEADER_PATH).read(), flags=re.S)
+    return re.sub(r"/\*.*?\*/", "", open(_lib.header_path("t4r_hip_filter.h")).read(), flags=re.S)
 
 
 def test_third_header_library_and_prototypes_agree():
     lib = _lib.load()
-    syms = _lib.filter_header_symbols()
-    assert sorted(syms) == sorted(_lib._SIGS_FILTER) and len(syms) == 7
+    syms = _lib.header_symbols("t4r_hip_filter.h")
+    assert len(syms) == 7
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in include/t4r_hip_filter.h but not exported"
-        assert getattr(lib, s).argtypes is not None                            # bound by load()
-    assert not set(syms) & (set(_lib.header_symbols()) | set(_lib.sampling_header_symbols()))
-    assert set(_lib.header_symbols()) == set(_lib._SIGS)                       # the first header is as it was
-    assert sorted(_lib.sampling_header_symbols()) == sorted(_lib._SIGS_SAMPLING) and len(_lib._SIGS_SAMPLING) == 6
-    text = open(_lib.FILTER_HEADER_PATH).read()
+    text = open(_lib.header_path("t4r_hip_filter.h")).read()
     for name in ("t4r_item_allow_pack", "t4r_item_mask_f32", "t4r_item_topk_filtered_f32", "t4r_item_sample_filtered_f32"):
         decl = text[: text.index(name + "(void* stream")]
         comment = decl[decl.rindex("/*"):]
         assert "replaces:" in comment and "prediction_task.py:452-470" in comment and "= -inf" in comment, name
-    # the filter tail of every entry that takes one
-    for name in syms:
-        if name not in ("t4r_item_allow_words", "t4r_item_allow_pack"):
-            assert _lib._SIGS_FILTER[name][1].endswith("ppil"), name
-    assert _lib._SIGS_FILTER["t4r_item_topk_filtered_f32"][1] == _lib._SIGS["t4r_item_topk_f32"][1] + "ppil"
-    assert _lib._SIGS_FILTER["t4r_item_sample_filtered_h16"][1] == _lib._SIGS_SAMPLING["t4r_item_sample_h16"][1] + "ppil"
+    # the filter tail of every entry that takes one: tests/test_abi_headers_cpu.py
 
 
 def test_no_torch_types_in_the_third_header():
@@ -144,7 +135,7 @@ def test_every_launching_entry_of_the_third_header_has_a_redzone_case():
     import test_item_filter_gpu as fg
 
     exempt = {"t4r_item_allow_words": "size query: nothing launches"}
-    names = _lib.filter_header_symbols()
+    names = _lib.header_symbols("t4r_hip_filter.h")
     cased = {e for c in fg.REDZONE_CASES for e in c.entries}
     assert set(exempt) <= set(names)
     missing = [n for n in names if n not in cased and n not in exempt]

@@ -16,7 +16,7 @@ def test_library_exports_and_header_declares_the_entry_points():
     lib = _lib.load()
     syms = _lib.header_symbols()
     for name in ("t4r_item_topk_f32", "t4r_item_topk_ws_bytes"):
-        assert name in syms and hasattr(lib, name) and name in _lib._SIGS
+        assert name in syms and hasattr(lib, name) and name in _lib.signatures()
     with open(_lib.HEADER_PATH) as f:
         text = f.read()
     decl = text[: text.index("t4r_item_topk_ws_bytes(int")]

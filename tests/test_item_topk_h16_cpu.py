@@ -18,7 +18,7 @@ def test_library_exports_and_header_declares_the_entry_points():
     lib = _lib.load()
     syms = _lib.header_symbols()
     for name in ENTRIES + ("t4r_item_topk_h16_supported",):
-        assert name in syms and hasattr(lib, name) and name in _lib._SIGS, name
+        assert name in syms and hasattr(lib, name) and name in _lib.signatures(), name
     with open(_lib.HEADER_PATH) as f:
         text = f.read()
     decl = text[: text.index("t4r_item_table_image_ld(int")]

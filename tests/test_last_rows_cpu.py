@@ -1,4 +1,4 @@
-"""CPU checks of the row-mapped last layer: the seventh header against the ctypes table and the library, and the Python gate
+"""CPU checks of the row-mapped last layer: the seventh header against the library and the derived prototypes, and the Python gate
 (model.last_rows_gate) that decides whether a training step may run the last XLNet layer on the label rows only."""
 import torch
 
@@ -8,17 +8,13 @@ from transformers4rec_amd import _lib, model as model_mod, transformer as tfm
 
 def test_rows_header_is_exported_and_bound():
     lib = _lib.load()
-    syms = _lib.rows_header_symbols()
-    assert sorted(syms) == sorted(_lib._SIGS_ROWS) == ["t4r_xlnet_ff_bwd_rows", "t4r_xlnet_ff_fwd_rows", "t4r_xlnet_layer_bwd_rows",
-                                                       "t4r_xlnet_layer_fwd_rows", "t4r_xlnet_ln1_bwd_rows"]
+    syms = _lib.header_symbols("t4r_hip_rows.h")
+    assert syms == ["t4r_xlnet_ff_bwd_rows", "t4r_xlnet_ff_fwd_rows", "t4r_xlnet_layer_bwd_rows", "t4r_xlnet_layer_fwd_rows",
+                    "t4r_xlnet_ln1_bwd_rows"]
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in include/t4r_hip_rows.h but not exported"
-    assert set(_lib.header_symbols()) == set(_lib._SIGS)                       # the first header is as it was
-    # every mapped entry = its plain entry + the map (rows, n) at the end (+ the compact h1 rows of the feed-forward backward)
-    for plain, tail in (("t4r_xlnet_ff_fwd", "pi"), ("t4r_xlnet_ff_bwd", "pip"), ("t4r_xlnet_layer_fwd", "pi"),
-                        ("t4r_xlnet_layer_bwd", "pi")):
-        assert _lib._SIGS_ROWS[plain + "_rows"][1] == _lib._SIGS[plain][1] + tail
-    hdr = open(_lib.ROWS_HEADER_PATH).read()
+    # every mapped entry = its plain entry + the map (rows, n) at the end: tests/test_abi_headers_cpu.py
+    hdr = open(_lib.header_path("t4r_hip_rows.h")).read()
     for word in ("at::", "torch", "Tensor", "std::", "c10"):
         assert word not in hdr
 

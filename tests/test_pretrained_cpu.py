@@ -1,4 +1,4 @@
-"""CPU checks of the pretrained-embedding feature: the fifth header against its ctypes table, the pure size queries, the argument
+"""CPU checks of the pretrained-embedding feature: the fifth header against the library, the pure size queries, the argument
 limits (refused before any launch: these run without a GPU), the module mirror's construction and refusals, and its state-dict
 names against the reference classes built live (oracle/ref_standins.py)."""
 import ctypes
@@ -16,13 +16,11 @@ ROOT = os.path.dirname(HERE)
 
 def test_header_symbols_match_the_ctypes_table_and_are_exported():
     lib = _lib.load()
-    syms = _lib.pretrained_header_symbols()
-    assert set(syms) == set(_lib._SIGS_PRETRAINED) and len(syms) == 4
+    syms = _lib.header_symbols("t4r_hip_pretrained.h")
+    assert len(syms) == 4
     for s in syms:
         assert hasattr(lib, s), s
     assert not set(syms) & set(_lib.header_symbols()), "the pretrained entries stay out of t4r_hip.h"
-    for s, (_ret, args) in _lib._SIGS_PRETRAINED.items():
-        assert len(getattr(lib, s).argtypes) == len(args)
 
 
 def test_workspace_queries_are_pure_and_monotone():

