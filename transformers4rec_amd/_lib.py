@@ -1,5 +1,7 @@
 """ctypes binding of libt4r_hip.so.  The C ABI is declared in the headers under include/ (HEADERS); the ctypes prototypes are
 derived from those declarations (signatures()), so a new header is registered by adding its file name to HEADERS.
+EXTENSION_HEADERS are headers of the same library that are bound after the main ones (extension_signatures()): their names
+are not part of signatures() / header_symbols() / HEADERS, and may not repeat one of those.
 
 There is NO fallback: if the shared library is missing or a call fails the product path
 raises.  Build with `python -m transformers4rec_amd.build` (or __graft_entry__.build()).
@@ -14,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("T4R_HIP_LIB") or os.path.join(_HERE, "lib", "libt4r_hip.so")
 HEADERS = ("t4r_hip.h", "t4r_hip_sampling.h", "t4r_hip_filter.h", "t4r_hip_optim.h", "t4r_hip_pretrained.h", "t4r_hip_attn.h",
            "t4r_hip_rows.h", "t4r_hip_rowadam.h", "t4r_hip_contproj.h", "t4r_hip_rowclip.h", "t4r_hip_seqtask.h", "t4r_hip_rtd.h")
+EXTENSION_HEADERS = ("t4r_hip_uni.h",)
 
 
 def header_path(name):
@@ -94,6 +97,22 @@ def signatures():
     return sigs
 
 
+@functools.lru_cache(maxsize=None)
+def extension_signatures():
+    """name -> (restype code, argtype codes) of the entries declared in EXTENSION_HEADERS (same parser); a name that
+    signatures() or another extension header already has is an error."""
+    main = signatures()
+    sigs, where = {}, {}
+    for header in EXTENSION_HEADERS:
+        for name, sig in _header_signatures(header).items():
+            if name in main:
+                raise T4RHipError(f"`{name}` of the extension header {header} is already declared in the main headers")
+            if name in sigs:
+                raise T4RHipError(f"`{name}` is declared in both {where[name]} and {header}")
+            sigs[name], where[name] = sig, header
+    return sigs
+
+
 def header_symbols(header=HEADERS[0]):
     """Sorted function names declared in include/<header>."""
     return sorted(_header_signatures(header))
@@ -108,7 +127,8 @@ def load():
         raise T4RHipError(
             f"{LIB_PATH} not found: the HIP extension is not built "
             "(run `python -m transformers4rec_amd.build`). There is no CPU fallback.")
-    sigs = signatures()
+    sigs = dict(signatures())
+    sigs.update(extension_signatures())                # bound after the main ones
     lib = ctypes.CDLL(LIB_PATH)
     for name, (ret, args) in sigs.items():
         fn = getattr(lib, name)

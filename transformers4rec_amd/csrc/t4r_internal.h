@@ -142,6 +142,13 @@ int t4r_xlnet_attn_long_bwd(hipStream_t st, const float* q, const float* k, cons
                             const float* rr, const float* out, const float* lse, const float* dout, float* dq, float* dk,
                             float* dv, float* part, float* delta, float* dkr, float* d_rw, float* d_rr, int B, int L, int n_head,
                             int d_head, float scale, long kr_bstride, DropCfg drop, const int* key_len, ReduceCtx* red);
+// t4r_xlnet_attn_uni_bwd (include/t4r_hip_uni.h: the causal core, xlnet_attn_uni.hip) with the context of its second stage
+int t4r_xlnet_attn_uni_bwd_impl(void* stream, const float* q, const float* k, const float* v, const float* k_r,
+                                const float* r_w_bias, const float* r_r_bias, const float* out, const float* lse,
+                                const float* dout, float* dq, float* dk, float* dv, float* dk_r, float* d_r_w_bias,
+                                float* d_r_r_bias, float* workspace, int B, int L, int n_head, int d_head, int kr_per_batch,
+                                float drop_p, unsigned long long seed, unsigned long long ctr_hi, const int* key_len,
+                                ReduceCtx* red);
 // MFMA kernels for L <= 32, d_head 16 / 32 (xlnet_attn_mfma.hip); T4R_ATTN_MFMA=0 keeps the VALU kernels
 int t4r_xlnet_attn_mfma_ok(int L, int d_head);
 int t4r_xlnet_attn_mfma_fwd(hipStream_t st, const float* q, const float* k, const float* v, const float* kr,

@@ -4,8 +4,9 @@
 //   XLNetFeedForward.forward                        :297-305
 //   XLNetLayer.forward                              :308-353
 // with the hyper-parameters fixed by XLNetConfig.build (transformers4rec/config/transformer.py:
-// 432-482): d_inner = 4 d_model, gelu(erf), layer_norm_eps as passed (0.03), attn_type "bi",
-// no masks, no mems.  Dropout = identity here (eval / p = 0).
+// 432-482): d_inner = 4 d_model, gelu(erf), layer_norm_eps as passed (0.03), attn_type "bi"
+// (no masks) or "uni" (the causal mask: the `causal` argument of the two *_impl functions, exported
+// as t4r_xlnet_layer_uni_fwd / _bwd, include/t4r_hip_uni.h), no mems.
 //
 // Layout (all fp32, row-major, token t = b*L + l):
 //   h [T,D] -> q,k,v = h @ {q,k,v}[D, n*dh]           (one batched MFMA GEMM when q,k,v are adjacent)
@@ -17,6 +18,7 @@
 #include "../../include/t4r_hip.h"
 #include "../../include/t4r_hip_rows.h"
 #include "../../include/t4r_hip_attn.h"
+#include "../../include/t4r_hip_uni.h"
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -167,9 +169,10 @@ static int layer_fwd_impl(void* stream, const float* h, const float* pos_emb,
                           const float* const* params, float* ws, float* h_out, int B, int L,
                           int D, int n_head, float ln_eps, float drop_p,
                           unsigned long long seed, unsigned long long offset, int layer_idx,
-                          const int* key_len, const float* pos_emb_b, const int* rows, int n_rows) {
+                          const int* key_len, const float* pos_emb_b, const int* rows, int n_rows, int causal) {
     if (B == 0) return 0;
     T4R_CHECK_ARG(D % n_head == 0 && D % 4 == 0, "xlnet_layer: d_model must divide by n_head and 4");
+    T4R_CHECK_ARG(!causal || !rows, "xlnet_layer: no row map with the causal core");
     T4R_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f, "xlnet_layer: dropout p in [0, 1)");
     hipStream_t st = (hipStream_t)stream;
     const int T = B * L, dh = D / n_head;
@@ -185,12 +188,16 @@ static int layer_fwd_impl(void* stream, const float* h, const float* pos_emb,
     const bool fuse_in = (layer_idx & T4R_LAYER_FUSE_INPUT) != 0 && drop;
     T4R_CHECK_ARG(!fuse_in || (use_fused(D) && use_attn_block(L, D, n_head)),
                   "xlnet_layer: the fused input dropout needs the one-kernel attention forward (L <= 32, d_model 32 / 64 / 128)");
+    T4R_CHECK_ARG(!causal || (layer_idx & T4R_LAYER_FUSE_INPUT) == 0,
+                  "xlnet_layer_uni: the fused input dropout rides in the one-kernel attention forward, which the causal layer never takes");
+    // the causal core (include/t4r_hip_uni.h, csrc/xlnet_attn_uni.hip) in place of the bi one; everything around it is shared
+    auto attn_core_fwd = causal ? t4r_xlnet_attn_uni_fwd : t4r_xlnet_attn_fwd;
     // the weight planes and k_r are already in `ws` (t4r_xlnet_stack_prepare): both launches are skipped (fused path only)
     const bool stack_prepared = (layer_idx & T4R_LAYER_STACK_PREPARED) != 0;
     if (use_fused(D)) {
         // ONE launch cuts the layer's nine weight matrices into bf16 planes; q, k, v in one token-tile launch; k_r; the
         // attention core; o-projection + dropout + residual + LayerNorm in one launch; the feed-forward block in one
-        const bool block = use_attn_block(L, D, n_head);
+        const bool block = !causal && use_attn_block(L, D, n_head);
         if (!stack_prepared) RUN(t4r_xlnet_layer_prepare(stream, params, D, w.planes));
         if (!block) RUN(t4r_xlnet_qkv_proj(stream, h, w.planes, w.qkv, T, D));
         if (stack_prepared) {
@@ -213,7 +220,7 @@ static int layer_fwd_impl(void* stream, const float* h, const float* pos_emb,
                                               w.mean1, w.rstd1, w.h1, B, L, D, n_head, ln_eps, drop_p, seed, C(SITE_PROB),
                                               C(SITE_ATTN_OUT), key_len, fuse_in, ctr_hi(offset, 255, SITE_INPUT), w.hin));
         } else {
-        RUN(t4r_xlnet_attn_fwd(stream, w.qkv, w.qkv + TD, w.qkv + 2 * TD, w.kr, params[P_RWB], params[P_RRB], w.av, w.lse,
+        RUN(attn_core_fwd(stream, w.qkv, w.qkv + TD, w.qkv + 2 * TD, w.kr, params[P_RWB], params[P_RRB], w.av, w.lse,
                                B, L, n_head, dh, drop, drop_p, seed, C(SITE_PROB), key_len));
         RUN(t4r_xlnet_oproj_ln(stream, w.av, h, w.planes, params[P_LN1W], params[P_LN1B], w.ao, w.mean1, w.rstd1, w.h1, T, D,
                                ln_eps, drop_p, seed, C(SITE_ATTN_OUT)));
@@ -259,8 +266,8 @@ static int layer_fwd_impl(void* stream, const float* h, const float* pos_emb,
         RUN(t4r_gemm_launch(st, 0, 0, 2 * L, D, D, 1.f, pos_emb, D, params[P_R], D, w.kr, D, nullptr,
                             EPI_NONE, nullptr, 0, 1, 0, 1, 0, 0, 0, nullptr));
     }
-    RUN(t4r_xlnet_attn_fwd(stream, w.qkv, w.qkv + TD, w.qkv + 2 * TD, w.kr, params[P_RWB],
-                           params[P_RRB], w.av, w.lse, B, L, n_head, dh, drop, drop_p, seed, C(SITE_PROB), key_len));
+    RUN(attn_core_fwd(stream, w.qkv, w.qkv + TD, w.qkv + 2 * TD, w.kr, params[P_RWB],
+                      params[P_RRB], w.av, w.lse, B, L, n_head, dh, drop, drop_p, seed, C(SITE_PROB), key_len));
     // attn_out[t, h] = sum_{nd} av[t, nd] * o[h, nd]
     RUN(t4r_gemm_launch(st, 0, 1, T, D, D, 1.f, w.av, D, params[P_O], D, w.ao, D, nullptr, EPI_NONE,
                         nullptr, 0, 1, 0, 1, 0, 0, 0, nullptr));
@@ -282,7 +289,15 @@ extern "C" int t4r_xlnet_layer_fwd(void* stream, const float* h, const float* po
                                    unsigned long long seed, unsigned long long offset, int layer_idx,
                                    const int* key_len, const float* pos_emb_b) {
     return layer_fwd_impl(stream, h, pos_emb, params, ws, h_out, B, L, D, n_head, ln_eps, drop_p, seed, offset, layer_idx, key_len,
-                          pos_emb_b, nullptr, 0);
+                          pos_emb_b, nullptr, 0, 0);
+}
+// include/t4r_hip_uni.h
+extern "C" int t4r_xlnet_layer_uni_fwd(void* stream, const float* h, const float* pos_emb, const float* const* params, float* ws,
+                                       float* h_out, int B, int L, int D, int n_head, float ln_eps, float drop_p,
+                                       unsigned long long seed, unsigned long long offset, int layer_idx, const int* key_len,
+                                       const float* pos_emb_b) {
+    return layer_fwd_impl(stream, h, pos_emb, params, ws, h_out, B, L, D, n_head, ln_eps, drop_p, seed, offset, layer_idx, key_len,
+                          pos_emb_b, nullptr, 0, 1);
 }
 extern "C" int t4r_xlnet_layer_fwd_rows(void* stream, const float* h, const float* pos_emb, const float* const* params, float* ws,
                                         float* h_out, int B, int L, int D, int n_head, float ln_eps, float drop_p,
@@ -290,7 +305,7 @@ extern "C" int t4r_xlnet_layer_fwd_rows(void* stream, const float* h, const floa
                                         const float* pos_emb_b, const int* rows, int n) {
     RUN(rows_args_ok("xlnet_layer_fwd_rows", B, L, D, n_head, key_len, rows, n));
     return layer_fwd_impl(stream, h, pos_emb, params, ws, h_out, B, L, D, n_head, ln_eps, drop_p, seed, offset, layer_idx, key_len,
-                          pos_emb_b, rows, n);
+                          pos_emb_b, rows, n, 0);
 }
 
 // Weight-gradient contractions feed nothing but the optimizer, so the layer backward issues them on a
@@ -370,8 +385,11 @@ static int layer_bwd_impl(void* stream, const float* h, const float* pos_emb,
                           float* bws, const float* dh_out, float* dh_in, int B, int L, int D,
                           int n_head, float ln_eps, float drop_p, unsigned long long seed,
                           unsigned long long offset, int layer_idx, const int* key_len,
-                          const float* pos_emb_b, const int* rows, int n_rows) {
+                          const float* pos_emb_b, const int* rows, int n_rows, int causal) {
     if (B == 0) return 0;
+    T4R_CHECK_ARG(!causal || !rows, "xlnet_layer: no row map with the causal core");
+    T4R_CHECK_ARG(!causal || (layer_idx & T4R_LAYER_FUSE_INPUT) == 0,
+                  "xlnet_layer_uni: the fused input dropout rides in the one-kernel attention forward, which the causal layer never takes");
     hipStream_t st = (hipStream_t)stream;
     const int T = B * L, dh = D / n_head;
     const long TD = (long)T * D, DD = (long)D * D;
@@ -502,7 +520,7 @@ static int layer_bwd_impl(void* stream, const float* h, const float* pos_emb,
     }
     if (fused) {
 #ifdef T4R_EXPERIMENTAL
-        const bool block = use_attn_block_bwd(L, D, n_head);
+        const bool block = !causal && use_attn_block_bwd(L, D, n_head);
         if (block) {
             // LayerNorm-1 backward, d attn_vec, the attention core backward and d h: ONE launch (tools/experimental)
             RUN(t4r_xlnet_attn_block_bwd_impl(stream, dx, w.ao, h, w.mean1, w.rstd1, params[P_LN1W], w.planes, params[P_Q], params[P_K],
@@ -525,6 +543,11 @@ static int layer_bwd_impl(void* stream, const float* h, const float* pos_emb,
         RUN(t4r_xlnet_ln1_bwd_impl(stream, dx, w.ao, h, w.mean1, w.rstd1, params[P_LN1W], w.planes, dh_in, dao_buf, dav,
                                    grads[P_LN1W], grads[P_LN1B], ln1_part, T, D, drop_p, seed, C(SITE_ATTN_OUT), red));
         // (the one-kernel forward left the probabilities in the workspace: the core reads them instead of recomputing the scores)
+        if (causal)   // (the causal layer's forward stored no probabilities: the core recomputes the scores)
+            RUN(t4r_xlnet_attn_uni_bwd_impl(stream, w.qkv, w.qkv + TD, w.qkv + 2 * TD, w.kr, params[P_RWB], params[P_RRB], w.av,
+                                            w.lse, dav, dqkv, dqkv + TD, dqkv + 2 * TD, dkr, grads[P_RWB], grads[P_RRB], attn_ws,
+                                            B, L, n_head, dh, drop, drop_p, seed, C(SITE_PROB), key_len, red));
+        else
         RUN(t4r_xlnet_attn_bwd_impl(stream, w.qkv, w.qkv + TD, w.qkv + 2 * TD, w.kr, params[P_RWB],
                                     params[P_RRB], w.av, w.lse, use_attn_block(L, D, n_head) ? w.prob : nullptr, dav, dqkv,
                                     dqkv + TD, dqkv + 2 * TD, dkr, grads[P_RWB], grads[P_RRB], attn_ws, B, L, n_head, dh, drop,
@@ -581,6 +604,11 @@ static int layer_bwd_impl(void* stream, const float* h, const float* pos_emb,
                         nullptr, 0, -1, 1, 1, 0, 0, 0, nullptr, wgrad));
     if (ss) (void)hipEventRecord(ss->done_o, ss->s);
     // attention core
+    if (causal)
+        RUN(t4r_xlnet_attn_uni_bwd_impl(stream, w.qkv, w.qkv + TD, w.qkv + 2 * TD, w.kr, params[P_RWB], params[P_RRB], w.av, w.lse,
+                                        dav, dqkv, dqkv + TD, dqkv + 2 * TD, dkr, grads[P_RWB], grads[P_RRB], attn_ws, B, L,
+                                        n_head, dh, drop, drop_p, seed, C(SITE_PROB), key_len, red));
+    else
     RUN(t4r_xlnet_attn_bwd_impl(stream, w.qkv, w.qkv + TD, w.qkv + 2 * TD, w.kr, params[P_RWB],
                                 params[P_RRB], w.av, w.lse, nullptr, dav, dqkv, dqkv + TD, dqkv + 2 * TD, dkr,
                                 grads[P_RWB], grads[P_RRB], attn_ws, B, L, n_head, dh, drop, drop_p, seed,
@@ -626,7 +654,15 @@ extern "C" int t4r_xlnet_layer_bwd(void* stream, const float* h, const float* po
                                    unsigned long long offset, int layer_idx, const int* key_len,
                                    const float* pos_emb_b) {
     return layer_bwd_impl(stream, h, pos_emb, params, grads, ws, bws, dh_out, dh_in, B, L, D, n_head, ln_eps, drop_p, seed, offset,
-                          layer_idx, key_len, pos_emb_b, nullptr, 0);
+                          layer_idx, key_len, pos_emb_b, nullptr, 0, 0);
+}
+// include/t4r_hip_uni.h
+extern "C" int t4r_xlnet_layer_uni_bwd(void* stream, const float* h, const float* pos_emb, const float* const* params,
+                                       float* const* grads, const float* ws, float* bws, const float* dh_out, float* dh_in, int B,
+                                       int L, int D, int n_head, float ln_eps, float drop_p, unsigned long long seed,
+                                       unsigned long long offset, int layer_idx, const int* key_len, const float* pos_emb_b) {
+    return layer_bwd_impl(stream, h, pos_emb, params, grads, ws, bws, dh_out, dh_in, B, L, D, n_head, ln_eps, drop_p, seed, offset,
+                          layer_idx, key_len, pos_emb_b, nullptr, 0, 1);
 }
 extern "C" int t4r_xlnet_layer_bwd_rows(void* stream, const float* h, const float* pos_emb, const float* const* params,
                                         float* const* grads, const float* ws, float* bws, const float* dh_out, float* dh_in,
@@ -635,7 +671,7 @@ extern "C" int t4r_xlnet_layer_bwd_rows(void* stream, const float* h, const floa
                                         const int* rows, int n) {
     RUN(rows_args_ok("xlnet_layer_bwd_rows", B, L, D, n_head, key_len, rows, n));
     return layer_bwd_impl(stream, h, pos_emb, params, grads, ws, bws, dh_out, dh_in, B, L, D, n_head, ln_eps, drop_p, seed, offset,
-                          layer_idx, key_len, pos_emb_b, rows, n);
+                          layer_idx, key_len, pos_emb_b, rows, n, 0);
 }
 
 // the caller's stream waits for everything queued so far on the weight-gradient streams of the current device, whichever

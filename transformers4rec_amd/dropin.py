@@ -299,13 +299,14 @@ def shadow_block(ref):
     kind = _cls(body)
     with _meta():
         if kind == "XLNetModel":
-            if getattr(c, "attn_type", "bi") != "bi" or getattr(c, "bi_data", False) or \
+            attn_type = getattr(c, "attn_type", "bi")
+            if attn_type not in ("bi", "uni") or getattr(c, "bi_data", False) or \
                     getattr(c, "clamp_len", -1) != -1 or getattr(c, "same_length", False):
-                raise NotImplementedError("dropin: XLNet with attn_type != 'bi' / bi_data / clamp_len / same_length "
-                                          "is off the HIP hot path")
+                raise NotImplementedError("dropin: XLNet with attn_type other than 'bi' / 'uni', or with bi_data / clamp_len / "
+                                          "same_length, is off the HIP hot path")
             if getattr(c, "ff_activation", "gelu") != "gelu":
                 raise NotImplementedError("dropin: XLNet ff_activation must be 'gelu'")
-            cfg = X.XLNetConfig.build(d_model=c.d_model, n_head=c.n_head, n_layer=c.n_layer,
+            cfg = X.XLNetConfig.build(d_model=c.d_model, n_head=c.n_head, n_layer=c.n_layer, attn_type=attn_type,
                                       initializer_range=c.initializer_range, layer_norm_eps=c.layer_norm_eps,
                                       dropout=c.dropout, mem_len=getattr(c, "mem_len", 1) or 1)
             cfg.d_inner, cfg.vocab_size = c.d_inner, c.vocab_size

@@ -31,6 +31,9 @@ def layer_params(model):
 def config_of(model):
     t = model.transformer_block.transformer
     m = model.input_features.masking
+    if getattr(t.config, "attn_type", "bi") != "bi":
+        raise NotImplementedError("functional: the operator-composed step restates the attn_type='bi' body only; an XLNet built "
+                                  "with attn_type='uni' trains through the module path (Model / TransformerBlock)")
     return dict(n_head=t.config.n_head, eps=float(t.config.layer_norm_eps), dropout=float(t.config.dropout),
                 mlm_probability=float(m.mlm_probability), padding_idx=int(m.padding_idx),
                 temperature=float(model.prediction_task.pre.module.softmax_temperature or 1.0),

@@ -728,6 +728,36 @@ def xlnet_attn_bwd_prob(q, k, v, k_r, r_w_bias, r_r_bias, prob, dout, d_rw, d_rr
     return dq, dk, dv, dkr
 
 
+def xlnet_attn_uni_fwd(q, k, v, k_r, r_w_bias, r_r_bias, B, L, n_head, drop=NO_DROP, key_len=None):
+    """xlnet_attn_fwd with the causal dead set of attn_type='uni' (include/t4r_hip_uni.h): key j of row i is dead when j > i,
+    or under the padding rule of key_len.  k_r keeps the [2L, D] layout; rows 1 .. L are read."""
+    D = q.shape[-1]
+    per_b = int(k_r.shape[0] == B * 2 * L and B > 1)
+    out = torch.empty((B * L, D), device=q.device, dtype=torch.float32)
+    lse = torch.empty((B, n_head, L), device=q.device, dtype=torch.float32)
+    call("t4r_xlnet_attn_uni_fwd", _stream(), _chk(q), _chk(k), _chk(v), _chk(k_r), _chk(r_w_bias),
+         _chk(r_r_bias), out.data_ptr(), lse.data_ptr(), B, L, n_head, D // n_head, per_b,
+         float(drop[0]), int(drop[1]), int(drop[2]), _p(key_len, torch.int32))
+    return out, lse
+
+
+def xlnet_attn_uni_bwd(q, k, v, k_r, r_w_bias, r_r_bias, out, lse, dout, d_rw, d_rr, B, L, n_head,
+                       drop=NO_DROP, key_len=None):
+    """-> dq, dk, dv, dkr (rows 0 and L + 1 .. 2L - 1 of dkr exact zeros); d_rw / d_rr accumulated"""
+    D = q.shape[-1]
+    dev = q.device
+    per_b = int(k_r.shape[0] == B * 2 * L and B > 1)
+    dq, dk, dv = torch.empty((3, B * L, D), device=dev, dtype=torch.float32).unbind(0)
+    dkr = torch.empty_like(k_r)
+    nws = _lib.load().t4r_xlnet_attn_bwd_ws_floats(B, L, D, n_head)
+    ws = torch.empty(nws, device=dev, dtype=torch.float32)
+    call("t4r_xlnet_attn_uni_bwd", _stream(), _chk(q), _chk(k), _chk(v), _chk(k_r), _chk(r_w_bias),
+         _chk(r_r_bias), _chk(out), _chk(lse), _chk(dout), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
+         dkr.data_ptr(), _chk(d_rw), _chk(d_rr), ws.data_ptr(), B, L, n_head, D // n_head, per_b,
+         float(drop[0]), int(drop[1]), int(drop[2]), _p(key_len, torch.int32))
+    return dq, dk, dv, dkr
+
+
 def mha_fwd(q, k, v, B, L, n_head, causal, drop=NO_DROP, key_len=None):
     """q,k,v: [B*L, D] views that may be column slices of one [B*L, 3D] buffer (row stride = ld)."""
     D = q.shape[1]
@@ -789,8 +819,9 @@ def xlnet_pos_emb_dropout(pos_emb, B, p, seed, offset):
 
 
 def xlnet_layer_fwd(h, pos_emb, params, B, L, n_head, eps, ws=None, drop_p=0.0, seed=0, offset=0,
-                    layer_idx=0, key_len=None, pos_emb_b=None, stack_prepared=False, rows=None, n_rows=None):
+                    layer_idx=0, key_len=None, pos_emb_b=None, stack_prepared=False, rows=None, n_rows=None, causal=False):
     """h [B*L, D]; params: sequence of 15 tensors in XLNET_PARAM_ORDER.  -> (h_out, ws)
+    causal: the layer of attn_type='uni' (include/t4r_hip_uni.h: t4r_xlnet_layer_uni_fwd; no row map, no LAYER_FUSE_INPUT)
     stack_prepared: `ws` already holds this layer's weight planes and k_r (xlnet_stack_prepare)
     rows (int32, ascending, unique, first n_rows entries valid): the feed-forward block runs on these rows only and h_out is
     zero elsewhere (include/t4r_hip_rows.h: t4r_xlnet_layer_fwd_rows); the backward must be given the same map"""
@@ -804,7 +835,11 @@ def xlnet_layer_fwd(h, pos_emb, params, B, L, n_head, eps, ws=None, drop_p=0.0, 
     args = (_stream(), _chk(h, torch.float32), _chk(pos_emb, torch.float32), parr,
             ws.data_ptr(), out.data_ptr(), B, L, D, n_head, float(eps), float(drop_p), int(seed),
             int(offset), int(layer_idx) | flags, _p(key_len, torch.int32), _p(pos_emb_b, torch.float32))
-    if rows is None:
+    if causal:
+        if rows is not None:
+            raise ValueError("xlnet_layer_fwd: no row map with causal=True")
+        call("t4r_xlnet_layer_uni_fwd", *args)
+    elif rows is None:
         call("t4r_xlnet_layer_fwd", *args)
     else:
         call("t4r_xlnet_layer_fwd_rows", *args, _chk(rows, torch.int32), int(n_rows))
@@ -845,8 +880,10 @@ def xlnet_stack_prepare(params_all, B, L, n_head, pos, drop, pos_dropout=None):
 
 
 def xlnet_layer_bwd(h, pos_emb, params, grads, ws, dh_out, B, L, n_head, eps, bws=None, drop_p=0.0,
-                    seed=0, offset=0, layer_idx=0, key_len=None, pos_emb_b=None, defer_join=None, rows=None, n_rows=None):
-    """rows, n_rows: the map the forward was given (xlnet_layer_fwd): dh_out is read at these rows only.
+                    seed=0, offset=0, layer_idx=0, key_len=None, pos_emb_b=None, defer_join=None, rows=None, n_rows=None,
+                    causal=False):
+    """causal: the forward was xlnet_layer_fwd(..., causal=True).
+    rows, n_rows: the map the forward was given (xlnet_layer_fwd): dh_out is read at these rows only.
     defer_join: a list -> the call returns without waiting for its weight-gradient streams (csrc/xlnet_layer.hip:
     deferred join) and appends every buffer those streams may still be using to the list; the caller keeps the list
     alive until it has called xlnet_layer_bwd_join()."""
@@ -861,7 +898,11 @@ def xlnet_layer_bwd(h, pos_emb, params, grads, ws, dh_out, B, L, n_head, eps, bw
     args = (_stream(), _chk(h), _chk(pos_emb), parr, garr, _chk(ws),
             bws.data_ptr(), _chk(dh_out), dh_in.data_ptr(), B, L, D, n_head, float(eps), float(drop_p),
             int(seed), int(offset), int(layer_idx) | flags, _p(key_len, torch.int32), _p(pos_emb_b, torch.float32))
-    if rows is None:
+    if causal:
+        if rows is not None:
+            raise ValueError("xlnet_layer_bwd: no row map with causal=True")
+        call("t4r_xlnet_layer_uni_bwd", *args)
+    elif rows is None:
         call("t4r_xlnet_layer_bwd", *args)
     else:
         call("t4r_xlnet_layer_bwd_rows", *args, _chk(rows, torch.int32), int(n_rows))

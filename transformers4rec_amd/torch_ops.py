@@ -269,6 +269,21 @@ def _(h, pos_emb, params, B, L, n_head, eps, key_len):
     return h.new_empty(h.shape)
 
 
+@torch.library.custom_op(f"{NS}::xlnet_layer_uni_infer", mutates_args=())
+def xlnet_layer_uni_infer(h: torch.Tensor, pos_emb: torch.Tensor, params: Sequence[torch.Tensor], B: int, L: int, n_head: int,
+                          eps: float, key_len: Optional[torch.Tensor]) -> torch.Tensor:
+    """xlnet_layer_infer for attn_type='uni': the causal relative-attention core (include/t4r_hip_uni.h), the rest of the
+    layer unchanged.  pos_emb keeps the [2L, D] layout."""
+    out, _ws = ops.xlnet_layer_fwd(h.contiguous(), pos_emb, [p.detach().contiguous() for p in params], B, L, n_head, eps,
+                                   key_len=key_len, causal=True)
+    return out
+
+
+@xlnet_layer_uni_infer.register_fake
+def _(h, pos_emb, params, B, L, n_head, eps, key_len):
+    return h.new_empty(h.shape)
+
+
 @torch.library.custom_op(f"{NS}::xlnet_layer_fwd", mutates_args=())
 def xlnet_layer_fwd(h: torch.Tensor, pos_emb: torch.Tensor, params: Sequence[torch.Tensor], B: int, L: int, n_head: int,
                     eps: float, drop_p: float, seed: int, offset: int, layer_idx: int,
@@ -867,7 +882,7 @@ def _(g, x, active, labels, z, n_active, W1, b1, w2, act):
 
 OPERATORS = ("gemm", "item_scores", "topk", "item_topk", "item_sample", "gumbel_argmax", "item_eval", "pack_item_table",
              "pack_item_filter", "item_mask_", "item_topk_filtered", "item_sample_filtered", "rank_of_target", "embedding_gather", "embedding_bag", "ragged_to_padded",
-             "xlnet_layer_infer", "xlnet_layer_fwd", "xlnet_layer_bwd", "mlm_targets", "seq_item_embedding",
+             "xlnet_layer_infer", "xlnet_layer_uni_infer", "xlnet_layer_fwd", "xlnet_layer_bwd", "mlm_targets", "seq_item_embedding",
              "seq_item_embedding_bwd", "xlnet_layer_grad", "gather_label_rows", "scatter_label_rows", "linear_softmax_ce",
              "linear_softmax_ce_bwd", "dropout", "pos_emb_dropout", "next_item_head", "next_item_head_bwd",
              "soft_embedding", "soft_embedding_grad", "seq_concat", "seq_concat_grad", "linear_relu", "linear_relu_grad", "apply_mask",

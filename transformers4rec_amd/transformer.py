@@ -45,8 +45,8 @@ class XLNetConfig:
     def build(cls, d_model, n_head, n_layer, total_seq_length=None, attn_type="bi", hidden_act="gelu",
               initializer_range=0.01, layer_norm_eps=0.03, dropout=0.3, pad_token=0,
               log_attention_weights=False, mem_len=1, **kwargs):
-        if attn_type != "bi":
-            raise NotImplementedError("only attn_type='bi' (the reference default) is on the hot path")
+        if attn_type not in ("bi", "uni"):
+            raise ValueError(f"attn_type must be 'bi' (masked LM, the reference default) or 'uni' (causal LM), not {attn_type!r}")
         if hidden_act != "gelu":
             raise NotImplementedError("only hidden_act='gelu' (erf) is on the hot path")
         if d_model % n_head:
@@ -141,8 +141,10 @@ def relative_positional_encoding(L, D):
 
 class _XLNetLayerFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, h, anchor, layer, pos_emb, n_head, eps, drop, key_len=None, pos_emb_b=None, ws=None, out_rows=None):
-        """ws: this layer's workspace with its weight planes and k_r already in it (XLNetModel.forward: stack prologue)
+    def forward(ctx, h, anchor, layer, pos_emb, n_head, eps, drop, key_len=None, pos_emb_b=None, ws=None, out_rows=None,
+                causal=False):
+        """causal: attn_type='uni' (include/t4r_hip_uni.h); never with out_rows
+        ws: this layer's workspace with its weight planes and k_r already in it (XLNetModel.forward: stack prologue)
         out_rows: (rows int32, n) -- the consumer reads the output at these rows only and returns a gradient that is zero
         elsewhere: the feed-forward block and LayerNorm-1 backward run on them alone (include/t4r_hip_rows.h)"""
         B, L, D = h.shape
@@ -153,8 +155,8 @@ class _XLNetLayerFn(torch.autograd.Function):
                                       offset=offset, layer_idx=idx, key_len=key_len, pos_emb_b=pos_emb_b,
                                       stack_prepared=ws is not None,
                                       rows=None if out_rows is None else out_rows[0],
-                                      n_rows=None if out_rows is None else out_rows[1])
-        ctx.out_rows = out_rows
+                                      n_rows=None if out_rows is None else out_rows[1], causal=causal)
+        ctx.out_rows, ctx.causal = out_rows, causal
         ctx.layer, ctx.pos_emb, ctx.cfg, ctx.drop, ctx.key_len = layer, pos_emb, (B, L, D, n_head, eps), drop, key_len
         ctx.pos_emb_b = pos_emb_b
         ctx.save_for_backward(h2, ws)
@@ -175,11 +177,11 @@ class _XLNetLayerFn(torch.autograd.Function):
                                  dout.contiguous().view(B * L, D), B, L, n_head, eps, drop_p=p, seed=seed,
                                  offset=offset, layer_idx=idx, key_len=ctx.key_len, pos_emb_b=ctx.pos_emb_b,
                                  defer_join=defer, rows=None if ctx.out_rows is None else ctx.out_rows[0],
-                                 n_rows=None if ctx.out_rows is None else ctx.out_rows[1])
+                                 n_rows=None if ctx.out_rows is None else ctx.out_rows[1], causal=ctx.causal)
         if defer is not None:
             # one callback per deferred call (idempotent): no state that an aborted backward pass could leave behind
             torch.autograd.Variable._execution_engine.queue_callback(_join_weight_gradient_streams)
-        return dh.view(B, L, D), None, None, None, None, None, None, None, None, None, None
+        return dh.view(B, L, D), None, None, None, None, None, None, None, None, None, None, None
 
 
 from ._lib import exp_env as _exp_env  # noqa: E402
@@ -275,11 +277,15 @@ class XLNetModel(SeedMixin, nn.Module):
             self._drop_offset += 1
             offset = self._drop_offset
         h = inputs_embeds
+        # attn_type 'uni': every layer runs the causal core (include/t4r_hip_uni.h).  Its attention half is never the one-kernel
+        # block, so the input dropout is the element-wise launch and no row map is taken (every row is computed); the positional
+        # tensor and its dropout keep the 2L-row layout and keys -- the core reads rows 1 .. L of k_r
+        causal = cfg.attn_type == "uni"
         # the model-level INPUT dropout (HF :1116) rides in the first layer's kernels (csrc/xlnet_layer.hip: T4R_LAYER_FUSE_INPUT: the
         # attention-block kernel masks h on load and keeps the dropped rows for the backward, xlnet_dh masks d h) where the
         # one-kernel attention forward takes the shape; else it is the element-wise launch
         fuse_in = (p > 0 and torch.is_grad_enabled() and _FUSE_INPUT and _FUSED_ON and ops.xlnet_fused_supported(D)
-                   and ops.xlnet_attn_block_supported(L, D, cfg.n_head) and key_len is None)
+                   and ops.xlnet_attn_block_supported(L, D, cfg.n_head) and key_len is None and not causal)
         if p > 0 and not fuse_in:
             h = _DropoutFn.apply(h, p, self.seed, ops.dropout_ctr_hi(offset, 255, ops.SITE_INPUT))
         # dropout(pos_emb) is drawn once per forward and shared by the layers (HF :1143).  With the stack prologue the projection
@@ -306,11 +312,11 @@ class XLNetModel(SeedMixin, nn.Module):
         fuse_final = p > 0 and not infer and _FUSE_FINAL and _FUSED_ON and ops.xlnet_fused_supported(D)
         for i, layer in enumerate(self.layer):
             if infer:
-                h = torch.ops.t4r_hip.xlnet_layer_infer(h.reshape(B * L, D), pos, layer.ordered_params(), B, L, cfg.n_head,
-                                                        cfg.layer_norm_eps, key_len).view(B, L, D)
+                op = torch.ops.t4r_hip.xlnet_layer_uni_infer if causal else torch.ops.t4r_hip.xlnet_layer_infer
+                h = op(h.reshape(B * L, D), pos, layer.ordered_params(), B, L, cfg.n_head, cfg.layer_norm_eps, key_len).view(B, L, D)
                 continue
             rows_i = None
-            if (out_rows is not None and i == len(self.layer) - 1 and not infer and key_len is None and torch.is_grad_enabled()
+            if (out_rows is not None and not causal and i == len(self.layer) - 1 and not infer and key_len is None and torch.is_grad_enabled()
                     and _FUSED_ON and ops.xlnet_fused_supported(D) and ops.xlnet_attn_block_supported(L, D, cfg.n_head)):
                 r = out_rows(B, L) if callable(out_rows) else out_rows        # Model.forward: decided (and the label count awaited) here
                 if r is not None:
@@ -319,7 +325,7 @@ class XLNetModel(SeedMixin, nn.Module):
             h = _XLNetLayerFn.apply(h, layer.rel_attn.q, layer, pos, cfg.n_head, cfg.layer_norm_eps,
                                     (p, self.seed, offset, i | (ops.LAYER_FUSE_FINAL if fuse_final and i == len(self.layer) - 1 else 0)
                                      | (ops.LAYER_FUSE_INPUT if fuse_in and i == 0 else 0)),
-                                    key_len, pos_b, None if ws_all is None else ws_all[i], rows_i)
+                                    key_len, pos_b, None if ws_all is None else ws_all[i], rows_i, causal)
         if p > 0 and not fuse_final:
             h = _DropoutFn.apply(h, p, self.seed, ops.dropout_ctr_hi(offset, 255, ops.SITE_FINAL))
         return (h,)
