@@ -21,6 +21,7 @@ from .prediction_task import LogUniformSampler, NextItemPredictionTask  # noqa: 
 from .session_task import BinaryClassificationTask, RegressionTask  # noqa: E402,F401
 from .rtd import RTDModel, ReplacedTokenDetectionHead  # noqa: E402,F401
 from .model import Head, Model  # noqa: E402,F401
+from . import experimental  # noqa: E402,F401
 from .optim import FlatParams, FusedAdam, RowSparseAdam, flatten_model, row_sparse_tables, warmup_schedule  # noqa: E402,F401
 from .distributed import GradReducer, SparseRowExchange, head_backward_hook, shard_batch  # noqa: E402,F401
 from .data import ParquetSessionLoader, read_ragged_columns  # noqa: E402,F401

@@ -1,7 +1,9 @@
 """ctypes binding of libt4r_hip.so.  The C ABI is declared in the headers under include/ (HEADERS); the ctypes prototypes are
 derived from those declarations (signatures()), so a new header is registered by adding its file name to HEADERS.
 EXTENSION_HEADERS are headers of the same library that are bound after the main ones (extension_signatures()): their names
-are not part of signatures() / header_symbols() / HEADERS, and may not repeat one of those.
+are not part of signatures() / header_symbols() / HEADERS, and may not repeat one of those.  FEATURE_HEADERS are bound after
+both (feature_signatures()), under the same rule: a later feature's header is appended to that tuple and changes neither of the
+other two.
 
 There is NO fallback: if the shared library is missing or a call fails the product path
 raises.  Build with `python -m transformers4rec_amd.build` (or __graft_entry__.build()).
@@ -17,6 +19,7 @@ LIB_PATH = os.environ.get("T4R_HIP_LIB") or os.path.join(_HERE, "lib", "libt4r_h
 HEADERS = ("t4r_hip.h", "t4r_hip_sampling.h", "t4r_hip_filter.h", "t4r_hip_optim.h", "t4r_hip_pretrained.h", "t4r_hip_attn.h",
            "t4r_hip_rows.h", "t4r_hip_rowadam.h", "t4r_hip_contproj.h", "t4r_hip_rowclip.h", "t4r_hip_seqtask.h", "t4r_hip_rtd.h")
 EXTENSION_HEADERS = ("t4r_hip_uni.h",)
+FEATURE_HEADERS = ("t4r_hip_postfusion.h",)
 
 
 def header_path(name):
@@ -113,6 +116,23 @@ def extension_signatures():
     return sigs
 
 
+@functools.lru_cache(maxsize=None)
+def feature_signatures():
+    """name -> (restype code, argtype codes) of the entries declared in FEATURE_HEADERS (same parser); a name that
+    signatures(), extension_signatures() or another feature header already has is an error."""
+    taken = {name: "the main headers" for name in signatures()}
+    taken.update({name: "the extension headers" for name in extension_signatures()})
+    sigs, where = {}, {}
+    for header in FEATURE_HEADERS:
+        for name, sig in _header_signatures(header).items():
+            if name in taken:
+                raise T4RHipError(f"`{name}` of the feature header {header} is already declared in {taken[name]}")
+            if name in sigs:
+                raise T4RHipError(f"`{name}` is declared in both {where[name]} and {header}")
+            sigs[name], where[name] = sig, header
+    return sigs
+
+
 def header_symbols(header=HEADERS[0]):
     """Sorted function names declared in include/<header>."""
     return sorted(_header_signatures(header))
@@ -129,6 +149,7 @@ def load():
             "(run `python -m transformers4rec_amd.build`). There is no CPU fallback.")
     sigs = dict(signatures())
     sigs.update(extension_signatures())                # bound after the main ones
+    sigs.update(feature_signatures())                  # and these after both
     lib = ctypes.CDLL(LIB_PATH)
     for name, (ret, args) in sigs.items():
         fn = getattr(lib, name)

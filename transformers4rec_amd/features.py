@@ -96,12 +96,47 @@ class SoftEmbedding(nn.Module):
         self.projection_layer = _Linear(1, num_embeddings)
 
 
+class _SeqEmbeddingsFn(torch.autograd.Function):
+    """the lookups of a stand-alone SequenceEmbeddingFeatures call: one concatenating gather (t4r_seq_features_fwd) into
+    [B, L, sum(dims)]; backward: each table's column block through the deterministic sorted scatter into `.grad`, as everywhere
+    on this path."""
+
+    @staticmethod
+    def forward(ctx, anchor, mod, names, ids, err):
+        B, L = ids[0].shape
+        feats, col = [], 0
+        for n, i in zip(names, ids):
+            tab = mod.embedding_tables[n].weight
+            feats.append(dict(kind=0, input=i, table=tab.detach(), dim=tab.shape[1], col=col, rows=tab.shape[0]))
+            col += tab.shape[1]
+        ctx.mod, ctx.names, ctx.ids, ctx.sorted_ids = mod, names, ids, {}
+        return ops.seq_features_fwd(feats, "concat", B, L, L, col, err_flag=err)
+
+    @staticmethod
+    def backward(ctx, dy):
+        d2 = dy.contiguous().view(-1, dy.shape[-1])
+        col = 0
+        for n, i in zip(ctx.names, ctx.ids):
+            tab = ctx.mod.embedding_tables[n].weight
+            if tab.requires_grad:
+                _table_scatter(ctx, n, d2, i.view(-1), tab, col, tab.shape[1], ctx.mod.padding_idx)
+            col += tab.shape[1]
+        return None, None, None, None, None
+
+
 class SequenceEmbeddingFeatures(nn.Module):
-    """Categorical sequence features; holds `embedding_tables` and the stateful `item_seq`."""
+    """Categorical sequence features; holds `embedding_tables` and the stateful `item_seq`.  Inside a TabularSequenceFeatures
+    the block's one kernel does the lookups; called on its own (a post-context module, experimental.PostContextFusion),
+    forward(inputs) returns {name: [B, L, dim]} (aggregation=None) or their concatenation in sorted-name order
+    (aggregation="concat", tabular/aggregation.py:35-47)."""
 
     def __init__(self, table_sizes: Dict[str, tuple], item_id: Optional[str] = None, padding_idx: int = 0,
-                 pre=None, post=None):
+                 pre=None, post=None, aggregation: Optional[str] = None):
         super().__init__()
+        if aggregation not in (None, "concat"):
+            raise NotImplementedError("SequenceEmbeddingFeatures on the HIP path aggregates with None or 'concat'")
+        self.aggregation = aggregation
+        self._err = None
         self.item_id = item_id
         self.padding_idx = padding_idx
         self.embedding_tables = nn.ModuleDict(
@@ -127,6 +162,35 @@ class SequenceEmbeddingFeatures(nn.Module):
 
     def item_ids(self, inputs):
         return inputs[self.item_id]
+
+    def forward(self, inputs, **kwargs):
+        """stand-alone lookups of the features present in `inputs` ([B, L] int64 ids each)"""
+        if self._pre is not None or self._post is not None:
+            raise NotImplementedError("pre / post transformations of a stand-alone SequenceEmbeddingFeatures are off the hot path")
+        names = [n for n in sorted(self.embedding_tables) if n in inputs]
+        if not names:
+            return {}
+        ids = [inputs[n].contiguous() for n in names]
+        if any(i.dim() != 2 or i.shape != ids[0].shape for i in ids):
+            raise ValueError("SequenceEmbeddingFeatures: every feature must be [B, L] ids of one shape")
+        dev = self.embedding_tables[names[0]].weight.device
+        if self._err is None or self._err.device != dev:
+            self._err = torch.zeros(1, dtype=torch.int32, device=dev)
+        if self.item_id and self.item_id in inputs:
+            self.item_seq = self.item_ids(inputs)
+        anchor = self.embedding_tables[names[0]].weight
+        if self.aggregation == "concat":
+            return _SeqEmbeddingsFn.apply(anchor, self, names, ids, self._err)
+        return {n: _SeqEmbeddingsFn.apply(self.embedding_tables[n].weight, self, [n], [i], self._err) for n, i in zip(names, ids)}
+
+    def forward_output_size(self, input_sizes=None):
+        return {n: torch.Size([-1, -1, t.embedding_dim]) for n, t in self.embedding_tables.items()}
+
+    def output_size(self, input_size=None):
+        sizes = self.forward_output_size()
+        if self.aggregation != "concat":
+            return sizes
+        return torch.Size([-1, -1, sum(s[-1] for s in sizes.values())])
 
 
 class TableConfig:

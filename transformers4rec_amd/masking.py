@@ -110,10 +110,14 @@ def enable_autograd_gradients(model, flag=True):
 
     params = hip_parameters(model) if flag else None
     n = 0
+    # a context module of a PostContextFusion is not the front of the path: the body's input block carries its parameters too
+    context = {id(c) for m in model.modules() if hasattr(m, "post_context_module") for c in m.post_context_module.modules()}
     for m in model.modules():
         is_hip_features = getattr(m, "_t4r_hip", False) and any(c.__name__ == "_HipFeaturesMixin" for c in type(m).__mro__)
         tgt = m.hip_shadow() if is_hip_features else m
-        if isinstance(tgt, TabularSequenceFeatures):
+        if isinstance(tgt, TabularSequenceFeatures) and id(m) in context:
+            object.__setattr__(tgt, "_t4r_carrier_params", None)
+        elif isinstance(tgt, TabularSequenceFeatures):
             object.__setattr__(tgt, "_t4r_carrier_params", params)
             n += 1
     if flag and n == 0:

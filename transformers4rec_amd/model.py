@@ -52,8 +52,9 @@ def last_rows_gate(model, training, B, L, n_labels=None):
         from .prediction_task import NextItemPredictionTask
 
         block, task, body = model.transformer_block, model.prediction_task, model.heads[0].body
-        # a session-level task reads every row of the body's output: the one task of the head must be the next-item task
-        kinds = (len(model.heads[0].prediction_task_dict) == 1 and type(block) is tfm.TransformerBlock and type(block.transformer) is tfm.XLNetModel
+        # a session-level task reads every row of the body's output: the one task of the head must be the next-item task;
+        # so does a post-context fusion: the body must be the plain one
+        kinds = (type(body) is _Body and len(model.heads[0].prediction_task_dict) == 1 and type(block) is tfm.TransformerBlock and type(block.transformer) is tfm.XLNetModel
                  and type(task) is NextItemPredictionTask and task.masking is not None and task.masking is body[0].masking
                  and type(task.masking) in (MaskedLanguageModeling, CausalLanguageModeling))
         parts = model.__dict__["_last_rows_parts"] = (block, block.transformer, task, body, kinds, {})
@@ -103,12 +104,20 @@ class Head(nn.Module):
 
 class Model(nn.Module):
     def __init__(self, input_features, transformer_block, prediction_task, max_sequence_length: Optional[int] = None,
-                 top_k: Optional[int] = None, exclude_seen: bool = False, task_weights=None, loss_reduction: str = "mean"):
+                 top_k: Optional[int] = None, exclude_seen: bool = False, task_weights=None, loss_reduction: str = "mean",
+                 post_context_module=None, fusion_aggregation: str = "elementwise-mul"):
         """prediction_task: one task or a list of them (NextItemPredictionTask, BinaryClassificationTask, RegressionTask), all
-        over the one body"""
+        over the one body.  post_context_module: context that does not go through the sequence model; the body then is
+        experimental.PostContextFusion around [input_features, transformer_block] (state-dict names
+        heads.0.body.sequential_module.{0,1}.*, .post_context_module.*, .context_projection.*) and the tasks see its last_dim"""
         super().__init__()
         body = _Body([input_features, transformer_block])
         hidden = transformer_block.transformer.config.hidden_size
+        if post_context_module is not None:
+            from .experimental import PostContextFusion
+
+            body = PostContextFusion(body, post_context_module, fusion_aggregation)
+            hidden = body.last_dim
         tasks = list(prediction_task) if isinstance(prediction_task, (list, tuple)) else [prediction_task]
         for task in tasks:
             task.build(body=body, input_size=(-1, -1, hidden), inputs=input_features)
@@ -118,12 +127,17 @@ class Model(nn.Module):
         self.exclude_seen = exclude_seen      # inference: drop the session's own items (NextItemPredictionTask.forward)
 
     @property
+    def _sequential(self):
+        body = self.heads[0].body
+        return body if isinstance(body, _Body) else body.sequential_module
+
+    @property
     def input_features(self):
-        return self.heads[0].body[0]
+        return self._sequential[0]
 
     @property
     def transformer_block(self):
-        return self.heads[0].body[1]
+        return self._sequential[1]
 
     @property
     def prediction_task(self):

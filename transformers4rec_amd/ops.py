@@ -2008,3 +2008,68 @@ def rtd_head_bwd_(g, x, active, labels, z, n_active, W1, b1, w2, act, d_W1=None,
          _chk(w2, torch.float32, "w2"), int(act), dx.data_ptr(), _p(d_W1, torch.float32, "d_W1"),
          _p(d_b1, torch.float32, "d_b1"), _p(d_w2, torch.float32, "d_w2"), _p(d_b2, torch.float32, "d_b2"), ws.data_ptr())
     return dx
+
+
+# ------------------------------------------------------------------------------------------------ post-context fusion
+# (include/t4r_hip_postfusion.h, csrc/post_fusion.hip): seq * (1 + Linear(ctx)), seq + Linear(ctx) or seq | ctx per token
+FUSION = {"elementwise-mul": 0, "elementwise-sum": 1, "concat": 2}
+FUSION_MUL, FUSION_SUM, FUSION_CONCAT = 0, 1, 2
+
+
+def post_fusion_supported(D, C):
+    return bool(_lib.load().t4r_post_fusion_supported(int(D), int(C)))
+
+
+def _post_fusion_args(what, seq, ctx, weight, bias, mode, width=None):
+    """checks both directions share -> (T, L, D, C, per_session); seq [B, L, D] (its place is taken by dout [B, L, width] in the
+    backward), ctx [B, L, C] or [B, C]"""
+    if not seq.is_cuda or not ctx.is_cuda:
+        raise _lib.T4RHipError(f"{what}: the tensors must live on the GPU (got {seq.device}, {ctx.device}); there is no CPU path")
+    if mode not in (0, 1, 2):
+        raise ValueError(f"{what}: mode must be 0 (elementwise-mul), 1 (elementwise-sum) or 2 (concat), got {mode}")
+    if seq.dim() != 3 or ctx.dim() not in (2, 3) or ctx.shape[0] != seq.shape[0] or (ctx.dim() == 3 and ctx.shape[1] != seq.shape[1]):
+        raise ValueError(f"{what}: seq must be [B, L, D] and ctx [B, L, C] or [B, C], got {tuple(seq.shape)} and {tuple(ctx.shape)}")
+    B, L, Dw = seq.shape
+    C = ctx.shape[-1]
+    D = Dw if width is None else width
+    if not (1 <= D <= 1024 and 1 <= C <= 256):
+        raise ValueError(f"{what}: D = {D}, C = {C} outside 1 <= D <= 1024, 1 <= C <= 256")
+    if mode == FUSION_CONCAT:
+        if weight is not None or bias is not None:
+            raise ValueError(f"{what}: concat has no parameters")
+    elif weight is None or bias is None or tuple(weight.shape) != (D, C) or tuple(bias.shape) != (D,):
+        raise ValueError(f"{what}: weight must be [{D}, {C}] and bias [{D}]")
+    return B * L, max(L, 1), D, C, int(ctx.dim() == 2)
+
+
+def post_fusion_fwd(seq, ctx, weight, bias, mode):
+    """seq [B, L, D], ctx [B, L, C] or -- session-level, row b serves every position of session b -- [B, C]; weight [D, C], bias
+    [D] (None for concat) -> out [B, L, D] = seq * (1 + p) (mode 0) or seq + p (1) with p = bias + ctx weight^T, or [B, L, D + C]
+    = seq | ctx (2).  One launch."""
+    T, L, D, C, per_session = _post_fusion_args("post_fusion_fwd", seq, ctx, weight, bias, mode)
+    out = torch.empty((seq.shape[0], seq.shape[1], D + C if mode == FUSION_CONCAT else D), device=seq.device, dtype=torch.float32)
+    call("t4r_post_fusion_fwd", _stream(), _chk(seq, torch.float32, "seq"), _chk(ctx, torch.float32, "ctx"),
+         _p(weight, torch.float32, "weight"), _p(bias, torch.float32, "bias"), out.data_ptr(), T, L, D, C, int(mode), per_session)
+    return out
+
+
+def post_fusion_bwd_(dout, seq, ctx, weight, bias, mode, d_w=None, d_b=None, want_dseq=True, want_dctx=True):
+    """the backward of post_fusion_fwd (p is recomputed; nothing is saved): -> (dseq [B, L, D] or None, dctx of ctx's shape or
+    None); the parameter gradients are ACCUMULATED into d_w [D, C] and d_b [D], either may be None.  seq may be None where it is
+    not read (modes 1 and 2).  Bit-reproducible (no float atomics).  At most three launches."""
+    D = weight.shape[0] if weight is not None else dout.shape[-1] - ctx.shape[-1]
+    T, L, D, C, per_session = _post_fusion_args("post_fusion_bwd_", dout, ctx, weight, bias, mode, width=D)
+    if dout.shape[-1] != (D + C if mode == FUSION_CONCAT else D):
+        raise ValueError(f"post_fusion_bwd_: dout's width {dout.shape[-1]} does not fit D = {D}, C = {C}, mode {mode}")
+    if mode == FUSION_MUL and (seq is None or tuple(seq.shape) != tuple(dout.shape)):
+        raise ValueError("post_fusion_bwd_: elementwise-mul needs seq of dout's shape")
+    if (d_w is not None and (weight is None or d_w.shape != weight.shape)) or (d_b is not None and (bias is None or d_b.shape != bias.shape)):
+        raise ValueError("post_fusion_bwd_: d_w and d_b must have the shapes of weight and bias")
+    dseq = torch.empty(tuple(dout.shape[:2]) + (D,), device=dout.device, dtype=torch.float32) if want_dseq else None
+    dctx = torch.empty_like(ctx) if want_dctx else None
+    ws = torch.empty(max(1, _lib.load().t4r_post_fusion_bwd_ws_floats(T, L, D, C, int(mode), per_session)), device=dout.device,
+                     dtype=torch.float32)
+    call("t4r_post_fusion_bwd", _stream(), _chk(dout, torch.float32, "dout"), _p(seq, torch.float32, "seq"),
+         _chk(ctx, torch.float32, "ctx"), _p(weight, torch.float32, "weight"), _p(bias, torch.float32, "bias"), _p(dseq), _p(dctx),
+         _p(d_w, torch.float32, "d_w"), _p(d_b, torch.float32, "d_b"), ws.data_ptr(), T, L, D, C, int(mode), per_session)
+    return dseq, dctx

@@ -880,10 +880,62 @@ def _(g, x, active, labels, z, n_active, W1, b1, w2, act):
     return x.new_empty(x.shape), W1.new_empty(W1.shape), b1.new_empty(b1.shape), w2.new_empty(w2.shape), x.new_empty((1,))
 
 
+# ------------------------------------------------------------------------------------------------ post-context fusion
+@torch.library.custom_op(f"{NS}::post_fusion", mutates_args=())
+def post_fusion(seq: torch.Tensor, ctx: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor],
+                mode: int) -> torch.Tensor:
+    """seq [B, L, D] fused with the context ctx [B, L, C] or [B, C] (repeated over L): mode 0 seq * (1 + Linear(ctx)), 1 seq +
+    Linear(ctx) -> [B, L, D]; 2 seq | ctx -> [B, L, D + C], weight and bias None (transformers4rec/torch/experimental.py:81-104;
+    include/t4r_hip_postfusion.h, csrc/post_fusion.hip)"""
+    return ops.post_fusion_fwd(seq.contiguous(), ctx.contiguous(), None if weight is None else weight.contiguous(),
+                               None if bias is None else bias.contiguous(), mode)
+
+
+@post_fusion.register_fake
+def _(seq, ctx, weight, bias, mode):
+    B, L, D = seq.shape
+    return seq.new_empty((B, L, D + ctx.shape[-1] if mode == ops.FUSION_CONCAT else D))
+
+
+@torch.library.custom_op(f"{NS}::post_fusion_bwd", mutates_args=())
+def post_fusion_bwd(dout: torch.Tensor, seq: torch.Tensor, ctx: torch.Tensor, weight: Optional[torch.Tensor],
+                    bias: Optional[torch.Tensor], mode: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """-> (d seq, d ctx, d weight, d bias) of post_fusion; the last two are empty [0] tensors for mode 2"""
+    has_w = weight is not None
+    d_w = torch.zeros_like(weight, memory_format=torch.contiguous_format) if has_w else dout.new_empty((0,))
+    d_b = torch.zeros_like(bias, memory_format=torch.contiguous_format) if has_w else dout.new_empty((0,))
+    dseq, dctx = ops.post_fusion_bwd_(dout.contiguous(), seq.contiguous(), ctx.contiguous(), weight.contiguous() if has_w else None,
+                                      bias.contiguous() if has_w else None, mode, d_w if has_w else None, d_b if has_w else None)
+    return dseq, dctx, d_w, d_b
+
+
+@post_fusion_bwd.register_fake
+def _(dout, seq, ctx, weight, bias, mode):
+    has_w = weight is not None
+    return (seq.new_empty(seq.shape), ctx.new_empty(ctx.shape), weight.new_empty(weight.shape) if has_w else dout.new_empty((0,)),
+            bias.new_empty(bias.shape) if has_w else dout.new_empty((0,)))
+
+
+def _pf_setup(ctx, inputs, output):
+    seq, c, weight, bias, mode = inputs
+    ctx.mode, ctx.has_w = mode, weight is not None
+    ctx.save_for_backward(seq, c, *([weight, bias] if ctx.has_w else []))
+
+
+def _pf_backward(ctx, dout):
+    seq, c, *wb = ctx.saved_tensors
+    g = torch.ops.t4r_hip.post_fusion_bwd(dout, seq, c, wb[0] if ctx.has_w else None, wb[1] if ctx.has_w else None, ctx.mode)
+    return g[0], g[1], (g[2] if ctx.has_w else None), (g[3] if ctx.has_w else None), None
+
+
+post_fusion.register_autograd(_pf_backward, setup_context=_pf_setup)
+
+
 OPERATORS = ("gemm", "item_scores", "topk", "item_topk", "item_sample", "gumbel_argmax", "item_eval", "pack_item_table",
              "pack_item_filter", "item_mask_", "item_topk_filtered", "item_sample_filtered", "rank_of_target", "embedding_gather", "embedding_bag", "ragged_to_padded",
              "xlnet_layer_infer", "xlnet_layer_uni_infer", "xlnet_layer_fwd", "xlnet_layer_bwd", "mlm_targets", "seq_item_embedding",
              "seq_item_embedding_bwd", "xlnet_layer_grad", "gather_label_rows", "scatter_label_rows", "linear_softmax_ce",
              "linear_softmax_ce_bwd", "dropout", "pos_emb_dropout", "next_item_head", "next_item_head_bwd",
              "soft_embedding", "soft_embedding_grad", "seq_concat", "seq_concat_grad", "linear_relu", "linear_relu_grad", "apply_mask",
-             "apply_mask_grad", "seq_task_fwd", "seq_task_bwd", "rtd_head_fwd", "rtd_head_bwd")
+             "apply_mask_grad", "seq_task_fwd", "seq_task_bwd", "rtd_head_fwd", "rtd_head_bwd",
+             "post_fusion", "post_fusion_bwd")
