@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("T4R_HIP_LIB") or os.path.join(_HERE, "lib", "libt4r_h
 HEADERS = ("t4r_hip.h", "t4r_hip_sampling.h", "t4r_hip_filter.h", "t4r_hip_optim.h", "t4r_hip_pretrained.h", "t4r_hip_attn.h",
            "t4r_hip_rows.h", "t4r_hip_rowadam.h", "t4r_hip_contproj.h", "t4r_hip_rowclip.h", "t4r_hip_seqtask.h", "t4r_hip_rtd.h")
 EXTENSION_HEADERS = ("t4r_hip_uni.h",)
-FEATURE_HEADERS = ("t4r_hip_postfusion.h",)
+FEATURE_HEADERS = ("t4r_hip_postfusion.h", "t4r_hip_mlpblock.h")
 
 
 def header_path(name):

@@ -31,6 +31,9 @@ def layer_params(model):
 def config_of(model):
     t = model.transformer_block.transformer
     m = model.input_features.masking
+    if getattr(model, "mlp_block", None) is not None:
+        raise NotImplementedError("functional: the operator-composed step restates the two-entry body only; a Model built with "
+                                  "mlp_block= trains through the module path (Model / block.MLPBlock)")
     if getattr(t.config, "attn_type", "bi") != "bi":
         raise NotImplementedError("functional: the operator-composed step restates the attn_type='bi' body only; an XLNet built "
                                   "with attn_type='uni' trains through the module path (Model / TransformerBlock)")

@@ -2,7 +2,8 @@
 (transformers4rec/torch/model/base.py:235-425, 544-598; block/base.py:236-262) reduced to one head
 -- with one or several prediction tasks, task_weights and loss_reduction --, with the reference's module tree names so
 state_dicts interchange:
-  heads.0.body.0 (TabularSequenceFeatures), heads.0.body.1 (TransformerBlock),
+  heads.0.body.0 (TabularSequenceFeatures), heads.0.body.1 (TransformerBlock) -- or, with mlp_block=, heads.0.body.1 (the built
+  MLPBlock, block.py) and heads.0.body.2 (TransformerBlock), the reference's SequentialBlock(inputs, MLPBlock, TransformerBlock),
   heads.0.prediction_task_dict.next-item (NextItemPredictionTask),
   heads.0.prediction_task_dict.<target>/binary_classification_task, .<target>/regression_task (session_task.py).
 Rewriting Model/Head/Trainer is out of scope; this exists so the path can
@@ -24,7 +25,9 @@ class _Body(nn.ModuleList):
     def forward(self, inputs, training=False, testing=False, out_rows=None, **kwargs):
         """out_rows: () -> (rows, n) or None, handed on to the transformer block, which asks it just before its last layer"""
         x = self[0](inputs, training=training, testing=testing)
-        return self[1](x) if out_rows is None else self[1](x, out_rows=out_rows)
+        if len(self) == 3:          # [inputs, MLP stack, transformer]
+            x = self[1](x, training=training)
+        return self[-1](x) if out_rows is None else self[-1](x, out_rows=out_rows)
 
 
 def last_rows_gate(model, training, B, L, n_labels=None):
@@ -105,13 +108,31 @@ class Head(nn.Module):
 class Model(nn.Module):
     def __init__(self, input_features, transformer_block, prediction_task, max_sequence_length: Optional[int] = None,
                  top_k: Optional[int] = None, exclude_seen: bool = False, task_weights=None, loss_reduction: str = "mean",
-                 post_context_module=None, fusion_aggregation: str = "elementwise-mul"):
+                 post_context_module=None, fusion_aggregation: str = "elementwise-mul", mlp_block=None):
         """prediction_task: one task or a list of them (NextItemPredictionTask, BinaryClassificationTask, RegressionTask), all
         over the one body.  post_context_module: context that does not go through the sequence model; the body then is
         experimental.PostContextFusion around [input_features, transformer_block] (state-dict names
-        heads.0.body.sequential_module.{0,1}.*, .post_context_module.*, .context_projection.*) and the tasks see its last_dim"""
+        heads.0.body.sequential_module.{0,1}.*, .post_context_module.*, .context_projection.*) and the tasks see its last_dim.
+        mlp_block: a block.MLPBlock (built here on input_features.output_size()) or a built one; the body then is
+        [input_features, the stack, transformer_block] (state-dict names heads.0.body.1.<i>.0.{weight,bias}, the transformer
+        under heads.0.body.2); the input block keeps its own width and the stack's last width must be the transformer's"""
         super().__init__()
-        body = _Body([input_features, transformer_block])
+        if mlp_block is None:
+            body = _Body([input_features, transformer_block])
+        else:
+            from .block import MLPBlock, MLPStack
+
+            if post_context_module is not None:
+                raise NotImplementedError("Model: mlp_block together with post_context_module is not supported.")
+            stack = mlp_block.build(input_features.output_size()) if isinstance(mlp_block, MLPBlock) else mlp_block
+            if not isinstance(stack, MLPStack):
+                raise TypeError(f"Model: mlp_block must be a block.MLPBlock or a built one, got {type(mlp_block).__name__}")
+            width = int(input_features.output_size()[-1])
+            d_model = int(transformer_block.transformer.config.hidden_size)
+            if stack.in_features != width or stack.out_features != d_model:
+                raise ValueError(f"Model: mlp_block maps {stack.in_features} -> {stack.out_features} columns, the input block "
+                                 f"gives {width} and the transformer takes {d_model}")
+            body = _Body([input_features, stack, transformer_block])
         hidden = transformer_block.transformer.config.hidden_size
         if post_context_module is not None:
             from .experimental import PostContextFusion
@@ -137,7 +158,13 @@ class Model(nn.Module):
 
     @property
     def transformer_block(self):
-        return self._sequential[1]
+        return self._sequential[-1]
+
+    @property
+    def mlp_block(self):
+        """the built MLPBlock of a three-entry body, else None"""
+        seq = self._sequential
+        return seq[1] if len(seq) == 3 else None
 
     @property
     def prediction_task(self):

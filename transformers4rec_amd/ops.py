@@ -2073,3 +2073,89 @@ def post_fusion_bwd_(dout, seq, ctx, weight, bias, mode, d_w=None, d_b=None, wan
          _chk(ctx, torch.float32, "ctx"), _p(weight, torch.float32, "weight"), _p(bias, torch.float32, "bias"), _p(dseq), _p(dctx),
          _p(d_w, torch.float32, "d_w"), _p(d_b, torch.float32, "d_b"), ws.data_ptr(), T, L, D, C, int(mode), per_session)
     return dseq, dctx
+
+
+# ------------------------------------------------------------------------------------------------ MLP block
+# (include/t4r_hip_mlpblock.h, csrc/mlp_block.hip): a stack of 1 .. 4 layers dropout(relu(Linear(.))) per token, one launch forward
+SITE_MLP_BLOCK = 8          # the dropout site of the block: ctr_hi of layer i = dropout_ctr_hi(offset, i, SITE_MLP_BLOCK)
+MLP_MAX_LAYERS, MLP_MAX_K0, MLP_MAX_N = 4, 1024, 512
+
+
+def mlp_stack_supported(K0, dims):
+    dims = [int(d) for d in dims]
+    if not dims:
+        return False
+    _, keep = int_array(dims)
+    return bool(_lib.load().t4r_mlp_stack_supported(len(dims), int(K0), keep))
+
+
+def _mlp_stack_args(what, x, weights, biases):
+    """checks both directions share -> (T, K0, dims); x [..., K0] (its place is taken by dout [..., N_last] in the backward)"""
+    if not x.is_cuda:
+        raise _lib.T4RHipError(f"{what}: the tensors must live on the GPU (got {x.device}); there is no CPU path")
+    n = len(weights)
+    if not 1 <= n <= MLP_MAX_LAYERS:
+        raise ValueError(f"{what}: 1 <= n <= {MLP_MAX_LAYERS} layers, got {n}")
+    if biases is not None and len(biases) != n:
+        raise ValueError(f"{what}: biases must be None or one entry (a tensor or None) per layer")
+    K0 = weights[0].shape[1]
+    dims, k = [], K0
+    for i, w in enumerate(weights):
+        if w.dim() != 2 or w.shape[1] != k:
+            raise ValueError(f"{what}: weight {i} must be [N_{i}, {k}], got {tuple(w.shape)}")
+        k = w.shape[0]
+        dims.append(k)
+        b = None if biases is None else biases[i]
+        if b is not None and tuple(b.shape) != (k,):
+            raise ValueError(f"{what}: bias {i} must be [{k}], got {tuple(b.shape)}")
+    if not (1 <= K0 <= MLP_MAX_K0 and all(1 <= d <= MLP_MAX_N for d in dims)):
+        raise ValueError(f"{what}: widths {K0} -> {dims} outside 1 <= K0 <= {MLP_MAX_K0}, 1 <= N_i <= {MLP_MAX_N}")
+    if x.dim() < 1:
+        raise ValueError(f"{what}: the input must have at least one dimension")
+    return (x.numel() // x.shape[-1] if x.shape[-1] else 0), K0, dims
+
+
+def mlp_stack_fwd(x, weights, biases=None, relu=True, drop=(0.0, 0, 0), save_acts=False):
+    """x [..., K0]; weights: n tensors [N_i, K_i] (torch.nn.Linear's layout), biases: None or n entries (tensor [N_i] or None);
+    drop = (p, seed, offset): dropout after every layer at site SITE_MLP_BLOCK of stream position `offset`.
+    -> out [..., N_last], or, save_acts (training), the list of every layer's output a_i [..., N_i] (the backward reads them).
+    One launch; without save_acts the intermediate activations never reach memory."""
+    T, K0, dims = _mlp_stack_args("mlp_stack_fwd", x, weights, biases)
+    if x.shape[-1] != K0:
+        raise ValueError(f"mlp_stack_fwd: the input is {x.shape[-1]} wide, the first weight takes {K0}")
+    n, lead = len(dims), tuple(x.shape[:-1])
+    outs = [torch.empty(lead + (d,), device=x.device, dtype=torch.float32) for d in (dims if save_acts else dims[-1:])]
+    Np, keepN = int_array(dims)
+    Wp, keepW = ptr_array([_chk(w, torch.float32, "weight") for w in weights])
+    Bp, keepB = (None, None) if biases is None else ptr_array([_p(b, torch.float32, "bias") for b in biases])
+    Ap, keepA = ptr_array([o.data_ptr() for o in outs]) if save_acts else (None, None)
+    call("t4r_mlp_stack_fwd", _stream(), _chk(x, torch.float32, "x"), Wp, Bp, Ap, None if save_acts else outs[0].data_ptr(), T, n, K0,
+         Np, int(bool(relu)), float(drop[0]), int(drop[1]), int(drop[2]))
+    return outs if save_acts else outs[0]
+
+
+def mlp_stack_bwd_(dout, x, weights, acts, relu=True, drop=(0.0, 0, 0), d_weights=None, d_biases=None, want_dx=True):
+    """the backward of mlp_stack_fwd(save_acts=True): -> dx [..., K0] or None; the parameter gradients are ACCUMULATED into
+    d_weights[i] [N_i, K_i] and d_biases[i] [N_i] (either list, and any entry, may be None).  x may be None where d_weights[0] and
+    d_biases[0] are.  Bit-reproducible (no float atomics).  At most three launches."""
+    T, K0, dims = _mlp_stack_args("mlp_stack_bwd_", dout, weights, None)
+    n = len(dims)
+    if dout.shape[-1] != dims[-1]:
+        raise ValueError(f"mlp_stack_bwd_: dout is {dout.shape[-1]} wide, the last layer gives {dims[-1]}")
+    if acts is None or len(acts) != n:
+        raise ValueError("mlp_stack_bwd_: acts must be the n tensors mlp_stack_fwd(save_acts=True) returned (entries may be None "
+                         "where they are not read)")
+    for name, lst, like in (("d_weights", d_weights, weights), ("d_biases", d_biases, [w[:, 0] for w in weights])):
+        if lst is not None and (len(lst) != n or any(g is not None and g.shape != p.shape for g, p in zip(lst, like))):
+            raise ValueError(f"mlp_stack_bwd_: {name} must be None or one entry (a tensor of the parameter's shape, or None) per layer")
+    lead = tuple(dout.shape[:-1])
+    dx = torch.empty(lead + (K0,), device=dout.device, dtype=torch.float32) if want_dx else None
+    Np, keepN = int_array(dims)
+    ws = torch.empty(max(1, _lib.load().t4r_mlp_stack_bwd_ws_floats(T, n, K0, Np)), device=dout.device, dtype=torch.float32)
+    Wp, keepW = ptr_array([_chk(w, torch.float32, "weight") for w in weights])
+    Ap, keepA = ptr_array([_p(t, torch.float32, "acts") for t in acts])
+    Gp, keepG = (None, None) if d_weights is None else ptr_array([_p(g, torch.float32, "d_weights") for g in d_weights])
+    Hp, keepH = (None, None) if d_biases is None else ptr_array([_p(g, torch.float32, "d_biases") for g in d_biases])
+    call("t4r_mlp_stack_bwd", _stream(), _chk(dout, torch.float32, "dout"), _p(x, torch.float32, "x"), Wp, Ap, _p(dx), Gp, Hp,
+         ws.data_ptr(), T, n, K0, Np, int(bool(relu)), float(drop[0]), int(drop[1]), int(drop[2]))
+    return dx

@@ -931,6 +931,61 @@ def _pf_backward(ctx, dout):
 post_fusion.register_autograd(_pf_backward, setup_context=_pf_setup)
 
 
+# ------------------------------------------------------------------------------------------------ MLP block
+@torch.library.custom_op(f"{NS}::mlp_stack", mutates_args=())
+def mlp_stack(x: torch.Tensor, weights: List[torch.Tensor], biases: List[torch.Tensor], relu: bool, drop_p: float,
+              seed: int, offset: int) -> torch.Tensor:
+    """x [..., K0] through the stack of len(weights) layers Linear (weights[i] [N_i, K_i], biases [] or one [N_i] per layer),
+    ReLU where relu, dropout where drop_p > 0 (site ops.SITE_MLP_BLOCK of stream position `offset`) -> [..., N_last]
+    (transformers4rec/torch/block/mlp.py; include/t4r_hip_mlpblock.h, csrc/mlp_block.hip).  One launch; the intermediate
+    activations stay on chip (the backward operator computes them again)."""
+    return ops.mlp_stack_fwd(x.contiguous(), [w.contiguous() for w in weights],
+                             [b.contiguous() for b in biases] or None, relu, (drop_p, seed, offset))
+
+
+@mlp_stack.register_fake
+def _(x, weights, biases, relu, drop_p, seed, offset):
+    return x.new_empty(tuple(x.shape[:-1]) + (weights[-1].shape[0],))
+
+
+@torch.library.custom_op(f"{NS}::mlp_stack_bwd", mutates_args=())
+def mlp_stack_bwd(dout: torch.Tensor, x: torch.Tensor, weights: List[torch.Tensor], biases: List[torch.Tensor], relu: bool,
+                  drop_p: float, seed: int, offset: int) -> List[torch.Tensor]:
+    """-> [d x, d weights[0], ..., d weights[n-1]] followed, where biases are given, by [d biases[0], ..., d biases[n-1]] of
+    mlp_stack; the activations are computed again from x (one more forward launch)"""
+    x = x.contiguous()
+    weights = [w.contiguous() for w in weights]
+    bs = [b.contiguous() for b in biases] or None
+    drop = (drop_p, seed, offset)
+    acts = ops.mlp_stack_fwd(x, weights, bs, relu, drop, save_acts=True)
+    d_w = [torch.zeros_like(w, memory_format=torch.contiguous_format) for w in weights]
+    d_b = None if bs is None else [torch.zeros_like(b, memory_format=torch.contiguous_format) for b in bs]
+    dx = ops.mlp_stack_bwd_(dout.contiguous(), x, weights, acts, relu, drop, d_w, d_b)
+    return [dx] + d_w + (d_b or [])
+
+
+@mlp_stack_bwd.register_fake
+def _(dout, x, weights, biases, relu, drop_p, seed, offset):
+    return [x.new_empty(x.shape)] + [w.new_empty(w.shape) for w in weights] + [b.new_empty(b.shape) for b in biases]
+
+
+def _mlp_setup(ctx, inputs, output):
+    x, weights, biases, ctx.relu, ctx.drop_p, ctx.seed, ctx.offset = inputs
+    ctx.n, ctx.has_b = len(weights), len(biases) > 0
+    ctx.save_for_backward(x, *weights, *biases)
+
+
+def _mlp_backward(ctx, dout):
+    x, *rest = ctx.saved_tensors
+    n = ctx.n
+    g = torch.ops.t4r_hip.mlp_stack_bwd(dout, x, list(rest[:n]), list(rest[n:]), ctx.relu, ctx.drop_p, ctx.seed,
+                                        ctx.offset)
+    return g[0], list(g[1:1 + n]), list(g[1 + n:]), None, None, None, None
+
+
+mlp_stack.register_autograd(_mlp_backward, setup_context=_mlp_setup)
+
+
 OPERATORS = ("gemm", "item_scores", "topk", "item_topk", "item_sample", "gumbel_argmax", "item_eval", "pack_item_table",
              "pack_item_filter", "item_mask_", "item_topk_filtered", "item_sample_filtered", "rank_of_target", "embedding_gather", "embedding_bag", "ragged_to_padded",
              "xlnet_layer_infer", "xlnet_layer_uni_infer", "xlnet_layer_fwd", "xlnet_layer_bwd", "mlm_targets", "seq_item_embedding",
@@ -938,4 +993,4 @@ OPERATORS = ("gemm", "item_scores", "topk", "item_topk", "item_sample", "gumbel_
              "linear_softmax_ce_bwd", "dropout", "pos_emb_dropout", "next_item_head", "next_item_head_bwd",
              "soft_embedding", "soft_embedding_grad", "seq_concat", "seq_concat_grad", "linear_relu", "linear_relu_grad", "apply_mask",
              "apply_mask_grad", "seq_task_fwd", "seq_task_bwd", "rtd_head_fwd", "rtd_head_bwd",
-             "post_fusion", "post_fusion_bwd")
+             "post_fusion", "post_fusion_bwd", "mlp_stack", "mlp_stack_bwd")
