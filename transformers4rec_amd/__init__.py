@@ -23,7 +23,7 @@ from .rtd import RTDModel, ReplacedTokenDetectionHead  # noqa: E402,F401
 from .model import Head, Model  # noqa: E402,F401
 from . import experimental  # noqa: E402,F401
 from . import block  # noqa: E402,F401
-from .block import MLPBlock  # noqa: E402,F401
+from .block import Block, GRUBlock, MLPBlock  # noqa: E402,F401
 from .optim import FlatParams, FusedAdam, RowSparseAdam, flatten_model, row_sparse_tables, warmup_schedule  # noqa: E402,F401
 from .distributed import GradReducer, SparseRowExchange, head_backward_hook, shard_batch  # noqa: E402,F401
 from .data import ParquetSessionLoader, read_ragged_columns  # noqa: E402,F401

@@ -2,8 +2,8 @@
 derived from those declarations (signatures()), so a new header is registered by adding its file name to HEADERS.
 EXTENSION_HEADERS are headers of the same library that are bound after the main ones (extension_signatures()): their names
 are not part of signatures() / header_symbols() / HEADERS, and may not repeat one of those.  FEATURE_HEADERS are bound after
-both (feature_signatures()), under the same rule: a later feature's header is appended to that tuple and changes neither of the
-other two.
+both (feature_signatures()), under the same rule: a later feature's header is added to that tuple (its order is not an
+interface: t4r_hip_gru.h stands between the two earlier ones) and changes neither of the other two.
 
 There is NO fallback: if the shared library is missing or a call fails the product path
 raises.  Build with `python -m transformers4rec_amd.build` (or __graft_entry__.build()).
@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("T4R_HIP_LIB") or os.path.join(_HERE, "lib", "libt4r_h
 HEADERS = ("t4r_hip.h", "t4r_hip_sampling.h", "t4r_hip_filter.h", "t4r_hip_optim.h", "t4r_hip_pretrained.h", "t4r_hip_attn.h",
            "t4r_hip_rows.h", "t4r_hip_rowadam.h", "t4r_hip_contproj.h", "t4r_hip_rowclip.h", "t4r_hip_seqtask.h", "t4r_hip_rtd.h")
 EXTENSION_HEADERS = ("t4r_hip_uni.h",)
-FEATURE_HEADERS = ("t4r_hip_postfusion.h", "t4r_hip_mlpblock.h")
+FEATURE_HEADERS = ("t4r_hip_postfusion.h", "t4r_hip_gru.h", "t4r_hip_mlpblock.h")
 
 
 def header_path(name):

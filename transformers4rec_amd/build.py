@@ -1,5 +1,5 @@
 """Builds libt4r_hip.so (all HIP kernels + the C ABI of include/t4r_hip.h, include/t4r_hip_sampling.h,
-include/t4r_hip_filter.h, include/t4r_hip_optim.h, include/t4r_hip_pretrained.h, include/t4r_hip_attn.h, include/t4r_hip_rows.h, include/t4r_hip_rowadam.h, include/t4r_hip_contproj.h, include/t4r_hip_rowclip.h, include/t4r_hip_seqtask.h, include/t4r_hip_rtd.h the extension header include/t4r_hip_uni.h and the feature headers include/t4r_hip_postfusion.h, include/t4r_hip_mlpblock.h) for gfx950 with
+include/t4r_hip_filter.h, include/t4r_hip_optim.h, include/t4r_hip_pretrained.h, include/t4r_hip_attn.h, include/t4r_hip_rows.h, include/t4r_hip_rowadam.h, include/t4r_hip_contproj.h, include/t4r_hip_rowclip.h, include/t4r_hip_seqtask.h, include/t4r_hip_rtd.h the extension header include/t4r_hip_uni.h and the feature headers include/t4r_hip_postfusion.h, include/t4r_hip_gru.h, include/t4r_hip_mlpblock.h) for gfx950 with
 hipcc, in-tree (transformers4rec_amd/lib/).  hipcc cross-compiles without a GPU.
 
     python -m transformers4rec_amd.build [--force]
@@ -17,7 +17,7 @@ SOURCES = ["gemm_f32.hip", "gemm_half.hip", "elementwise.hip", "embedding.hip", 
            "head.hip", "xlnet_layer.hip", "mha.hip", "swap_noise.hip", "xlnet_attn_mfma.hip", "mha_mfma.hip",
            "embedding_sorted.hip", "head_split.hip", "tok_gemm.hip", "embedding_bag.hip", "xlnet_fused.hip", "xlnet_fused_attn.hip", "xlnet_attn_block.hip",
            "xlnet_attn_long.hip", "item_topk.hip", "item_topk_h16.hip", "item_eval_h16.hip", "item_sample.hip", "item_filter.hip", "optim.hip",
-           "pretrained_proj.hip", "row_adam.hip", "cont_proj.hip", "seq_task.hip", "rtd_head.hip", "xlnet_attn_uni.hip", "post_fusion.hip", "mlp_block.hip"]
+           "pretrained_proj.hip", "row_adam.hip", "cont_proj.hip", "seq_task.hip", "rtd_head.hip", "xlnet_attn_uni.hip", "post_fusion.hip", "mlp_block.hip", "gru.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
          "-Wno-unused-result"]
 # per-source additions.  The head and the token-tile kernels: no NaN is ever looked at there (its maxima are over finite scores and -inf masks), and

@@ -29,6 +29,9 @@ def layer_params(model):
 
 
 def config_of(model):
+    if not hasattr(model.transformer_block, "transformer"):
+        raise NotImplementedError("functional: the operator-composed step restates the XLNet body only; a Model whose sequence "
+                                  "model is a GRUBlock trains through the module path (Model / block.GRUBlock)")
     t = model.transformer_block.transformer
     m = model.input_features.masking
     if getattr(model, "mlp_block", None) is not None:

@@ -60,7 +60,7 @@ def last_rows_gate(model, training, B, L, n_labels=None):
         kinds = (type(body) is _Body and len(model.heads[0].prediction_task_dict) == 1 and type(block) is tfm.TransformerBlock and type(block.transformer) is tfm.XLNetModel
                  and type(task) is NextItemPredictionTask and task.masking is not None and task.masking is body[0].masking
                  and type(task.masking) in (MaskedLanguageModeling, CausalLanguageModeling))
-        parts = model.__dict__["_last_rows_parts"] = (block, block.transformer, task, body, kinds, {})
+        parts = model.__dict__["_last_rows_parts"] = (block, getattr(block, "transformer", None), task, body, kinds, {})   # a GRUBlock has none: kinds is False
     block, xl, task, body, kinds, shapes = parts
     if not kinds or block.mask_padding or not task.weight_tying or not xl.training or not tfm._FUSED_ON:
         return None
@@ -77,6 +77,16 @@ def last_rows_gate(model, training, B, L, n_labels=None):
     if n < 1 or n > tfm._LAST_ROWS_MAX_FRACTION * B * L:
         return None
     return n
+
+
+def _block_widths(block):
+    """(input width, output width) of the sequence model in the body's last slot: a TransformerBlock or a block.GRUBlock"""
+    from .block import GRUBlock
+
+    if isinstance(block, GRUBlock):
+        return block.input_size, block.hidden_size
+    d_model = int(block.transformer.config.hidden_size)
+    return d_model, d_model
 
 
 class Head(nn.Module):
@@ -115,8 +125,13 @@ class Model(nn.Module):
         heads.0.body.sequential_module.{0,1}.*, .post_context_module.*, .context_projection.*) and the tasks see its last_dim.
         mlp_block: a block.MLPBlock (built here on input_features.output_size()) or a built one; the body then is
         [input_features, the stack, transformer_block] (state-dict names heads.0.body.1.<i>.0.{weight,bias}, the transformer
-        under heads.0.body.2); the input block keeps its own width and the stack's last width must be the transformer's"""
+        under heads.0.body.2); the input block keeps its own width and the stack's last width must be the transformer's.
+        transformer_block: a TransformerBlock, or a block.GRUBlock (the reference's Block(torch.nn.GRU)): the slot keeps its
+        name, the widths are the block's input_size / hidden_size, any masking module is accepted"""
         super().__init__()
+        d_in, hidden = _block_widths(transformer_block)
+        if post_context_module is not None and not hasattr(transformer_block, "transformer"):
+            raise NotImplementedError("Model: post_context_module together with a GRUBlock is not supported.")
         if mlp_block is None:
             body = _Body([input_features, transformer_block])
         else:
@@ -128,12 +143,10 @@ class Model(nn.Module):
             if not isinstance(stack, MLPStack):
                 raise TypeError(f"Model: mlp_block must be a block.MLPBlock or a built one, got {type(mlp_block).__name__}")
             width = int(input_features.output_size()[-1])
-            d_model = int(transformer_block.transformer.config.hidden_size)
-            if stack.in_features != width or stack.out_features != d_model:
+            if stack.in_features != width or stack.out_features != d_in:
                 raise ValueError(f"Model: mlp_block maps {stack.in_features} -> {stack.out_features} columns, the input block "
-                                 f"gives {width} and the transformer takes {d_model}")
+                                 f"gives {width} and the transformer takes {d_in}")
             body = _Body([input_features, stack, transformer_block])
-        hidden = transformer_block.transformer.config.hidden_size
         if post_context_module is not None:
             from .experimental import PostContextFusion
 

@@ -2159,3 +2159,89 @@ def mlp_stack_bwd_(dout, x, weights, acts, relu=True, drop=(0.0, 0, 0), d_weight
     call("t4r_mlp_stack_bwd", _stream(), _chk(dout, torch.float32, "dout"), _p(x, torch.float32, "x"), Wp, Ap, _p(dx), Gp, Hp,
          ws.data_ptr(), T, n, K0, Np, int(bool(relu)), float(drop[0]), int(drop[1]), int(drop[2]))
     return dx
+
+
+# ------------------------------------------------------------------------------------------------ GRU body
+# (include/t4r_hip_gru.h, csrc/gru.hip): a stack of 1 .. 4 GRU layers over [B, L, K0], one launch per layer for the time loop
+SITE_GRU = 9                # the dropout site between the layers: ctr_hi of layer k = dropout_ctr_hi(offset, k, SITE_GRU)
+GRU_MAX_LAYERS, GRU_MAX_K0, GRU_MAX_H, GRU_MAX_L = 4, 1024, 128, 1023
+
+
+def gru_supported(n, K0, H, L=1):
+    return bool(_lib.load().t4r_gru_supported(int(n), int(K0), int(H), int(L)))
+
+
+def _gru_args(what, x, w_ih, w_hh, b_ih, b_hh, h0, width):
+    """checks both directions share -> (B, L, n, K0, H); x [B, L, width] (its place is taken by dout [B, L, H] in the backward)"""
+    if not x.is_cuda:
+        raise _lib.T4RHipError(f"{what}: the tensors must live on the GPU (got {x.device}); there is no CPU path")
+    n = len(w_ih)
+    if not 1 <= n <= GRU_MAX_LAYERS or len(w_hh) != n:
+        raise ValueError(f"{what}: 1 <= n <= {GRU_MAX_LAYERS} layers with one W_ih and one W_hh each, got {n} and {len(w_hh)}")
+    if x.dim() != 3:
+        raise ValueError(f"{what}: the input must be [B, L, width] (batch_first), got {tuple(x.shape)}")
+    H, K0 = w_hh[0].shape[1], w_ih[0].shape[1]
+    for k in range(n):
+        K = K0 if k == 0 else H
+        if tuple(w_ih[k].shape) != (3 * H, K) or tuple(w_hh[k].shape) != (3 * H, H):
+            raise ValueError(f"{what}: layer {k} must have W_ih [{3 * H}, {K}] and W_hh [{3 * H}, {H}], got "
+                             f"{tuple(w_ih[k].shape)} and {tuple(w_hh[k].shape)}")
+        for name, bs in (("b_ih", b_ih), ("b_hh", b_hh)):
+            if bs is not None and (len(bs) != n or (bs[k] is not None and tuple(bs[k].shape) != (3 * H,))):
+                raise ValueError(f"{what}: {name} must be None or one entry ([{3 * H}] or None) per layer")
+    B, L = int(x.shape[0]), int(x.shape[1])
+    if x.shape[2] != (K0 if width == "in" else H):
+        raise ValueError(f"{what}: the tensor is {x.shape[2]} wide, expected {K0 if width == 'in' else H}")
+    if not gru_supported(n, K0, H, max(L, 1)) or L < 1:
+        raise ValueError(f"{what}: n {n}, K0 {K0}, H {H}, L {L} outside 1 <= n <= {GRU_MAX_LAYERS}, 1 <= K0 <= {GRU_MAX_K0}, "
+                         f"1 <= H <= {GRU_MAX_H}, 1 <= L <= {GRU_MAX_L}")
+    if h0 is not None and tuple(h0.shape) != (n, B, H):
+        raise ValueError(f"{what}: h0 must be None or [{n}, {B}, {H}], got {tuple(h0.shape)}")
+    return B, L, n, K0, H
+
+
+def _gru_ptrs(lst, name):
+    return (None, None) if lst is None else ptr_array([_p(t, torch.float32, name) for t in lst])
+
+
+def gru_fwd(x, w_ih, w_hh, b_ih=None, b_hh=None, h0=None, drop=(0.0, 0, 0), save=False):
+    """x [B, L, K0]; w_ih: n tensors [3H, K_k], w_hh: n tensors [3H, H] (torch.nn.GRU's layout, gates r | z | n), b_ih / b_hh: None
+    or n entries (tensor [3H] or None); h0: None or [n, B, H]; drop = (p, seed, offset): dropout between the layers at site
+    SITE_GRU of stream position `offset`.  -> out [B, L, H], or, save (training), (out, saved) with `saved` what gru_bwd_ reads.
+    Two launches per layer, none per time step."""
+    B, L, n, K0, H = _gru_args("gru_fwd", x, w_ih, w_hh, b_ih, b_hh, h0, "in")
+    lib = _lib.load()
+    out = torch.empty((B, L, H), device=x.device, dtype=torch.float32)
+    saved = torch.empty(max(1, lib.t4r_gru_saved_floats(B, L, n, K0, H)), device=x.device, dtype=torch.float32) if save else None
+    ws = torch.empty(max(1, lib.t4r_gru_fwd_ws_floats(B, L, n, K0, H)), device=x.device, dtype=torch.float32)
+    Ip, keepI = ptr_array([_chk(w, torch.float32, "w_ih") for w in w_ih])
+    Hp, keepH = ptr_array([_chk(w, torch.float32, "w_hh") for w in w_hh])
+    Bi, keepBi = _gru_ptrs(b_ih, "b_ih")
+    Bh, keepBh = _gru_ptrs(b_hh, "b_hh")
+    call("t4r_gru_fwd", _stream(), _chk(x, torch.float32, "x"), _p(h0, torch.float32, "h0"), Ip, Hp, Bi, Bh, out.data_ptr(),
+         _p(saved), ws.data_ptr(), B, L, n, K0, H, float(drop[0]), int(drop[1]), int(drop[2]))
+    return (out, saved) if save else out
+
+
+def gru_bwd_(dout, x, w_ih, w_hh, out, saved, h0=None, drop=(0.0, 0, 0), d_w_ih=None, d_w_hh=None, d_b_ih=None, d_b_hh=None,
+             want_dx=True):
+    """the backward of gru_fwd(save=True): -> dx [B, L, K0] or None; the parameter gradients are ACCUMULATED into d_w_ih[k],
+    d_w_hh[k], d_b_ih[k], d_b_hh[k] (any list, and any entry, may be None).  x may be None where d_w_ih[0] and d_b_ih[0] are.
+    Bit-reproducible (no float atomics).  At most four launches per layer."""
+    B, L, n, K0, H = _gru_args("gru_bwd_", dout, w_ih, w_hh, None, None, h0, "out")
+    for name, lst, like in (("d_w_ih", d_w_ih, w_ih), ("d_w_hh", d_w_hh, w_hh), ("d_b_ih", d_b_ih, [w[:, 0] for w in w_ih]),
+                            ("d_b_hh", d_b_hh, [w[:, 0] for w in w_hh])):
+        if lst is not None and (len(lst) != n or any(g is not None and g.shape != p.shape for g, p in zip(lst, like))):
+            raise ValueError(f"gru_bwd_: {name} must be None or one entry (a tensor of the parameter's shape, or None) per layer")
+    lib = _lib.load()
+    if tuple(out.shape) != (B, L, H) or saved is None or saved.numel() < lib.t4r_gru_saved_floats(B, L, n, K0, H):
+        raise ValueError("gru_bwd_: out and saved must be what gru_fwd(save=True) returned")
+    dx = torch.empty((B, L, K0), device=dout.device, dtype=torch.float32) if want_dx else None
+    ws = torch.empty(max(1, lib.t4r_gru_bwd_ws_floats(B, L, n, K0, H)), device=dout.device, dtype=torch.float32)
+    Ip, keepI = ptr_array([_chk(w, torch.float32, "w_ih") for w in w_ih])
+    Hp, keepH = ptr_array([_chk(w, torch.float32, "w_hh") for w in w_hh])
+    G = [_gru_ptrs(g, nm) for g, nm in ((d_w_ih, "d_w_ih"), (d_w_hh, "d_w_hh"), (d_b_ih, "d_b_ih"), (d_b_hh, "d_b_hh"))]
+    call("t4r_gru_bwd", _stream(), _chk(dout, torch.float32, "dout"), _p(x, torch.float32, "x"), _p(h0, torch.float32, "h0"), Ip, Hp,
+         _chk(out, torch.float32, "out"), _chk(saved, torch.float32, "saved"), _p(dx), G[0][0], G[1][0], G[2][0], G[3][0],
+         ws.data_ptr(), B, L, n, K0, H, float(drop[0]), int(drop[1]), int(drop[2]))
+    return dx

@@ -986,6 +986,64 @@ def _mlp_backward(ctx, dout):
 mlp_stack.register_autograd(_mlp_backward, setup_context=_mlp_setup)
 
 
+# ------------------------------------------------------------------------------------------------ GRU body
+@torch.library.custom_op(f"{NS}::gru_fwd", mutates_args=())
+def gru_fwd(x: torch.Tensor, w_ih: List[torch.Tensor], w_hh: List[torch.Tensor], b_ih: List[torch.Tensor],
+            b_hh: List[torch.Tensor], drop_p: float, seed: int, offset: int) -> torch.Tensor:
+    """x [B, L, K0] through len(w_ih) GRU layers (w_ih[k] [3H, K_k], w_hh[k] [3H, H], b_ih / b_hh [] or one [3H] per layer; gate
+    order r | z | n, batch_first), dropout between the layers where drop_p > 0 (site ops.SITE_GRU of stream position `offset`)
+    -> [B, L, H], the last layer's output (torch.nn.GRU in a Block, transformers4rec/torch/block/base.py:87-106;
+    include/t4r_hip_gru.h, csrc/gru.hip).  Two launches per layer (the backward operator runs the forward again)."""
+    return ops.gru_fwd(x.contiguous(), [w.contiguous() for w in w_ih], [w.contiguous() for w in w_hh],
+                       [b.contiguous() for b in b_ih] or None, [b.contiguous() for b in b_hh] or None, None,
+                       (drop_p, seed, offset))
+
+
+@gru_fwd.register_fake
+def _(x, w_ih, w_hh, b_ih, b_hh, drop_p, seed, offset):
+    return x.new_empty(tuple(x.shape[:-1]) + (w_hh[-1].shape[1],))
+
+
+@torch.library.custom_op(f"{NS}::gru_bwd", mutates_args=())
+def gru_bwd(dout: torch.Tensor, x: torch.Tensor, w_ih: List[torch.Tensor], w_hh: List[torch.Tensor], b_ih: List[torch.Tensor],
+            b_hh: List[torch.Tensor], drop_p: float, seed: int, offset: int) -> List[torch.Tensor]:
+    """-> [d x, d w_ih[0 .. n-1], d w_hh[0 .. n-1]] followed, where the biases are given, by [d b_ih[0 .. n-1]] and
+    [d b_hh[0 .. n-1]] of gru_fwd; the gate values are computed again from x (one more forward)"""
+    x = x.contiguous()
+    w_ih, w_hh = [w.contiguous() for w in w_ih], [w.contiguous() for w in w_hh]
+    bi, bh = [b.contiguous() for b in b_ih] or None, [b.contiguous() for b in b_hh] or None
+    drop = (drop_p, seed, offset)
+    out, saved = ops.gru_fwd(x, w_ih, w_hh, bi, bh, None, drop, save=True)
+    zeros = lambda ts: None if ts is None else [torch.zeros_like(t, memory_format=torch.contiguous_format) for t in ts]  # noqa: E731
+    d_wi, d_wh, d_bi, d_bh = zeros(w_ih), zeros(w_hh), zeros(bi), zeros(bh)
+    dx = ops.gru_bwd_(dout.contiguous(), x, w_ih, w_hh, out, saved, None, drop, d_wi, d_wh, d_bi, d_bh)
+    return [dx] + d_wi + d_wh + (d_bi or []) + (d_bh or [])
+
+
+@gru_bwd.register_fake
+def _(dout, x, w_ih, w_hh, b_ih, b_hh, drop_p, seed, offset):
+    return [x.new_empty(x.shape)] + [w.new_empty(w.shape) for w in list(w_ih) + list(w_hh)] + \
+        [b.new_empty(b.shape) for b in list(b_ih) + list(b_hh)]
+
+
+def _gru_setup(ctx, inputs, output):
+    x, w_ih, w_hh, b_ih, b_hh, ctx.drop_p, ctx.seed, ctx.offset = inputs
+    ctx.n, ctx.n_bi, ctx.n_bh = len(w_ih), len(b_ih), len(b_hh)
+    ctx.save_for_backward(x, *w_ih, *w_hh, *b_ih, *b_hh)
+
+
+def _gru_backward(ctx, dout):
+    x, *rest = ctx.saved_tensors
+    n, n_bi = ctx.n, ctx.n_bi
+    w_ih, w_hh, b_ih, b_hh = rest[:n], rest[n:2 * n], rest[2 * n:2 * n + n_bi], rest[2 * n + n_bi:]
+    g = torch.ops.t4r_hip.gru_bwd(dout, x, list(w_ih), list(w_hh), list(b_ih), list(b_hh), ctx.drop_p, ctx.seed, ctx.offset)
+    return (g[0], list(g[1:1 + n]), list(g[1 + n:1 + 2 * n]), list(g[1 + 2 * n:1 + 2 * n + n_bi]), list(g[1 + 2 * n + n_bi:]),
+            None, None, None)
+
+
+gru_fwd.register_autograd(_gru_backward, setup_context=_gru_setup)
+
+
 OPERATORS = ("gemm", "item_scores", "topk", "item_topk", "item_sample", "gumbel_argmax", "item_eval", "pack_item_table",
              "pack_item_filter", "item_mask_", "item_topk_filtered", "item_sample_filtered", "rank_of_target", "embedding_gather", "embedding_bag", "ragged_to_padded",
              "xlnet_layer_infer", "xlnet_layer_uni_infer", "xlnet_layer_fwd", "xlnet_layer_bwd", "mlm_targets", "seq_item_embedding",
@@ -993,4 +1051,4 @@ OPERATORS = ("gemm", "item_scores", "topk", "item_topk", "item_sample", "gumbel_
              "linear_softmax_ce_bwd", "dropout", "pos_emb_dropout", "next_item_head", "next_item_head_bwd",
              "soft_embedding", "soft_embedding_grad", "seq_concat", "seq_concat_grad", "linear_relu", "linear_relu_grad", "apply_mask",
              "apply_mask_grad", "seq_task_fwd", "seq_task_bwd", "rtd_head_fwd", "rtd_head_bwd",
-             "post_fusion", "post_fusion_bwd", "mlp_stack", "mlp_stack_bwd")
+             "post_fusion", "post_fusion_bwd", "mlp_stack", "mlp_stack_bwd", "gru_fwd", "gru_bwd")
